@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
 """Headline benchmark: training samples/s of the fusion hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (one rank per GPU, RCCL).  A step = zero_grad -> forward -> sigmoid focal loss (soft target) ->
 backward (-> bucketed gradient all-reduce overlapped with backward) -> AdamW step, train mode with
 the reference's dropout 0.1 and batch-statistics BatchNorm, on one synthetic batch that is already
 resident in HBM.  Workload = BASELINE.json configs[2] (full camera+LiDAR+radar+GPS fusion, 5-step
 sequence, bs=12 per GPU); configs[1] ("image-only") is the same compute with zeroed LiDAR/radar
- and configs[0] is the CPU plumbing case timed here as `cpu_baseline`.
+ and configs[0] is the CPU plumbing case timed under --full as `cpu_baseline`.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+A plain run sets up, runs W warm-up and K timed steps and prints ONE JSON line on rank 0 with the contract fields
+(`value` = samples/s of the K timed steps, `ms_per_step` = wall-clock milliseconds of one timed step).  Model weights,
+batch and dropout seeds are fixed, so the same arguments give the same inputs on every run.
+  --dump-outputs DIR : after the timed steps, rank 0 writes what the last timed step computed as float32 DIR/<name>.npy:
+                       `loss` and `logits` (what the step returns) and a fixed seeded sample of the parameter and
+                       gradient arenas the step left behind (`params_sample`, `grads_sample`; 16 MiB in all)
+  --full             : after the timed steps (never inside them) the line also carries the legs below; the --no-* options
+                       switch single legs off.  A plain run reports them as null.
   roofline     : dominant kernel = the matrix-core kernel with the largest share of step time; achieved = the MFMA
                  FLOPs its launches EXECUTE / their HIP-event time, measured live in one extra instrumented step
                  (single stream, so brackets are not inflated by the concurrent trunk streams of the timed region);
@@ -187,6 +194,34 @@ def pmc_traffic_table():
         if os.path.exists(path):
             return {k: v["hbm_bytes_per_launch"] for k, v in json.load(open(path))["kernels"].items()}
     return {}
+
+
+DUMP_SAMPLE = 1 << 21        # arena elements kept by --dump-outputs per sampled arena (8 MiB of float32 each)
+DUMP_SEED = 20261016
+DUMP_MAX_BYTES = 64_000_000
+
+
+def step_outputs(loss, logits, model):
+    """What a caller of the timed step receives, as float32 numpy arrays: the loss and logits train_iteration /
+    CapturedTrainStep.step return, and the model the step updated - a fixed seeded sample (same indices on every run) of
+    the parameter arena after the AdamW update and of the gradient arena that update consumed (the whole arenas are
+    ~300 MB each)."""
+    import numpy as np
+    params, grads = model.flat_parameters()
+    n = params.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    idx = torch.from_numpy(idx).to(params.device)
+    out = {"loss": loss, "logits": logits, "params_sample": params[idx], "grads_sample": grads[idx]}
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 class IgemmTimer:
@@ -392,6 +427,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=12, help="per-GPU batch (sequences)")
     ap.add_argument("--ema", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, seeded parameter / gradient samples) as "
+                         "float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline step, hbm_families / eval / seq10, the other "
+                         "matrix-core modes, the held-out DBA leg and the CPU baseline (off: the headline line only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt-modes", action="store_true",
                     help="skip the extra f32x3 / f32x6 / bf16 / bf16-image-only timings beside the exact-fp32 value")
@@ -421,6 +462,8 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-oracle steps at --cpu-batch (after 1 warm-up)")
     ap.add_argument("--cpu-small-steps", type=int, default=10, help="timed CPU-oracle steps at bs=2 (after 3 warm-up); 0 = skip")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from deepsense6g_tii_amd import dist as ddist
     from deepsense6g_tii_amd import ops
@@ -478,7 +521,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = run_step()
+        loss, logits = run_step()
     sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -486,26 +529,29 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:   # before anything below takes another step on the model
+        dump_outputs(args.dump_outputs, step_outputs(loss, logits, model))
 
     # ---- roofline of the dominant kernel: one extra instrumented step (not part of the timed region) ----
     roof = None
-    timer = IgemmTimer()
-    timer.install()
     ms_flag = model.multi_stream
-    model.multi_stream = False  # kernels of concurrent trunk streams would inflate each other's event brackets
-    try:
-        train_iteration(model, opt, batch, ema, reducer)
-        agg = timer.summary()
-    finally:
-        model.multi_stream = ms_flag
-    if agg:
-        table = pmc_traffic_table()
-        roof = roofline_from_records(agg, args.dtype, lambda v: table.get(variant_name(v, args.dtype)))
+    if args.full:
+        timer = IgemmTimer()
+        timer.install()
+        model.multi_stream = False  # kernels of concurrent trunk streams would inflate each other's event brackets
+        try:
+            train_iteration(model, opt, batch, ema, reducer)
+            agg = timer.summary()
+        finally:
+            model.multi_stream = ms_flag
+        if agg:
+            table = pmc_traffic_table()
+            roof = roofline_from_records(agg, args.dtype, lambda v: table.get(variant_name(v, args.dtype)))
 
     # ---- the HBM-bound kernel families of the same step, the eval-mode forward (f2) and the seq_len-10 variant (f4):
     # separate untimed legs of a few seconds each
     hbm = ev = None
-    if rank == 0 and world == 1 and not args.no_extra_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_legs:
         try:
             hbm = hbm_families(model, opt, batch, ema, reducer)
         except Exception as e:
@@ -518,7 +564,7 @@ def main():
     # ---- the other matrix-core modes next to the exact one (same model / timing protocol; reported beside `value`, never
     # as it): split-bf16 on the same batch, and the bf16 configuration BASELINE configs[1] names ----
     alt = None
-    if args.dtype == "f32" and not args.no_alt_modes:
+    if args.full and args.dtype == "f32" and not args.no_alt_modes:
         what = {"f32x3": "split-bf16 products (hi*hi + hi*lo + lo*hi, ~2^-16), fp32 accumulate and storage; "
                          "ds6g_set_compute_mode(2); Winograd off (direct implicit GEMM); tests/test_bf16_gpu.py",
                 "f32x6": "three-way bf16 split, six products (fp32-grade, ~2^-23) in the direct kernels and attention, fp32 "
@@ -581,14 +627,14 @@ def main():
 
     # ---- the second half of the metric: held-out DBA / top-k after a short training run on the HIP path ----
     dba = None
-    if rank == 0 and world == 1 and not args.no_dba and args.dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_dba and args.dtype == "f32":
         try:
             dba = dba_leg(dev, steps=args.dba_steps)
         except Exception as e:
             dba = {"error": repr(e)}
 
     seq10 = None
-    if rank == 0 and world == 1 and not args.no_extra_legs and args.dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_extra_legs and args.dtype == "f32":
         del model, opt
         torch.cuda.empty_cache()
         try:
@@ -597,7 +643,7 @@ def main():
             seq10 = {"error": repr(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_batch, args.cpu_steps, 1, 2, args.cpu_small_steps, 3)
 
     if rank == 0:
@@ -616,6 +662,7 @@ def main():
             "vs_baseline": None,
             "dtype": args.dtype,
             "data": "synthetic",
+            "full": bool(args.full),
             "config": {"workload": ("BASELINE configs[1]: image-only (LiDAR / radar inputs zeroed), " if args.image_only else
                                     "BASELINE configs[2]: full camera+LiDAR+radar+GPS fusion, ") +
                                    f"5x(3+1+2)x256x256 + 2x2 GPS per sample, bs={args.batch} per GPU, sigmoid focal loss, "

@@ -325,6 +325,39 @@ def test_bench_roofline_fraction_is_an_executed_fraction():
     assert roof["frac"] <= 1.0 and roof["largest_direct_kernel"]["frac"] <= 1.0
 
 
+def test_bench_dump_outputs_are_float32_within_budget_and_sample_fixed_indices(tmp_path):
+    """bench.py --dump-outputs: loss / logits as returned, the same seeded arena indices on every call, float32 .npy files,
+    at most 64 MB in all at the real arena size."""
+    import bench
+
+    class Model:   # flat_parameters() of the benchmark's TransFuser: 78 422 528 fp32 parameters + as many gradients
+        def __init__(self, n):
+            self.p = torch.arange(n, dtype=torch.float32)
+            self.g = -self.p
+
+        def flat_parameters(self):
+            return self.p, self.g
+
+    n = 78_422_528
+    loss, logits = torch.tensor([0.5]), torch.randn(12, 64, dtype=torch.float64)
+    a = bench.step_outputs(loss, logits, Model(n))
+    b = bench.step_outputs(loss, logits, Model(n))
+    assert set(a) == {"loss", "logits", "params_sample", "grads_sample"}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["params_sample"], b["params_sample"])
+    idx = a["params_sample"].astype(np.int64)          # arange arena: the values are the sampled indices (exact < 2^24)
+    assert idx.size == bench.DUMP_SAMPLE and np.all(np.diff(idx[idx < (1 << 24)]) > 0)
+    assert np.array_equal(a["grads_sample"], -a["params_sample"])
+    assert np.array_equal(a["logits"], logits.float().numpy()) and a["loss"].shape == (1,)
+    bench.dump_outputs(str(tmp_path / "out"), a)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["grads_sample.npy", "logits.npy", "loss.npy", "params_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= bench.DUMP_MAX_BYTES == 64_000_000
+    assert np.array_equal(np.load(tmp_path / "out" / "logits.npy"), a["logits"])
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(16_000_001, np.float32)})
+
+
 def test_train_pieces_match_reference_run(tmp_path):
     """The product's host-side training pieces (train.py) against outputs of the REFERENCE's own functions
     (tests/golden/train_golden.npz <- tests/golden/make_golden_train.py: train2_seq.py:338-383, scheduler.py:82-119)."""

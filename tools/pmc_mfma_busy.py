@@ -1,5 +1,5 @@
 """Post-processes a `rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv` pass over
-`bench.py --steps 1 --warmup 1 --single-stream --no-cpu-baseline --no-alt-modes` into profiles/<round>_pmc_mfma_busy.json:
+`bench.py --steps 1 --warmup 1 --full --single-stream --no-cpu-baseline --no-alt-modes` into profiles/<round>_pmc_mfma_busy.json:
 per kernel the clock (GRBM_GUI_ACTIVE / 8 XCDs / duration) and the matrix-core busy fraction
 (MFMA busy cycles / (1024 SIMDs x cycles)).
 usage: python tools/pmc_mfma_busy.py <counter_collection.csv> <out.json>"""
@@ -27,7 +27,7 @@ for k, (n, gui, mf, ns) in sorted(acc.items(), key=lambda kv: -kv[1][3]):
     cyc = gui / 8.0
     out[k] = dict(launches=n, total_ms=ns / 1e6, clock_ghz=cyc / ns, mfma_busy_frac=(mf / (1024.0 * cyc)) if cyc else 0.0)
 json.dump(dict(note="rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE over `bench.py --steps 1 --warmup 1 "
-                    "--single-stream` (3 steps); clock = GRBM_GUI_ACTIVE/8 XCDs/duration (inflated for kernels of a few "
+                    "--full --single-stream` (3 steps); clock = GRBM_GUI_ACTIVE/8 XCDs/duration (inflated for kernels of a few "
                     "microseconds); mfma_busy_frac = MFMA busy cycles / (1024 SIMDs x cycles)", kernels=out),
           open(sys.argv[2], "w"), indent=1)
 print(len(out), "kernels ->", sys.argv[2])

@@ -1,5 +1,5 @@
 """Post-processes the two rocprofv3 PMC passes (separate --pmc FETCH_SIZE / --pmc WRITE_SIZE runs of
-`bench.py --steps 1 --warmup 1 --single-stream --no-cpu-baseline`, --output-format csv) into
+`bench.py --steps 1 --warmup 1 --full --single-stream --no-cpu-baseline`, --output-format csv) into
 profiles/<round>_pmc_traffic.json: HBM-side bytes per launch for every kernel, corrected as
 /opt/skills/guides/MI355X_MICROARCH.md prescribes (counter unit KiB -> x1024; FETCH_SIZE x2 on gfx950 for wide reads).
 usage: python tools/pmc_traffic.py <fetch_counter_collection.csv> <write_counter_collection.csv> <out.json>"""
@@ -34,7 +34,7 @@ def main():
         wr = w[k][1] * 1024 / w[k][0] if k in w else 0.0
         kernels[k] = dict(launches=n, read_bytes_per_launch=rd, write_bytes_per_launch=wr, hbm_bytes_per_launch=rd + wr)
     json.dump(dict(note="rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 1 "
-                        "--warmup 1 --single-stream --no-cpu-baseline` (3 steps incl. the instrumented one); bytes = "
+                        "--warmup 1 --full --single-stream --no-cpu-baseline` (3 steps incl. the instrumented one); bytes = "
                         "KiB*1024, FETCH x2 (gfx950 wide-read correction)", kernels=kernels), open(out, "w"), indent=1)
     print(len(kernels), "kernels ->", out)
 
