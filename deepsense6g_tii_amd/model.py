@@ -23,6 +23,8 @@ from __future__ import annotations
 
 import math
 import os
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -31,6 +33,7 @@ from . import ops
 from ._lib import lib
 
 F32 = torch.float32
+BF16 = torch.bfloat16
 STAGE_WIDTH = (64, 128, 256, 512)
 RESNET_LAYERS = {"resnet34": (3, 4, 6, 3), "resnet18": (2, 2, 2, 2)}
 
@@ -169,6 +172,38 @@ class Encoder(nn.Module):  # model2_seq.py:406-470
         self.transformer2 = GPT(128, config)
         self.transformer3 = GPT(256, config)
         self.transformer4 = GPT(512, config)
+
+
+# ------------------------------------------------------------------------------------------------
+# tape records: what the forward walk keeps for the backward walk, one typing.NamedTuple per kind
+# ------------------------------------------------------------------------------------------------
+def _record(name, fields):
+    return NamedTuple(name, [(f, object) for f in fields.split()])
+
+
+# the stem: packed NHWC x4 input, conv output (None when BN is folded), folded conv + ReLU output (inference only),
+# BatchNorm (mean, invstd), max-pool argmax, input channels
+_StemRec = _record("_StemRec", "x c1 a1 stats idx cin")
+# a BasicBlock: ud1 / ud2 = the Winograd dgrad filters handed over to the backward (fp32 storage), else None
+_BlockRec = _record("_BlockRec", "x c1 a1 s1 c2 s2 cd sd out ud1 ud2")
+# a GPT block: the dtype of h is the block's storage; (off_a, pa), (off_p, pr), (off_m, pr) = dropout offset and p of the
+# attention, proj-branch and fc2-branch masks
+_GptRec = _record("_GptRec", "x h m1 r1 q k v y lse off_a pa off_p pr x1 h2 m2 r2 f1 off_m")
+# a GPT fusion stage: blocks = its _GptRecs; x_last, mf, rf = input and statistics of ln_f
+_StageRec = _record("_StageRec", "s C T fps offs pe off_e gps_src blocks x_last mf rf fshapes")
+# the head: fused tokens, join MLP hiddens, final feature-map shapes, (join output, saved state) of the GRU head or None,
+# feature-map dtype
+_HeadRec = _record("_HeadRec", "fused h1 h2 fshapes gru fdtype")
+# a whole training forward: stems / stages per trunk / stage, layers[stage][trunk] = [_BlockRec]
+_Tape = _record("_Tape", "B stems layers stages head gps salt")
+
+# GPT-block kernels of the two activation storages (same arguments; bf16: operands stored as bf16, weights from the shadow)
+_F32_OPS = SimpleNamespace(dtype=F32, ln_fwd=ops.layernorm_fwd, ln_bwd=ops.layernorm_bwd, lin_fwd=ops.linear_fwd,
+                           lin_dgrad=ops.linear_dgrad, lin_wgrad=ops.linear_wgrad, attn_fwd=ops.attention_fwd,
+                           attn_bwd=ops.attention_bwd)
+_BF16_OPS = SimpleNamespace(dtype=BF16, ln_fwd=ops.layernorm_fwd_bf16, ln_bwd=ops.layernorm_bwd_bf16,
+                            lin_fwd=ops.bf16_linear_fwd, lin_dgrad=ops.bf16_linear_dgrad, lin_wgrad=ops.bf16_linear_wgrad,
+                            attn_fwd=ops.attention_fwd_bf16, attn_bwd=ops.attention_bwd_bf16io)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -622,16 +657,19 @@ class TransFuser(nn.Module):
                 (e.radar_encoder._model, "resnet18", 2 if self.config.add_velocity else 1, False))
 
     def _bn_fwd(self, bn, x, relu, residual, train):
+        """BatchNorm (+ residual, + ReLU) of an fp32 or bf16 feature map; statistics fp32 -> (y, (mean, invstd))"""
+        f16 = x.dtype == BF16
         C = x.shape[-1]
         M = x.numel() // C
         stats = torch.empty(2, C, dtype=F32, device=x.device)
         mean, invstd = stats[0], stats[1]
         if train:
-            ops.bn_stats(M, C, x, mean, invstd, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self._ws,
-                         bn.eps, bn.momentum)
+            (ops.bf16_bn_stats if f16 else ops.bn_stats)(M, C, x, mean, invstd, bn.running_mean.data_ptr(),
+                                                         bn.running_var.data_ptr(), self._ws, bn.eps, bn.momentum)
         else:
             ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), C, mean, invstd, bn.eps)
-        y = ops.bn_apply(x, mean, invstd, self._w(bn.weight), self._w(bn.bias), relu, residual)
+        y = (ops.bf16_bn_apply if f16 else ops.bn_apply)(x, mean, invstd, self._w(bn.weight), self._w(bn.bias), relu,
+                                                         residual)
         return y, (mean, invstd)
 
     def _stem_fwd(self, trunk, cin, normalize, frames, train):
@@ -656,7 +694,7 @@ class TransFuser(nn.Module):
                 c1 = ops.bf16_stem_fwd(x16, self._w(trunk.conv1.weight), cin, self._ws)
                 ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), 64, stats[0], stats[1], bn.eps)
             p1, idx = ops.bf16_stem_bn_relu_maxpool(c1, stats[0], stats[1], self._w(bn.weight), self._w(bn.bias))
-            return p1, (x16, c1, None, (stats[0], stats[1]), idx, cin)
+            return p1, _StemRec(x16, c1, None, (stats[0], stats[1]), idx, cin)
         if torch.is_tensor(frames):  # data.PackedInputs: already NHWC x4, normalised
             x = frames
             assert x.dim() == 4 and x.shape[3] == 4 and x.dtype == F32 and x.is_contiguous() and x.device == self.device
@@ -687,112 +725,47 @@ class TransFuser(nn.Module):
             st1 = (stats[0], stats[1])
             pool = ops.bn_relu_maxpool_bf16out if self._use16 else ops.bn_relu_maxpool
             p1, idx = pool(c1, st1[0], st1[1], self._w(bn.weight), self._w(bn.bias))
-            return p1, (x, c1, None, st1, idx, cin)
+            return p1, _StemRec(x, c1, None, st1, idx, cin)
         N, H1, W1, _ = a1.shape
         Ho, Wo = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
         p1 = torch.empty((N, Ho, Wo, 64), dtype=F32, device=self.device)
         idx = torch.empty((N, Ho, Wo, 64), dtype=torch.uint8, device=self.device)
         L.maxpool3x3s2_fwd(a1.data_ptr(), p1.data_ptr(), idx.data_ptr(), N, H1, W1, 64, st)
-        return p1, (x, c1, a1, st1, idx, cin)
+        return p1, _StemRec(x, c1, a1, st1, idx, cin)
 
-    def _conv3x3(self, x, conv, K, stride):
-        """3x3 conv of a BasicBlock: Winograd F(2x2, 3x3) where the shape allows it (stride 1, exact-fp32 mode: 2.25x
-        fewer MFMA FLOPs - the direct kernel already runs at the chip's power-limited fp32 rate), else the implicit GEMM.
-        -> (y, ud): ud = the transformed dgrad filter when the backward pass will want it (recording), else None."""
-        if stride == 1 and self.use_winograd and ops.winograd_ok(x.shape, K):
+    def _conv_fwd(self, x, conv, K, R, stride):
+        """R x R conv (padding R // 2) of a BasicBlock -> (y, ud).  bf16 storage: the direct implicit GEMM on bf16 tiles
+        and the bf16 weight shadow.  fp32: a 3x3 runs as Winograd F(2x2, 3x3) where the shape allows it (stride 1,
+        exact-fp32 mode: 2.25x fewer MFMA FLOPs - the direct kernel already runs at the chip's power-limited fp32 rate),
+        else the implicit GEMM.  ud = the transformed dgrad filter when the backward pass will want it (recording), else
+        None."""
+        if x.dtype == BF16:
+            return ops.bf16_conv2d_fwd(x, self._w16(conv.weight), K, R, R, stride, R // 2), None
+        if R == 3 and stride == 1 and self.use_winograd and ops.winograd_ok(x.shape, K):
             C = x.shape[-1]
             if self._recording and ops.winograd_ok((x.shape[0], x.shape[1], x.shape[2], K), C):
                 u, ud = ops.winograd_weights(self._w(conv.weight), K, C, self.device, both=True)  # one launch for both
                 return ops.conv3x3_winograd(x, u, K), ud
             u = ops.winograd_weights(self._w(conv.weight), K, C, self.device)
             return ops.conv3x3_winograd(x, u, K), None
-        return ops.conv2d_fwd(x, self._w(conv.weight), K, 3, 3, stride, 1), None
+        return ops.conv2d_fwd(x, self._w(conv.weight), K, R, R, stride, R // 2), None
 
-    def _dgrad3x3(self, dy, conv, x_shape, stride, out=None, accumulate=False, ud=None):
+    def _conv_dgrad(self, dy, conv, x_shape, R, stride, out=None, accumulate=False, ud=None):
+        """data gradient of _conv_fwd; ud: the Winograd dgrad filter recorded by the forward (fp32 storage) or None"""
+        if dy.dtype == BF16:
+            return ops.bf16_conv2d_dgrad(dy, self._w16(conv.weight), tuple(x_shape), R, R, stride, R // 2, out=out,
+                                         accumulate=accumulate)
         K = dy.shape[-1]
-        if stride == 1 and self.use_winograd and ops.winograd_ok(dy.shape, x_shape[-1]):
+        if R == 3 and stride == 1 and self.use_winograd and ops.winograd_ok(dy.shape, x_shape[-1]):
             if ud is None:  # (weights are unchanged between forward and backward: normally handed over by the tape)
                 ud = ops.winograd_weights(self._w(conv.weight), K, x_shape[-1], self.device, dgrad=True)
             return ops.conv3x3_winograd(dy, ud, x_shape[-1], out=out, accumulate=accumulate)
-        return ops.conv2d_dgrad(dy, self._w(conv.weight), tuple(x_shape), 3, 3, stride, 1, out=out, accumulate=accumulate)
-
-    def _bn_fwd16(self, bn, x, relu, residual, train):
-        C = x.shape[-1]
-        stats = torch.empty(2, C, dtype=F32, device=x.device)
-        if train:
-            ops.bf16_bn_stats(x.numel() // C, C, x, stats[0], stats[1], bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                              self._ws, bn.eps, bn.momentum)
-        else:
-            ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), C, stats[0], stats[1], bn.eps)
-        y = ops.bf16_bn_apply(x, stats[0], stats[1], self._w(bn.weight), self._w(bn.bias), relu, residual)
-        return y, (stats[0], stats[1])
-
-    def _block_fwd16(self, blk, x, train):
-        """BasicBlock on bf16-stored feature maps: convs on csrc/bgemm.hip (direct implicit GEMM, bf16 tiles, bf16 weight
-        shadow), BatchNorm reading / writing bf16 with fp32 statistics.  Same tape layout as _block_fwd."""
-        K = blk.conv1.out_channels
-        if train and self.fuse_bn_stats16:
-            # train mode: the conv's epilogue emits the BatchNorm statistics of its (stored) output - no statistics pass
-            def conv_bn(inp, conv, bn, R, stride, pad, relu, residual):
-                stats = torch.empty(2, K, dtype=F32, device=inp.device)
-                c = ops.bf16_conv2d_fwd_bnstats(inp, self._w16(conv.weight), K, R, R, stride, pad, stats[0], stats[1],
-                                                bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self._ws, bn.eps,
-                                                bn.momentum)
-                y = ops.bf16_bn_apply(c, stats[0], stats[1], self._w(bn.weight), self._w(bn.bias), relu, residual)
-                return c, y, (stats[0], stats[1])
-            c1, a1, s1 = conv_bn(x, blk.conv1, blk.bn1, 3, blk.stride, 1, True, None)
-            if blk.downsample is not None:
-                cd, idn, sd = conv_bn(x, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None)
-            else:
-                cd, sd, idn = None, None, x
-            c2, out, s2 = conv_bn(a1, blk.conv2, blk.bn2, 3, 1, 1, True, idn)
-            return out, (x, c1, a1, s1, c2, s2, cd, sd, out, None, None)
-        c1 = ops.bf16_conv2d_fwd(x, self._w16(blk.conv1.weight), K, 3, 3, blk.stride, 1)
-        a1, s1 = self._bn_fwd16(blk.bn1, c1, True, None, train)
-        c2 = ops.bf16_conv2d_fwd(a1, self._w16(blk.conv2.weight), K, 3, 3, 1, 1)
-        if blk.downsample is not None:
-            cd = ops.bf16_conv2d_fwd(x, self._w16(blk.downsample[0].weight), K, 1, 1, blk.stride, 0)
-            idn, sd = self._bn_fwd16(blk.downsample[1], cd, False, None, train)
-        else:
-            cd, sd, idn = None, None, x
-        out, s2 = self._bn_fwd16(blk.bn2, c2, True, idn, train)
-        return out, (x, c1, a1, s1, c2, s2, cd, sd, out, None, None)
-
-    def _block_bwd16(self, blk, ctx, dout):
-        x, c1, a1, s1, c2, s2, cd, sd, out, _, _ = ctx
-
-        def bn_bwd(bn, dy, y_mask, xin, stats, want_dres=False, relu_no_residual=False):
-            gw, aw = self._g(bn.weight)
-            gb, _ = self._g(bn.bias)
-            return ops.bf16_bn_bwd(dy, None if relu_no_residual else y_mask, xin, stats[0], stats[1], self._w(bn.weight), gw,
-                                   gb, self._ws, want_dres=want_dres, accumulate=bool(aw),
-                                   relu_beta_ptr=self._w(bn.bias) if relu_no_residual else 0)
-
-        def wgrad(conv, xin, dy, R, stride, pad):
-            gp, acc = self._g(conv.weight)
-            self._wg_launch(lambda: ops.bf16_conv2d_wgrad(xin, dy, gp, R, R, stride, pad, self._ws, accumulate=bool(acc)),
-                            (xin, dy))
-
-        dc2, dres = bn_bwd(blk.bn2, dout, out, c2, s2, want_dres=True)
-        wgrad(blk.conv2, a1, dc2, 3, 1, 1)
-        da1 = ops.bf16_conv2d_dgrad(dc2, self._w16(blk.conv2.weight), tuple(a1.shape), 3, 3, 1, 1)
-        dc1, _ = bn_bwd(blk.bn1, da1, a1, c1, s1, relu_no_residual=True)
-        wgrad(blk.conv1, x, dc1, 3, blk.stride, 1)
-        if blk.downsample is not None:
-            dcd, _ = bn_bwd(blk.downsample[1], dres, None, cd, sd)
-            wgrad(blk.downsample[0], x, dcd, 1, blk.stride, 0)
-            dx = ops.bf16_conv2d_dgrad(dc1, self._w16(blk.conv1.weight), tuple(x.shape), 3, 3, blk.stride, 1)
-            ops.bf16_conv2d_dgrad(dcd, self._w16(blk.downsample[0].weight), tuple(x.shape), 1, 1, blk.stride, 0, out=dx,
-                                  accumulate=True)
-        else:
-            dx = dres
-            ops.bf16_conv2d_dgrad(dc1, self._w16(blk.conv1.weight), tuple(x.shape), 3, 3, blk.stride, 1, out=dx,
-                                  accumulate=True)
-        return dx
+        return ops.conv2d_dgrad(dy, self._w(conv.weight), tuple(x_shape), R, R, stride, R // 2, out=out,
+                                accumulate=accumulate)
 
     def _block_fwd(self, blk, x, train):
-        if x.dtype == torch.bfloat16:
-            return self._block_fwd16(blk, x, train)
+        """BasicBlock on fp32 or bf16-stored feature maps (bf16: convs on csrc/bgemm.hip with the bf16 weight shadow,
+        BatchNorm reading / writing bf16 with fp32 statistics) -> (out, _BlockRec or None when BN is folded)"""
         K = blk.conv1.out_channels
         if self._fold_now:
             # inference: eval-mode BN is an affine map per channel - folded into the conv weights, the block is three
@@ -815,122 +788,68 @@ class TransFuser(nn.Module):
                 idn = ops.conv2d_bias_act_fwd(x, wd.data_ptr(), bd.data_ptr(), K, 1, 1, blk.stride, 0, relu=0)
             out = conv3(a1, blk.conv2, blk.bn2, 1, 2, residual=idn)
             return out, None
-        c1, ud1 = self._conv3x3(x, blk.conv1, K, blk.stride)
+        if train and self.fuse_bn_stats16 and x.dtype == BF16:
+            # bf16 train mode: the conv's epilogue emits the BatchNorm statistics of its (stored) output - no statistics
+            # pass (the downsample conv runs before conv2 here)
+            def conv_bn(inp, conv, bn, R, stride, pad, relu, residual):
+                stats = torch.empty(2, K, dtype=F32, device=inp.device)
+                c = ops.bf16_conv2d_fwd_bnstats(inp, self._w16(conv.weight), K, R, R, stride, pad, stats[0], stats[1],
+                                                bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self._ws, bn.eps,
+                                                bn.momentum)
+                y = ops.bf16_bn_apply(c, stats[0], stats[1], self._w(bn.weight), self._w(bn.bias), relu, residual)
+                return c, y, (stats[0], stats[1])
+            c1, a1, s1 = conv_bn(x, blk.conv1, blk.bn1, 3, blk.stride, 1, True, None)
+            if blk.downsample is not None:
+                cd, idn, sd = conv_bn(x, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None)
+            else:
+                cd, sd, idn = None, None, x
+            c2, out, s2 = conv_bn(a1, blk.conv2, blk.bn2, 3, 1, 1, True, idn)
+            return out, _BlockRec(x, c1, a1, s1, c2, s2, cd, sd, out, None, None)
+        c1, ud1 = self._conv_fwd(x, blk.conv1, K, 3, blk.stride)
         a1, s1 = self._bn_fwd(blk.bn1, c1, True, None, train)
-        c2, ud2 = self._conv3x3(a1, blk.conv2, K, 1)
+        c2, ud2 = self._conv_fwd(a1, blk.conv2, K, 3, 1)
         if blk.downsample is not None:
-            cd = ops.conv2d_fwd(x, self._w(blk.downsample[0].weight), K, 1, 1, blk.stride, 0)
+            cd, _ = self._conv_fwd(x, blk.downsample[0], K, 1, blk.stride)
             idn, sd = self._bn_fwd(blk.downsample[1], cd, False, None, train)
         else:
             cd, sd, idn = None, None, x
-        C = c2.shape[-1]
-        M = c2.numel() // C
-        stats = torch.empty(2, C, dtype=F32, device=x.device)
-        bn2 = blk.bn2
-        if train:
-            ops.bn_stats(M, C, c2, stats[0], stats[1], bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(),
-                         self._ws, bn2.eps, bn2.momentum)
-        else:
-            ops.bn_eval_prepare(bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(), C, stats[0], stats[1], bn2.eps)
-        out = ops.bn_apply(c2, stats[0], stats[1], self._w(bn2.weight), self._w(bn2.bias), True, idn)
-        return out, (x, c1, a1, s1, c2, (stats[0], stats[1]), cd, sd, out, ud1, ud2)
-
-    def _gpt_block_fwd16(self, blk, x, B, T, train):
-        """_gpt_block_fwd on bf16-stored operands: LN -> h (bf16) -> fused k|q|v GEMM (bf16) -> attention on bf16 tiles (o
-        bf16) -> proj GEMM + dropout + residual (fp32 stream) -> LN -> h2 (bf16) -> fc1 + ReLU (bf16) -> fc2 + dropout +
-        residual (fp32).  Same dropout counters / masks as the fp32-storage path."""
-        cfg = self.config
-        C = x.shape[1]
-        nh = cfg.n_head
-        pa = cfg.attn_pdrop if train else 0.0
-        pr = cfg.resid_pdrop if train else 0.0
-        at = blk.attn
-        h, m1, r1 = ops.layernorm_fwd_bf16(x, self._w(blk.ln1.weight), self._w(blk.ln1.bias), blk.ln1.eps)
-        kqv = ops.bf16_linear_fwd(h, self._w16(at.key.weight), self._w(at.key.bias), 3 * C)   # bf16 [M, 3C]
-        k, q, v = kqv[:, :C], kqv[:, C:2 * C], kqv[:, 2 * C:]
-        off_a = self._next_drop(B * nh * T * T) if pa > 0 else 0
-        y, lse = ops.attention_fwd_bf16(q, k, v, B, T, nh, self._ws, pa, self._seed, off_a)
-        off_p = self._next_drop(x.numel()) if pr > 0 else 0
-        x1 = ops.bf16_linear_fwd(y, self._w16(at.proj.weight), self._w(at.proj.bias), C, residual=x, drop_p=pr,
-                                 seed=self._seed, seed_off=off_p)
-        h2, m2, r2 = ops.layernorm_fwd_bf16(x1, self._w(blk.ln2.weight), self._w(blk.ln2.bias), blk.ln2.eps)
-        fc1, fc2 = blk.mlp[0], blk.mlp[2]
-        f1 = ops.bf16_linear_fwd(h2, self._w16(fc1.weight), self._w(fc1.bias), fc1.out_features, relu=True)
-        off_m = self._next_drop(x.numel()) if pr > 0 else 0
-        x2 = ops.bf16_linear_fwd(f1, self._w16(fc2.weight), self._w(fc2.bias), C, residual=x1, drop_p=pr, seed=self._seed,
-                                 seed_off=off_m)
-        return x2, (x, h, m1, r1, q, k, v, y, lse, off_a, pa, off_p, pr, x1, h2, m2, r2, f1, off_m)
-
-    def _gpt_block_bwd16(self, blk, ctx, dx2, B, T, dz2, next_drop=None, want_dz=True):
-        """backward of _gpt_block_fwd16.  dx2: fp32 gradient of the block output (residual stream); dz2: dropout(dx2) as
-        bf16 (emitted by the LayerNorm backward above); returns (dx fp32, dropout(dx) as bf16 on the next block's mask)."""
-        (x, h, m1, r1, q, k, v, y, lse, off_a, pa, off_p, pr, x1, h2, m2, r2, f1, off_m) = ctx
-        C = x.shape[1]
-        nh = self.config.n_head
-        at = blk.attn
-        fc1, fc2 = blk.mlp[0], blk.mlp[2]
-
-        def wgrad(lin_w, lin_b, xin, dyin):
-            gw, aw = self._g(lin_w)
-            gb, _ = self._g(lin_b)
-            self._wg_launch(lambda: ops.bf16_linear_wgrad(xin, dyin, gw, self._ws, accumulate=bool(aw), dbias_ptr=gb), (xin, dyin))
-
-        wgrad(fc2.weight, fc2.bias, f1, dz2)
-        df1 = ops.bf16_linear_dgrad(dz2, self._w16(fc2.weight), fc1.out_features, relu_mask_src=f1)
-        wgrad(fc1.weight, fc1.bias, h2, df1)
-        dh2 = ops.bf16_linear_dgrad(df1, self._w16(fc1.weight), C)
-        g2w, a2 = self._g(blk.ln2.weight)
-        g2b, _ = self._g(blk.ln2.bias)
-        dx1, dz1 = ops.layernorm_bwd_bf16(dh2, x1, m2, r2, self._w(blk.ln2.weight), g2w, g2b, self._ws, add=dx2,
-                                          accumulate=bool(a2), drop=(pr, self._seed, off_p))
-        wgrad(at.proj.weight, at.proj.bias, y, dz1)
-        dy = ops.bf16_linear_dgrad(dz1, self._w16(at.proj.weight), C)   # bf16: the attention backward's dO
-        # the fused [3C, C] weight-gradient block and its [3C] bias block start at key.*: only valid while the three
-        # projections' gradients are contiguous arena views with ONE accumulate flag (the fp32 path falls back to three
-        # GEMMs otherwise; the bf16-storage path has no such fallback, so it refuses instead of writing wrong slices)
-        if self._qkv_fused(at, grads=True) is None:
-            raise RuntimeError("bf16-storage backward needs key / query / value gradients in the gradient arena with one "
-                               "common state (all None or all arena views): call zero_grad(set_to_none=True) first")
-        dkqv = torch.empty((dy.shape[0], 3 * C), dtype=torch.bfloat16, device=dy.device)
-        ops.attention_bwd_bf16io(q, k, v, y, dy, lse, B, T, nh, self._attn_ws(B, T, nh, C), pa, self._seed, off_a,
-                                 out=(dkqv[:, C:2 * C], dkqv[:, :C], dkqv[:, 2 * C:]))
-        wgrad(at.key.weight, at.key.bias, h, dkqv)   # the fused [3C, C] block and its [3C] bias start at key.*
-        dh = ops.bf16_linear_dgrad(dkqv, self._w16(at.key.weight), C)
-        g1w, a1 = self._g(blk.ln1.weight)
-        g1b, _ = self._g(blk.ln1.bias)
-        return ops.layernorm_bwd_bf16(dh, x, m1, r1, self._w(blk.ln1.weight), g1w, g1b, self._ws, add=dx1,
-                                      accumulate=bool(a1), drop=next_drop, want_drop=want_dz)
+        out, s2 = self._bn_fwd(blk.bn2, c2, True, idn, train)
+        return out, _BlockRec(x, c1, a1, s1, c2, s2, cd, sd, out, ud1, ud2)
 
     def _gpt_block_fwd(self, blk, x, B, T, train):
-        if self._use16:
-            return self._gpt_block_fwd16(blk, x, B, T, train)
+        """LN -> h -> k|q|v GEMM -> attention -> proj GEMM + dropout + residual -> LN -> h2 -> fc1 + ReLU -> fc2 + dropout +
+        residual, on fp32 or (self._use16) bf16-stored GEMM operands: h, q / k / v, y, h2, f1 bf16 and the weights from
+        the bf16 shadow, while the residual stream x, x1, x2 and every statistic stay fp32.  Same dropout counters / masks
+        in both storages.  -> (x2, _GptRec)"""
+        f16 = self._use16
+        op, w = (_BF16_OPS, self._w16) if f16 else (_F32_OPS, self._w)
         cfg = self.config
         C = x.shape[1]
         nh = cfg.n_head
         pa = cfg.attn_pdrop if train else 0.0
         pr = cfg.resid_pdrop if train else 0.0
         at = blk.attn
-        h, m1, r1 = ops.layernorm_fwd(x, self._w(blk.ln1.weight), self._w(blk.ln1.bias), blk.ln1.eps)
-        fused = self._qkv_fused(at) if self.fuse_qkv else None
-        if fused is not None:  # one GEMM, columns key | query | value
-            kqv = ops.linear_fwd(h, fused[0], fused[1], 3 * C)
+        h, m1, r1 = op.ln_fwd(x, self._w(blk.ln1.weight), self._w(blk.ln1.bias), blk.ln1.eps)
+        # one GEMM, columns key | query | value, when the three projections are contiguous (always on the bf16 storage,
+        # which runs on the arena only)
+        if f16 or (self.fuse_qkv and self._qkv_fused(at) is not None):
+            kqv = op.lin_fwd(h, w(at.key.weight), self._w(at.key.bias), 3 * C)
             k, q, v = kqv[:, :C], kqv[:, C:2 * C], kqv[:, 2 * C:]
         else:
-            q = ops.linear_fwd(h, self._w(at.query.weight), self._w(at.query.bias), C)
-            k = ops.linear_fwd(h, self._w(at.key.weight), self._w(at.key.bias), C)
-            v = ops.linear_fwd(h, self._w(at.value.weight), self._w(at.value.bias), C)
+            q = op.lin_fwd(h, w(at.query.weight), self._w(at.query.bias), C)
+            k = op.lin_fwd(h, w(at.key.weight), self._w(at.key.bias), C)
+            v = op.lin_fwd(h, w(at.value.weight), self._w(at.value.bias), C)
         off_a = self._next_drop(B * nh * T * T) if pa > 0 else 0
-        y, lse = ops.attention_fwd(q, k, v, B, T, nh, self._ws, pa, self._seed, off_a)
+        y, lse = op.attn_fwd(q, k, v, B, T, nh, self._ws, pa, self._seed, off_a)
         off_p = self._next_drop(x.numel()) if pr > 0 else 0
-        x1 = ops.linear_fwd(y, self._w(at.proj.weight), self._w(at.proj.bias), C, residual=x, drop_p=pr,
-                            seed=self._seed, seed_off=off_p)
-        h2, m2, r2 = ops.layernorm_fwd(x1, self._w(blk.ln2.weight), self._w(blk.ln2.bias), blk.ln2.eps)
+        x1 = op.lin_fwd(y, w(at.proj.weight), self._w(at.proj.bias), C, residual=x, drop_p=pr, seed=self._seed,
+                        seed_off=off_p)
+        h2, m2, r2 = op.ln_fwd(x1, self._w(blk.ln2.weight), self._w(blk.ln2.bias), blk.ln2.eps)
         fc1, fc2 = blk.mlp[0], blk.mlp[2]
-        f1 = ops.linear_fwd(h2, self._w(fc1.weight), self._w(fc1.bias), fc1.out_features, relu=True)
+        f1 = op.lin_fwd(h2, w(fc1.weight), self._w(fc1.bias), fc1.out_features, relu=True)
         off_m = self._next_drop(x.numel()) if pr > 0 else 0
-        x2 = ops.linear_fwd(f1, self._w(fc2.weight), self._w(fc2.bias), C, residual=x1, drop_p=pr, seed=self._seed,
-                            seed_off=off_m)
-        return x2, (x, h, m1, r1, q, k, v, y, lse, off_a, pa, off_p, pr, x1, h2, m2, r2, f1, off_m)
+        x2 = op.lin_fwd(f1, w(fc2.weight), self._w(fc2.bias), C, residual=x1, drop_p=pr, seed=self._seed, seed_off=off_m)
+        return x2, _GptRec(x, h, m1, r1, q, k, v, y, lse, off_a, pa, off_p, pr, x1, h2, m2, r2, f1, off_m)
 
     def _stage_fwd(self, s, feats, gps_src, B, train):
         """GPT fusion at scale s (1-based).  feats: 3 NHWC maps.  gps_src: (tensor, ptr, rows_per_group,
@@ -974,8 +893,7 @@ class TransFuser(nn.Module):
             (L.bf16_upsample_add_fwd if f16 else L.upsample_add_fwd)(
                 feats[m].data_ptr(), xo.data_ptr(), o.data_ptr(), N, H, C, fps[m], offs[m], T, st)
             outs.append(o)
-        ctx = (s, C, T, fps, offs, pe, off_e, gps_src, blk_ctx, x, mf, rf, [f.shape for f in feats])
-        return outs, xo, ctx
+        return outs, xo, _StageRec(s, C, T, fps, offs, pe, off_e, gps_src, blk_ctx, x, mf, rf, [f.shape for f in feats])
 
     def _dp_check_fresh_grads(self):
         # data parallel: a bucket is all-reduced in place the moment it is final, so every gradient must be written
@@ -1062,10 +980,10 @@ class TransFuser(nn.Module):
                 cap[f"gpt{s}"] = xo.clone()
                 cap[f"fused{s}"] = [f.clone() for f in feats]
             stage_ctx.append(sc)
-            C, T = sc[1], sc[2]
+            C, T = sc.C, sc.T
             gps_src = (xo, xo.data_ptr() + (T - 2) * C * 4, 2, T * C, C)
         # head: global pool, 17-token sum, join MLP
-        C, T = 512, stage_ctx[-1][2]
+        C, T = 512, stage_ctx[-1].T
         pooled = []
         for m in range(3):
             N = feats[m].shape[0]
@@ -1098,20 +1016,25 @@ class TransFuser(nn.Module):
             logits = pred
         tape = None
         if record:
-            tape = (B, stem_ctx, layer_ctx, stage_ctx, (fused, h1, h2, [f.shape for f in feats], gru, feats[0].dtype), gps,
-                    self._salt_cur if train else None)
+            head = _HeadRec(fused, h1, h2, [f.shape for f in feats], gru, feats[0].dtype)
+            tape = _Tape(B, stem_ctx, layer_ctx, stage_ctx, head, gps, self._salt_cur if train else None)
         return logits, tape
 
     # ================================================================ backward walk =============
-    def _wgrad_conv(self, conv, x, dy, R, stride, pad):
+    def _conv_wgrad(self, conv, x, dy, R, stride):
+        """weight gradient of _conv_fwd (bf16 storage: bf16 operands, fp32 gradient)"""
         gp, acc = self._g(conv.weight)
+        if x.dtype == BF16:
+            self._wg_launch(lambda: ops.bf16_conv2d_wgrad(x, dy, gp, R, R, stride, R // 2, self._ws, accumulate=bool(acc)),
+                            (x, dy))
+            return
         K = dy.shape[-1]
         if (R == 3 and stride == 1 and self.use_winograd and x.shape[-1] * K >= 128 * 128
                 and ops.winograd_wgrad_ok(x.shape, K)):
             # Winograd-domain weight gradient (measured faster from 128 x 128 channels up; 64 x 64 stays direct)
             self._wg_launch(lambda: ops.conv3x3_winograd_wgrad(x, dy, gp, self._ws, accumulate=bool(acc)), (x, dy))
             return
-        self._wg_launch(lambda: ops.conv2d_wgrad(x, dy, gp, R, R, stride, pad, self._ws, accumulate=bool(acc)), (x, dy))
+        self._wg_launch(lambda: ops.conv2d_wgrad(x, dy, gp, R, R, stride, R // 2, self._ws, accumulate=bool(acc)), (x, dy))
 
     # Weight gradients feed nothing but the optimizer, while the dgrad / attention / LayerNorm kernels around them form
     # the serial chain of the backward walk.  In the GPT stages (one stream) the weight-gradient launches therefore go
@@ -1147,103 +1070,104 @@ class TransFuser(nn.Module):
         self._wg_keep = []
 
     def _bn_bwd(self, bn, dy, y_mask, x, stats, want_dres=False, relu_no_residual=False):
-        """relu_no_residual: y_mask is relu(bn(x)) itself (bn1 of a block / of the stem) - its sign is recomputed from
-        x inside the kernels instead of reading the activation tensor twice"""
+        """backward of _bn_fwd (fp32 or bf16 maps) -> (dx, dresidual or None).  relu_no_residual: y_mask is relu(bn(x))
+        itself (bn1 of a block) - its sign is recomputed from x inside the kernels instead of reading the activation
+        tensor twice"""
         gw, aw = self._g(bn.weight)
-        gb, ab = self._g(bn.bias)
-        if relu_no_residual:
-            dx, dres = ops.bn_bwd(dy, None, x, stats[0], stats[1], self._w(bn.weight), gw, gb, self._ws,
-                                  want_dres=want_dres, accumulate=bool(aw), relu_beta_ptr=self._w(bn.bias))
-            return dx, dres
-        dx, dres = ops.bn_bwd(dy, y_mask, x, stats[0], stats[1], self._w(bn.weight), gw, gb, self._ws,
-                              want_dres=want_dres, accumulate=bool(aw))
-        return dx, dres
+        gb, _ = self._g(bn.bias)
+        return (ops.bf16_bn_bwd if dy.dtype == BF16 else ops.bn_bwd)(
+            dy, None if relu_no_residual else y_mask, x, stats[0], stats[1], self._w(bn.weight), gw, gb, self._ws,
+            want_dres=want_dres, accumulate=bool(aw), relu_beta_ptr=self._w(bn.bias) if relu_no_residual else 0)
 
-    def _lin_param_grads(self, lin, x, dy):
-        gw, aw = self._g(lin.weight)
-        gb, ab = self._g(lin.bias)
-        self._linear_wgrad(x, dy, gw, bool(aw), gb)
-
-    def _linear_wgrad(self, x, dy, gw, accumulate, gb):
-        self._wg_launch(lambda: ops.linear_wgrad(x, dy, gw, self._ws, accumulate=accumulate, dbias_ptr=gb), (x, dy))
-
-    def _block_bwd(self, blk, ctx, dout, need_dx=True):
-        if dout.dtype == torch.bfloat16:
-            return self._block_bwd16(blk, ctx, dout)
-        x, c1, a1, s1, c2, s2, cd, sd, out, ud1, ud2 = ctx
-        dc2, dres = self._bn_bwd(blk.bn2, dout, out, c2, s2, want_dres=True)
-        self._wgrad_conv(blk.conv2, a1, dc2, 3, 1, 1)
-        da1 = self._dgrad3x3(dc2, blk.conv2, a1.shape, 1, ud=ud2)
-        dc1, _ = self._bn_bwd(blk.bn1, da1, a1, c1, s1, relu_no_residual=True)
-        self._wgrad_conv(blk.conv1, x, dc1, 3, blk.stride, 1)
+    def _block_bwd(self, blk, rec, dout):
+        r = rec
+        dc2, dres = self._bn_bwd(blk.bn2, dout, r.out, r.c2, r.s2, want_dres=True)
+        self._conv_wgrad(blk.conv2, r.a1, dc2, 3, 1)
+        da1 = self._conv_dgrad(dc2, blk.conv2, r.a1.shape, 3, 1, ud=r.ud2)
+        dc1, _ = self._bn_bwd(blk.bn1, da1, r.a1, r.c1, r.s1, relu_no_residual=True)
+        self._conv_wgrad(blk.conv1, r.x, dc1, 3, blk.stride)
         if blk.downsample is not None:
-            dcd, _ = self._bn_bwd(blk.downsample[1], dres, None, cd, sd)
-            self._wgrad_conv(blk.downsample[0], x, dcd, 1, blk.stride, 0)
+            dcd, _ = self._bn_bwd(blk.downsample[1], dres, None, r.cd, r.sd)
+            self._conv_wgrad(blk.downsample[0], r.x, dcd, 1, blk.stride)
             # the 3x3 dgrad writes every input pixel; the strided 1x1 only touches the even/even parity class
-            dx = self._dgrad3x3(dc1, blk.conv1, x.shape, blk.stride, ud=ud1)
-            ops.conv2d_dgrad(dcd, self._w(blk.downsample[0].weight), tuple(x.shape), 1, 1, blk.stride, 0, out=dx,
-                             accumulate=True)
+            dx = self._conv_dgrad(dc1, blk.conv1, r.x.shape, 3, blk.stride, ud=r.ud1)
+            self._conv_dgrad(dcd, blk.downsample[0], r.x.shape, 1, blk.stride, out=dx, accumulate=True)
         else:
             dx = dres
-            self._dgrad3x3(dc1, blk.conv1, x.shape, blk.stride, out=dx, accumulate=True, ud=ud1)
+            self._conv_dgrad(dc1, blk.conv1, r.x.shape, 3, blk.stride, out=dx, accumulate=True, ud=r.ud1)
         return dx
 
-    def _gpt_block_bwd(self, blk, ctx, dx2, B, T, dz2=None, next_drop=None):
-        """dx2: gradient of the block output; dz2: dropout(dx2) on this block's resid_drop mask if the producer of
-        dx2 already emitted it (fused into its LayerNorm backward); next_drop = (p, seed, off) of the block below:
-        the final LayerNorm backward then also emits dropout(dx).  Returns (dx, dropout(dx) or None)."""
-        (x, h, m1, r1, q, k, v, y, lse, off_a, pa, off_p, pr, x1, h2, m2, r2, f1, off_m) = ctx
-        C = x.shape[1]
+    def _gpt_block_bwd(self, blk, rec, dx2, B, T, dz2=None, next_drop=None):
+        """backward of _gpt_block_fwd on the storage the block was recorded in.  dx2: fp32 gradient of the block output
+        (residual stream); dz2: dropout(dx2) on this block's fc2-branch mask in the storage's dtype if the producer of dx2
+        already emitted it (fused into its LayerNorm backward), else None (fp32 storage: the block applies the dropout
+        itself); next_drop = (p, seed, off) of the block below: the final LayerNorm backward then also emits dropout(dx).
+        Returns (dx fp32, dropout(dx) or None)."""
+        r = rec
+        f16 = r.h.dtype == BF16
+        op, w = (_BF16_OPS, self._w16) if f16 else (_F32_OPS, self._w)
+        C = r.x.shape[1]
         nh = self.config.n_head
         at = blk.attn
         fc1, fc2 = blk.mlp[0], blk.mlp[2]
+
+        def wgrad(lin, x, dy):
+            gw, aw = self._g(lin.weight)
+            gb, _ = self._g(lin.bias)
+            self._wg_launch(lambda: op.lin_wgrad(x, dy, gw, self._ws, accumulate=bool(aw), dbias_ptr=gb), (x, dy))
+
         # x2 = x1 + drop(fc2(f1))
         if dz2 is None:
-            dz2 = ops.dropout(dx2, pr, self._seed, off_m) if pr > 0 else dx2
-        self._lin_param_grads(fc2, f1, dz2)
-        df1 = ops.linear_dgrad(dz2, self._w(fc2.weight), fc1.out_features, relu_mask_src=f1)
-        self._lin_param_grads(fc1, h2, df1)
-        dh2 = ops.linear_dgrad(df1, self._w(fc1.weight), C)
+            dz2 = ops.dropout(dx2, r.pr, self._seed, r.off_m) if r.pr > 0 else dx2
+        wgrad(fc2, r.f1, dz2)
+        df1 = op.lin_dgrad(dz2, w(fc2.weight), fc1.out_features, relu_mask_src=r.f1)
+        wgrad(fc1, r.h2, df1)
+        dh2 = op.lin_dgrad(df1, w(fc1.weight), C)
         g2w, a2 = self._g(blk.ln2.weight)
         g2b, _ = self._g(blk.ln2.bias)
         # x1 = x + drop(proj(y)): the LayerNorm backward emits dx1 and dropout(dx1) together
-        dx1, dz1 = ops.layernorm_bwd(dh2, x1, m2, r2, self._w(blk.ln2.weight), g2w, g2b, self._ws, add=dx2,
-                                     accumulate=bool(a2), drop=(pr, self._seed, off_p))
-        self._lin_param_grads(at.proj, y, dz1)
-        dy = ops.linear_dgrad(dz1, self._w(at.proj.weight), C)
-        fw = self._qkv_fused(at) if self.fuse_qkv else None
-        fg = self._qkv_fused(at, grads=True) if fw is not None else None
-        if fg is not None:  # gradients of the fused projection: one [M, 3C] matrix, one wgrad, one dgrad
-            dkqv = torch.empty((dy.shape[0], 3 * C), dtype=F32, device=dy.device)
-            ops.attention_bwd(q, k, v, y, dy, lse, B, T, nh, self._attn_ws(B, T, nh, C), pa, self._seed, off_a,
-                              out=(dkqv[:, C:2 * C], dkqv[:, :C], dkqv[:, 2 * C:]))
-            self._linear_wgrad(h, dkqv, fg[0], bool(self._g(at.key.weight)[1]), fg[1])
-            dh = ops.linear_dgrad(dkqv, fw[0], C)
+        dx1, dz1 = op.ln_bwd(dh2, r.x1, r.m2, r.r2, self._w(blk.ln2.weight), g2w, g2b, self._ws, add=dx2,
+                             accumulate=bool(a2), drop=(r.pr, self._seed, r.off_p))
+        wgrad(at.proj, r.y, dz1)
+        dy = op.lin_dgrad(dz1, w(at.proj.weight), C)   # bf16 storage: the attention backward's dO
+        # the fused [3C, C] weight-gradient block and its [3C] bias block start at key.*: only valid while the three
+        # projections' gradients are contiguous arena views with ONE accumulate flag.  fp32 storage falls back to three
+        # GEMMs otherwise; the bf16 storage has no such fallback, so it refuses instead of writing wrong slices
+        fused = ((f16 or (self.fuse_qkv and self._qkv_fused(at) is not None))
+                 and self._qkv_fused(at, grads=True) is not None)
+        if f16 and not fused:
+            raise RuntimeError("bf16-storage backward needs key / query / value gradients in the gradient arena with one "
+                               "common state (all None or all arena views): call zero_grad(set_to_none=True) first")
+        if fused:  # gradients of the fused projection: one [M, 3C] matrix, one wgrad, one dgrad
+            dkqv = torch.empty((dy.shape[0], 3 * C), dtype=op.dtype, device=dy.device)
+            op.attn_bwd(r.q, r.k, r.v, r.y, dy, r.lse, B, T, nh, self._attn_ws(B, T, nh, C), r.pa, self._seed, r.off_a,
+                        out=(dkqv[:, C:2 * C], dkqv[:, :C], dkqv[:, 2 * C:]))
+            wgrad(at.key, r.h, dkqv)
+            dh = op.lin_dgrad(dkqv, w(at.key.weight), C)
         else:
-            dq, dk, dv = ops.attention_bwd(q, k, v, y, dy, lse, B, T, nh, self._attn_ws(B, T, nh, C), pa, self._seed,
-                                           off_a)
-            self._lin_param_grads(at.query, h, dq)
-            self._lin_param_grads(at.key, h, dk)
-            self._lin_param_grads(at.value, h, dv)
-            dh = ops.linear_dgrad(dq, self._w(at.query.weight), C)
-            ops.linear_dgrad(dk, self._w(at.key.weight), C, out=dh, accumulate=True)
-            ops.linear_dgrad(dv, self._w(at.value.weight), C, out=dh, accumulate=True)
+            dq, dk, dv = op.attn_bwd(r.q, r.k, r.v, r.y, dy, r.lse, B, T, nh, self._attn_ws(B, T, nh, C), r.pa,
+                                     self._seed, r.off_a)
+            wgrad(at.query, r.h, dq)
+            wgrad(at.key, r.h, dk)
+            wgrad(at.value, r.h, dv)
+            dh = op.lin_dgrad(dq, w(at.query.weight), C)
+            op.lin_dgrad(dk, w(at.key.weight), C, out=dh, accumulate=True)
+            op.lin_dgrad(dv, w(at.value.weight), C, out=dh, accumulate=True)
         g1w, a1 = self._g(blk.ln1.weight)
         g1b, _ = self._g(blk.ln1.bias)
-        if next_drop is not None:
-            return ops.layernorm_bwd(dh, x, m1, r1, self._w(blk.ln1.weight), g1w, g1b, self._ws, add=dx1,
-                                     accumulate=bool(a1), drop=next_drop)
-        dx = ops.layernorm_bwd(dh, x, m1, r1, self._w(blk.ln1.weight), g1w, g1b, self._ws, add=dx1,
-                               accumulate=bool(a1))
-        return dx, None
+        ln1 = (dh, r.x, r.m1, r.r1, self._w(blk.ln1.weight), g1w, g1b, self._ws)
+        if next_drop is not None:   # also dropout(dx) on the mask of the block below
+            return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1), drop=next_drop)
+        if f16:
+            return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1), want_drop=False)
+        return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1)), None
 
-    def _stage_bwd(self, ctx, dfeats_out, dgps_tok, B):
-        """dfeats_out: grads of the 3 post-fusion maps; dgps_tok: (tensor, bcast) grad of the GPS rows of
-        this stage's output.  Returns grads of the 3 pre-fusion maps and leaves the GPS-input gradient
-        in self._dgps_prev."""
+    def _stage_bwd(self, rec, dfeats_out, dgps_tok, B):
+        """rec: the stage's _StageRec; dfeats_out: grads of the 3 post-fusion maps; dgps_tok: (tensor, bcast) grad of the
+        GPS rows of this stage's output.  Returns the grads of the 3 pre-fusion maps and of the GPS input (None at s = 1)."""
         L = lib()
         st = ops._stream()
-        (s, C, T, fps, offs, pe, off_e, gps_src, blk_ctx, x_last, mf, rf, fshapes) = ctx
+        s, C, T, fps, offs, fshapes = rec.s, rec.C, rec.T, rec.fps, rec.offs, rec.fshapes
         gpt = getattr(self.encoder, f"transformer{s}")
         vel = getattr(self.encoder, f"vel_emb{s}")
         dxo = torch.empty((B * T, C), dtype=F32, device=self.device)
@@ -1256,22 +1180,16 @@ class TransFuser(nn.Module):
         L.gps_rows(gsrc.data_ptr(), dxo.data_ptr(), B, C, T, 1, 0, int(bcast), st)
         gfw, af = self._g(gpt.ln_f.weight)
         gfb, _ = self._g(gpt.ln_f.bias)
-        rev = list(zip(reversed(list(gpt.blocks)), reversed(blk_ctx)))
-        drops = [(bc[12], self._seed, bc[18]) for _, bc in rev]  # (resid_pdrop, seed, fc2-branch mask offset) per block
-        if blk_ctx and blk_ctx[0][1].dtype == torch.bfloat16:   # recorded on the bf16-storage path
-            dx, dz = ops.layernorm_bwd_bf16(dxo, x_last, mf, rf, self._w(gpt.ln_f.weight), gfw, gfb, self._ws,
-                                            accumulate=bool(af), drop=drops[0])
-            for i, (blk, bc) in enumerate(rev):
-                last = i + 1 == len(rev)
-                dx, dz = self._gpt_block_bwd16(blk, bc, dx, B, T, dz, next_drop=None if last else drops[i + 1],
-                                               want_dz=not last)
-        else:
-            dx, dz = ops.layernorm_bwd(dxo, x_last, mf, rf, self._w(gpt.ln_f.weight), gfw, gfb, self._ws,
-                                       accumulate=bool(af), drop=drops[0])
-            for i, (blk, bc) in enumerate(rev):
-                dx, dz = self._gpt_block_bwd(blk, bc, dx, B, T, dz2=dz, next_drop=drops[i + 1] if i + 1 < len(rev) else None)
+        rev = list(zip(reversed(list(gpt.blocks)), reversed(rec.blocks)))
+        # (resid_pdrop, seed, fc2-branch mask offset) of each block, in backward order; None below the last
+        drops = [(bc.pr, self._seed, bc.off_m) for _, bc in rev] + [None]
+        ln_bwd = ops.layernorm_bwd_bf16 if rec.blocks and rec.blocks[0].h.dtype == BF16 else ops.layernorm_bwd
+        dx, dz = ln_bwd(dxo, rec.x_last, rec.mf, rec.rf, self._w(gpt.ln_f.weight), gfw, gfb, self._ws, accumulate=bool(af),
+                        drop=drops[0])
+        for i, (blk, bc) in enumerate(rev):
+            dx, dz = self._gpt_block_bwd(blk, bc, dx, B, T, dz2=dz, next_drop=drops[i + 1])
         self._wg_join()
-        dpre = ops.dropout(dx, pe, self._seed, off_e) if pe > 0 else dx
+        dpre = ops.dropout(dx, rec.pe, self._seed, rec.off_e) if rec.pe > 0 else dx
         gpos, apos = self._g(gpt.pos_emb)
         L.batch_sum(dpre.data_ptr(), gpos, T * C, B, T * C, apos, st)
         dfeats = []
@@ -1283,7 +1201,7 @@ class TransFuser(nn.Module):
             dfeats.append(d)
         dgemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
         L.gps_rows(dpre.data_ptr(), dgemb.data_ptr(), B, C, T, 0, 0, 0, st)
-        src_t, gptr, rpg, gstride, K = gps_src
+        _, gptr, rpg, gstride, K = rec.gps_src
         gw, aw = self._g(vel.weight)
         gb, _ = self._g(vel.bias)
         if s > 1:
@@ -1295,10 +1213,9 @@ class TransFuser(nn.Module):
                            2 * B, 0, 0, aw, st)
         return dfeats, dprev
 
-    def _stem_bwd(self, trunk, ctx, dpool, cin):
+    def _stem_bwd(self, trunk, rec, dpool, cin):
         L = lib()
-        st = ops._stream()
-        x, c1, _, st1, idx, _ = ctx
+        x, c1, st1, idx = rec.x, rec.c1, rec.stats, rec.idx
         bn = trunk.bn1
         gw_bn, a_bn = self._g(bn.weight)
         gb_bn, _ = self._g(bn.bias)
@@ -1330,9 +1247,9 @@ class TransFuser(nn.Module):
         L = lib()
         st = ops._stream()
         cfg = self.config
-        B, stem_ctx, layer_ctx, stage_ctx, head, gps, salt = tape
-        fused, h1, h2, fshapes, gru, fdtype = head
-        L.set_dropout_salt(salt.data_ptr() if salt is not None else 0)
+        B, head = tape.B, tape.head
+        fshapes, gru, fdtype = head.fshapes, head.gru, head.fdtype
+        L.set_dropout_salt(tape.salt.data_ptr() if tape.salt is not None else 0)
         self._begin_backward()
         if gru is not None:  # back through the GRU head: dpred (B, pred_len, 64) -> gradient of the join output
             z0, saved = gru
@@ -1353,6 +1270,7 @@ class TransFuser(nn.Module):
         assert dlogits.shape == (B, 64) and dlogits.dtype == F32
         S = cfg.seq_len
         j0, j2, j4 = self.join[0], self.join[2], self.join[4]
+        fused, h1, h2 = head.fused, head.h1, head.h2
         dh2 = torch.empty_like(h2)
         dh1 = torch.empty_like(h1)
         dfused = torch.empty_like(fused)
@@ -1377,7 +1295,7 @@ class TransFuser(nn.Module):
             dfeats.append(d)
         dgps = (dfused, True)
         for s in range(4, 0, -1):
-            dfeats, dprev = self._stage_bwd(stage_ctx[s - 1], dfeats, dgps, B)
+            dfeats, dprev = self._stage_bwd(tape.stages[s - 1], dfeats, dgps, B)
             self._milestone_done(1 + 2 * (4 - s))
             dgps = (dprev, False)
             streams = self._fork() if self.multi_stream else None
@@ -1385,10 +1303,10 @@ class TransFuser(nn.Module):
                 blocks = list(getattr(trunk, f"layer{s}"))
                 d = dfeats[m]
                 with self._trunk_ctx(streams, m):
-                    for blk, bc in zip(reversed(blocks), reversed(layer_ctx[s - 1][m])):
+                    for blk, bc in zip(reversed(blocks), reversed(tape.layers[s - 1][m])):
                         d = self._block_bwd(blk, bc, d)
                     if s == 1:  # the stem backward continues on the same trunk stream
-                        self._stem_bwd(trunk, stem_ctx[m], d, cin)
+                        self._stem_bwd(trunk, tape.stems[m], d, cin)
                 dfeats[m] = d
             if streams is not None:
                 self._join()
