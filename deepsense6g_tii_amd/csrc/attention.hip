@@ -82,7 +82,7 @@ struct AttnParams {
     // split slabs and every kernel-internal tensor stay fp32); o16: the backward reads its forward output as bf16
     int out16;
     int o16;
-    int in16;   // q / k / v / d_o are bf16 in HBM (kernels instantiated with BF == 4)
+    int in16;   // q / k / v / d_o are 16-bit in HBM: 1 bf16 (kernels instantiated with BF == 4), 2 f16 (BF == 5)
 };
 
 __device__ __forceinline__ int krow16(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
@@ -173,7 +173,8 @@ __device__ __forceinline__ float dim_read(unsigned tile, const unsigned* dtab, i
     return *reinterpret_cast<lds_cf*>(tile + dtab[k] + (unsigned)cst);
 }
 
-// ---- bf16-STORED tiles (template value BF == 4: q / k / v / dO live in HBM as bf16; implies the bf16 matrix cores) -------
+// ---- 16-bit STORED tiles (template value BF == 4: q / k / v / dO live in HBM as bf16; implies the bf16 matrix cores; BF == 5:
+// the same as f16 on the f16 matrix cores) -------
 // LDS image [32 rows][HD] bf16, row = HD*2 bytes, filled by LDS-DMA; the 16-B chunk index (8 dims) is XOR-swizzled by the
 // row so that BOTH read patterns are conflict-free: "row on the lane" (one ds_read_b128 = the MFMA operand of a 16-deep
 // k-step as it lies in memory) and "dim on the lane" (ds_read_b64_tr_b16: 4 rows x 16 dims per 16-lane group, delivered
@@ -185,24 +186,27 @@ __device__ __forceinline__ int swz16(int r) {
     if (HD == 32) return (r >> 2) & 3;
     return (r >> 3) & 1;
 }
-typedef __attribute__((address_space(3))) const bf16x8 lds_cb8;
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-template <int HD>
-__device__ __forceinline__ bf16x8 row_read16(unsigned tile, int r, int c) {
+// storage type of the 16-bit tiles: BF == 4 bf16, BF == 5 f16 (same images, same reads; v_mfma_f32_32x32x16_f16 instead of
+// _bf16); the fp32-storage kernels (BF 0 - 3) write their optional 16-bit output (out16) as bf16
+template <int BF> struct AttnT16 { typedef __bf16 T; };
+template <> struct AttnT16<5> { typedef _Float16 T; };
+template <int HD, typename T16>
+__device__ __forceinline__ typename H16<T16>::x8 row_read16(unsigned tile, int r, int c) {
+    typedef __attribute__((address_space(3))) const typename H16<T16>::x8 lds_cb8;
     return *reinterpret_cast<lds_cb8*>(tile + (unsigned)(r * HD * 2 + ((c ^ swz16<HD>(r)) << 4)));
 }
 // operand fragment of k-step s2 for "dim on the lane": element e <-> row krow16(8 s2 + e, half), dim 32 blk + (lane & 31)
-template <int HD>
-__device__ __forceinline__ bf16x8 dim_read16(unsigned tile, int s2, int blk, int lane) {
+template <int HD, typename T16>
+__device__ __forceinline__ typename H16<T16>::x8 dim_read16(unsigned tile, int s2, int blk, int lane) {
     const int half = lane >> 5, g = (lane >> 4) & 1, q = (lane >> 2) & 3, pp = lane & 3;
     int dim0 = blk * 32 + 16 * g + 4 * pp;
     if (HD < 32 && dim0 >= HD) dim0 -= 16;  // HD = 16: lanes 16..31 re-read valid dims (their outputs are never stored)
-    bf16x4v part[2];
+    typename H16<T16>::x4 part[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int row = 16 * s2 + 8 * t + 4 * half + q;
         const unsigned a = tile + (unsigned)(row * HD * 2 + (((dim0 >> 3) ^ swz16<HD>(row)) << 4) + (dim0 & 7) * 2);
-        part[t] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4v*)(unsigned long)a);
+        part[t] = ds_read_tr16((const T16*)nullptr, (lds16_void*)(unsigned long)a);
     }
     return __builtin_shufflevector(part[0], part[1], 0, 1, 2, 3, 4, 5, 6, 7);
 }
@@ -230,7 +234,7 @@ __device__ __forceinline__ void load_frag(float* reg, const float* base, long ro
 }
 
 // LDS-DMA of 32 x HD tiles (rows row0 .. row0 + 31 of ONE batch element's [T][ld] block, head h) into the swizzled LDS
-// image: fp32 tiles [row][HD] with the 16-B chunk index XOR swz<HD>(row), bf16 tiles (BF == 4) with swz16<HD>(row); one
+// image: fp32 tiles [row][HD] with the 16-B chunk index XOR swz<HD>(row), 16-bit tiles (BF >= 4) with swz16<HD>(row); one
 // wave-instruction moves 1 KiB, wave w issues the pieces w, w + 4, ...  Everything that does not change from tile to tile
 // is computed ONCE per kernel: the lane's byte offset of each of its pieces inside a tile at row 0 (division, modulo,
 // swizzle, head column), so a tile costs one add and one DMA instruction per piece (measured before: 1 200 clocks of address
@@ -239,7 +243,7 @@ __device__ __forceinline__ void load_frag(float* reg, const float* base, long ro
 // them - no per-lane row test.
 template <int HD, int BF>
 struct TileLoader {
-    static constexpr int EL = BF == 4 ? 2 : 4;        // bytes per element
+    static constexpr int EL = BF >= 4 ? 2 : 4;        // bytes per element
     static constexpr int CH = 16 / EL;                // elements per 16-B chunk
     static constexpr int NC = HD / CH;                // chunks per row
     static constexpr int NWI = NC / 2;                // wave-instructions (64 chunks) per 32-row tile
@@ -255,7 +259,7 @@ struct TileLoader {
         for (int j = 0; j < NP; ++j) {
             const int g = (wave + 4 * j) * 64 + lane;
             const int row = g / NC, pos = g % NC;
-            const int c = pos ^ (BF == 4 ? swz16<HD>(row) : swz<HD>(row));
+            const int c = pos ^ (BF >= 4 ? swz16<HD>(row) : swz<HD>(row));
             voff[j] = (unsigned)((row * ld + col0 + c * CH) * EL);
         }
     }
@@ -270,7 +274,7 @@ struct TileLoader {
 // bf16 storage: the fragment stays packed bf16 and is NOT scaled (callers scale the product instead; mul 0 = zero it)
 template <int HD, int BF>
 __device__ __forceinline__ void load_frag_any(float* reg, const float* base, long row_off, int half, float mul) {
-    if (BF == 4) {
+    if (BF >= 4) {
         load_frag16<HD>(reg, base, row_off, half);
         if (mul == 0.f) {
 #pragma unroll
@@ -285,12 +289,14 @@ __device__ __forceinline__ void load_frag_any(float* reg, const float* base, lon
 template <int HD, int BF>
 __device__ __forceinline__ void mma_rows(f32x16& acc, unsigned tile, const float* breg, int l31, int half) {
     constexpr int NCH = HD / 8;  // 16-B chunks per lane half
-    if (BF == 4) {  // bf16-stored: LDS chunk and register chunk ARE the operands (lane half h: dims h*HD/2 + 8c .. + 7)
+    if (BF >= 4) {  // bf16-stored: LDS chunk and register chunk ARE the operands (lane half h: dims h*HD/2 + 8c .. + 7)
 #pragma unroll
         for (int c = 0; c < HD / 16; ++c) {
-            const bf16x8 a8 = row_read16<HD>(tile, l31, half * (HD / 16) + c);
-            const bf16x8 b8 = __builtin_bit_cast(bf16x8, f32x4{breg[4 * c], breg[4 * c + 1], breg[4 * c + 2], breg[4 * c + 3]});
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a8, b8, acc, 0, 0, 0);
+            typedef typename AttnT16<BF>::T T16;
+            typedef typename H16<T16>::x8 h8;
+            const h8 a8 = row_read16<HD, T16>(tile, l31, half * (HD / 16) + c);
+            const h8 b8 = __builtin_bit_cast(h8, f32x4{breg[4 * c], breg[4 * c + 1], breg[4 * c + 2], breg[4 * c + 3]});
+            acc = mfma_32x32x16(a8, b8, acc);
         }
         return;
     }
@@ -342,16 +348,17 @@ __device__ __forceinline__ void mma_rows(f32x16& acc, unsigned tile, const float
 template <int HD, int BF>
 __device__ __forceinline__ void mma_dims(f32x16* acc, unsigned tile, const f32x16& p, const unsigned* dtab) {
     constexpr int NB = (HD + 31) / 32;
-    if (BF == 4) {  // bf16-stored tile: the A fragment comes transposed out of LDS (ds_read_b64_tr_b16), no conversion
+    if (BF >= 4) {  // bf16-stored tile: the A fragment comes transposed out of LDS (ds_read_b64_tr_b16), no conversion
         const int lane_ = (int)(threadIdx.x & 63);
+        typedef typename AttnT16<BF>::T T16;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            bf16x8 b8;
+            typename H16<T16>::x8 b8;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) b8[e] = (__bf16)p[8 * s2 + e];
+            for (int e = 0; e < 8; ++e) b8[e] = (T16)p[8 * s2 + e];
 #pragma unroll
             for (int blk = 0; blk < NB; ++blk)
-                acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dim_read16<HD>(tile, s2, blk, lane_), b8, acc[blk], 0, 0, 0);
+                acc[blk] = mfma_32x32x16(dim_read16<HD, T16>(tile, s2, blk, lane_), b8, acc[blk]);
         }
         return;
     }
@@ -447,21 +454,22 @@ __device__ __forceinline__ void mma_dims(f32x16* acc, unsigned tile, const f32x1
 
 // write an accumulator set acc[blk][16] = X^T[d][row] to global X[row][d] (row on the lane)
 template <int HD, int BF>
-__device__ __forceinline__ void store_rows16(const f32x16* acc, __bf16* base, int ld, int row, int T, int half, float mul) {
+__device__ __forceinline__ void store_rows16(const f32x16* acc, typename AttnT16<BF>::T* base, int ld, int row, int T, int half, float mul) {
     constexpr int NB = (HD + 31) / 32;
-    typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
+    typedef typename AttnT16<BF>::T T16;
+    typedef typename H16<T16>::x4 bf16x4_;
     if constexpr (quad16<HD, BF>()) {  // (see quad16) this lane holds dims 4 (lane / 16) .. + 3 of rows l16 and 16 + l16
         const int lane = (int)(threadIdx.x & 63), l16 = lane & 15, d = 4 * (lane >> 4);
         const int r_lo = row - (lane & 31) + l16;
         const float m_lo = __shfl(mul, l16, 64), m_hi = __shfl(mul, 16 + l16, 64);
         if (r_lo < T)
             *reinterpret_cast<bf16x4_*>(base + (long)r_lo * ld + d) =
-                bf16x4_{(__bf16)((acc[0][0] + acc[0][8]) * m_lo), (__bf16)((acc[0][1] + acc[0][9]) * m_lo),
-                        (__bf16)((acc[0][2] + acc[0][10]) * m_lo), (__bf16)((acc[0][3] + acc[0][11]) * m_lo)};
+                bf16x4_{(T16)((acc[0][0] + acc[0][8]) * m_lo), (T16)((acc[0][1] + acc[0][9]) * m_lo),
+                        (T16)((acc[0][2] + acc[0][10]) * m_lo), (T16)((acc[0][3] + acc[0][11]) * m_lo)};
         if (r_lo + 16 < T)
             *reinterpret_cast<bf16x4_*>(base + (long)(r_lo + 16) * ld + d) =
-                bf16x4_{(__bf16)((acc[0][4] + acc[0][12]) * m_hi), (__bf16)((acc[0][5] + acc[0][13]) * m_hi),
-                        (__bf16)((acc[0][6] + acc[0][14]) * m_hi), (__bf16)((acc[0][7] + acc[0][15]) * m_hi)};
+                bf16x4_{(T16)((acc[0][4] + acc[0][12]) * m_hi), (T16)((acc[0][5] + acc[0][13]) * m_hi),
+                        (T16)((acc[0][6] + acc[0][14]) * m_hi), (T16)((acc[0][7] + acc[0][15]) * m_hi)};
         return;
     }
     if (row >= T) return;
@@ -471,7 +479,7 @@ __device__ __forceinline__ void store_rows16(const f32x16* acc, __bf16* base, in
             const int d = NB * krow16(r, half);
             const float v0 = acc[0][r] * mul, v1 = acc[1][r] * mul;
             const float v2 = (NB == 4 ? acc[2][r] : acc[0][r + 1]) * mul, v3 = (NB == 4 ? acc[3][r] : acc[1][r + 1]) * mul;
-            *reinterpret_cast<bf16x4_*>(base + (long)row * ld + d) = bf16x4_{(__bf16)v0, (__bf16)v1, (__bf16)v2, (__bf16)v3};
+            *reinterpret_cast<bf16x4_*>(base + (long)row * ld + d) = bf16x4_{(T16)v0, (T16)v1, (T16)v2, (T16)v3};
         }
         return;
     }
@@ -482,8 +490,8 @@ __device__ __forceinline__ void store_rows16(const f32x16* acc, __bf16* base, in
             const int d = blk * 32 + 8 * g + 4 * half;
             if (d < HD)
                 *reinterpret_cast<bf16x4_*>(base + (long)row * ld + d) =
-                    bf16x4_{(__bf16)(acc[blk][4 * g] * mul), (__bf16)(acc[blk][4 * g + 1] * mul),
-                            (__bf16)(acc[blk][4 * g + 2] * mul), (__bf16)(acc[blk][4 * g + 3] * mul)};
+                    bf16x4_{(T16)(acc[blk][4 * g] * mul), (T16)(acc[blk][4 * g + 1] * mul),
+                            (T16)(acc[blk][4 * g + 2] * mul), (T16)(acc[blk][4 * g + 3] * mul)};
         }
     }
 }
@@ -596,7 +604,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
         mma_rows<HD, BF>(s, Kc, qreg, l31, half);
-        if (BF == 4) {  // the bf16-stored q fragment is unscaled: scale the scores (exact in fp32)
+        if (BF >= 4) {  // the bf16-stored q fragment is unscaled: scale the scores (exact in fp32)
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[r] *= scale2;
         }
@@ -666,7 +674,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
     const float ltot = l + __shfl_xor(l, 32, 64);
     const long stat = (long)(b * p.nh + h) * T + q_row;
     if (p.splits == 1) {
-        if (p.out16) store_rows16<HD, BF>(oacc, reinterpret_cast<__bf16*>(p.o) + head_off, p.ld, q_row, T, half, 1.0f / ltot);
+        if (p.out16) store_rows16<HD, BF>(oacc, reinterpret_cast<typename AttnT16<BF>::T*>(p.o) + head_off, p.ld, q_row, T, half, 1.0f / ltot);
         else store_rows<HD, BF>(oacc, p.o + head_off, p.ld, q_row, T, half, 1.0f / ltot);
         if (half == 0 && q_row < T) p.lse[stat] = (m + __log2f(ltot)) * 0.6931471805599453f;  // natural-log units in HBM
     } else {
@@ -703,7 +711,9 @@ __global__ __launch_bounds__(256) void attn_fwd_merge_kernel(const float* __rest
         acc += w * *reinterpret_cast<const f32x4*>(part + (size_t)s * slab + row * ld + c4 * 4);
     }
     acc = acc * (1.0f / l);
-    if (out16) {
+    if (out16 == 2) {
+        st4(reinterpret_cast<_Float16*>(o) + row * ld + c4 * 4, acc);
+    } else if (out16) {
         typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
         *reinterpret_cast<bf16x4_*>(reinterpret_cast<__bf16*>(o) + row * ld + c4 * 4) =
             bf16x4_{(__bf16)acc[0], (__bf16)acc[1], (__bf16)acc[2], (__bf16)acc[3]};
@@ -795,7 +805,7 @@ __global__ __launch_bounds__(256, (HD >= 128 ? 1 : 2)) void attn_bwd_dq_kernel(c
         step(Xa0, Xb0, Xa1, Xb1, kt, kt + 1 < t_end);
         if (kt + 1 < t_end) step(Xa1, Xb1, Xa0, Xb0, kt + 1, kt + 2 < t_end);
     }
-    if (p.splits == 1 && p.out16) store_rows16<HD, BF>(dq, reinterpret_cast<__bf16*>(p.dq) + head_offd, p.ldd, q_row, T, half, 1.0f);
+    if (p.splits == 1 && p.out16) store_rows16<HD, BF>(dq, reinterpret_cast<typename AttnT16<BF>::T*>(p.dq) + head_offd, p.ldd, q_row, T, half, 1.0f);
     else if (p.splits == 1) store_rows<HD, BF>(dq, p.dq + head_offd, p.ldd, q_row, T, half, 1.0f);
     else store_rows<HD, BF>(dq, p.dq + (size_t)split * p.slab + head_off, p.ld, q_row, T, half, 1.0f);
 }
@@ -904,16 +914,18 @@ __global__ __launch_bounds__(256, (HD <= 16 ? 3 : (HD <= 64 ? 2 : (PART == 1 ? 2
         ATTN_CLK(3);   // elementwise (exp, dropout hash, dS)
         if (HAND) {  // tile image: [reg / 4][lane][reg % 4] - four 1-KiB stores per wave and tensor
             const size_t tile = ((((size_t)(b * p.nh + h) * p.nkg + qt) * p.nkg) + (bx_ * 4 + wave)) * 1024 + lane * 4;
-            if (BF == 4) {
+            if (BF >= 4) {
                 // bf16-stored path: attn_bwd_dq2_kernel rounds dS to bf16 on its way into the MFMA anyway, so the tile is handed
                 // over AS bf16 - [reg / 8][lane][reg % 8], two 1-KiB stores, half the HBM bytes in both kernels (dQ from dS
                 // was HBM-bound on these tiles: 201 MB per layer at bs = 12), bit-identical dQ
-                bf16x8* ds16 = reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(p.hs) + (tile - lane * 4) + lane * 8);
+                typedef typename AttnT16<BF>::T T16;
+                typedef typename H16<T16>::x8 h8;
+                h8* ds16 = reinterpret_cast<h8*>(reinterpret_cast<T16*>(p.hs) + (tile - lane * 4) + lane * 8);
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
-                    bf16x8 v;
+                    h8 v;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = key_ok ? (__bf16)dp[8 * g + e] : (__bf16)0.f;
+                    for (int e = 0; e < 8; ++e) v[e] = key_ok ? (T16)dp[8 * g + e] : (T16)0.f;
                     ds16[g * 64] = v;
                 }
             } else {
@@ -939,7 +951,7 @@ __global__ __launch_bounds__(256, (HD <= 16 ? 3 : (HD <= 64 ? 2 : (PART == 1 ? 2
         ATTN_CLK(6);   // dK product
         // the next tile's DMA is older than this step's hand-over stores and vmcnt retires in order: wait for the DMA
         // only, the 4 (8) stores drain under the next step
-        if (HAND) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BF == 4 ? 2 : 4) + (PART == 2 ? 4 : 0)) : "memory");
+        if (HAND) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BF >= 4 ? 2 : 4) + (PART == 2 ? 4 : 0)) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ATTN_CLK(7);   // wait for the next tile's DMA
         __syncthreads();
@@ -961,8 +973,8 @@ __global__ __launch_bounds__(256, (HD <= 16 ? 3 : (HD <= 64 ? 2 : (PART == 1 ? 2
         if (qt + 1 < t_end) step(Xa1, Xb1, Xa0, Xb0, qt + 1, 1, qt + 2 < t_end);
     }
     if (p.splits == 1 && p.out16) {
-        if (DO_DK) store_rows16<HD, BF>(dk, reinterpret_cast<__bf16*>(p.dk) + head_offd, p.ldd, key, T, half, 1.0f);
-        if (DO_DV) store_rows16<HD, BF>(dv, reinterpret_cast<__bf16*>(p.dv) + head_offd, p.ldd, key, T, half, 1.0f);
+        if (DO_DK) store_rows16<HD, BF>(dk, reinterpret_cast<typename AttnT16<BF>::T*>(p.dk) + head_offd, p.ldd, key, T, half, 1.0f);
+        if (DO_DV) store_rows16<HD, BF>(dv, reinterpret_cast<typename AttnT16<BF>::T*>(p.dv) + head_offd, p.ldd, key, T, half, 1.0f);
     } else if (p.splits == 1) {
         if (DO_DK) store_rows<HD, BF>(dk, p.dk + head_offd, p.ldd, key, T, half, 1.0f);
         if (DO_DV) store_rows<HD, BF>(dv, p.dv + head_offd, p.ldd, key, T, half, 1.0f);
@@ -983,7 +995,14 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
     const float* a = o + row * ld + h * hd;
     const float* g = d_o + row * ld + h * hd;
     float acc = 0.f;
-    if (o16 == 3) {       // o and dO both bf16
+    if (o16 == 6) {       // o and dO both f16
+        const _Float16* a16 = reinterpret_cast<const _Float16*>(o) + row * ld + h * hd;
+        const _Float16* g16 = reinterpret_cast<const _Float16*>(d_o) + row * ld + h * hd;
+        for (int d = 0; d < hd; d += 4) {
+            const f32x4 x = ld4(a16 + d), y = ld4(g16 + d);
+            acc += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
+        }
+    } else if (o16 == 3) {       // o and dO both bf16
         typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
         const __bf16* a16 = reinterpret_cast<const __bf16*>(o) + row * ld + h * hd;
         const __bf16* g16 = reinterpret_cast<const __bf16*>(d_o) + row * ld + h * hd;
@@ -1029,12 +1048,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const AttnParams p
     const bool have = qt < ntiles;  // wave-uniform: query tiles beyond T were never written
     float f[16], fn[16];
     auto fetch = [&](float* dst, int kt) {
-        if (BF == 4) {   // bf16 tiles [reg / 8][lane][reg % 8] (see attn_bwd_dkv_kernel)
-            const __bf16* t16 = reinterpret_cast<const __bf16*>(p.hs) + ((((size_t)(b * p.nh + h) * p.nkg + qt) * p.nkg) + kt) * 1024 + lane * 8;
+        if (BF >= 4) {   // bf16 tiles [reg / 8][lane][reg % 8] (see attn_bwd_dkv_kernel)
+            typedef typename AttnT16<BF>::T T16;
+            typedef typename H16<T16>::x8 h8;
+            const T16* t16 = reinterpret_cast<const T16*>(p.hs) + ((((size_t)(b * p.nh + h) * p.nkg + qt) * p.nkg) + kt) * 1024 + lane * 8;
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-                bf16x8 v;
-                if (have) v = *reinterpret_cast<const bf16x8*>(t16 + g * 512);
+                h8 v;
+                if (have) v = *reinterpret_cast<const h8*>(t16 + g * 512);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) dst[8 * g + e] = have ? (float)v[e] : 0.f;
             }
@@ -1079,7 +1100,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const AttnParams p
         step(Xa0, Xa1, kt, kt + 1 < t_end);
         if (kt + 1 < t_end) step(Xa1, Xa0, kt + 1, kt + 2 < t_end);
     }
-    if (p.splits == 1 && p.out16) store_rows16<HD, BF>(dq, reinterpret_cast<__bf16*>(p.dq) + head_offd, p.ldd, q_row, T, half, 1.0f);
+    if (p.splits == 1 && p.out16) store_rows16<HD, BF>(dq, reinterpret_cast<typename AttnT16<BF>::T*>(p.dq) + head_offd, p.ldd, q_row, T, half, 1.0f);
     else if (p.splits == 1) store_rows<HD, BF>(dq, p.dq + head_offd, p.ldd, q_row, T, half, 1.0f);
     else store_rows<HD, BF>(dq, p.dq + (size_t)split * p.slab + head_off, p.ld, q_row, T, half, 1.0f);
 }
@@ -1130,7 +1151,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dv2_kernel(const AttnParams p
         step(Xb0, Xb1, qt, qt + 1 < t_end);
         if (qt + 1 < t_end) step(Xb1, Xb0, qt + 1, qt + 2 < t_end);
     }
-    if (p.splits == 1 && p.out16) store_rows16<HD, BF>(dv, reinterpret_cast<__bf16*>(p.dv) + head_offd, p.ldd, key, T, half, 1.0f);
+    if (p.splits == 1 && p.out16) store_rows16<HD, BF>(dv, reinterpret_cast<typename AttnT16<BF>::T*>(p.dv) + head_offd, p.ldd, key, T, half, 1.0f);
     else if (p.splits == 1) store_rows<HD, BF>(dv, p.dv + head_offd, p.ldd, key, T, half, 1.0f);
     else store_rows<HD, BF>(dv, p.dv + (size_t)split * p.slab + head_off, p.ld, key, T, half, 1.0f);
 }
@@ -1150,7 +1171,9 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
     const float* src = part + row * ld_in + c;
     f32x4 s = *reinterpret_cast<const f32x4*>(src);
     for (int k = 1; k < splits; ++k) s += *reinterpret_cast<const f32x4*>(src + (size_t)k * slab);
-    if (out16) {
+    if (out16 == 2) {
+        st4(reinterpret_cast<_Float16*>(out) + row * ld_out + c, s);
+    } else if (out16) {
         typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
         *reinterpret_cast<bf16x4_*>(reinterpret_cast<__bf16*>(out) + row * ld_out + c) =
             bf16x4_{(__bf16)s[0], (__bf16)s[1], (__bf16)s[2], (__bf16)s[3]};
@@ -1216,19 +1239,19 @@ int launch_hd_bf(const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
     return DS6G_OK;
 }
 
-// bf16-stored q / k / v / dO (BF == 4): forward, dK/dV with hand-over, dV from P (HD = 128), dQ from dS
-template <int KIND>
+// 16-bit stored q / k / v / dO (BF >= 4): forward, dK/dV with hand-over, dV from P (HD = 128), dQ from dS
+template <int KIND, int BF>
 int launch_hd_st(const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
 #define ATTN_CASE16(HDV)                                                                                      \
     case HDV:                                                                                                 \
-        if constexpr (KIND == 0) hipLaunchKernelGGL((attn_fwd_kernel<HDV, 4>), grid, dim3(256), 0, st, p);    \
+        if constexpr (KIND == 0) hipLaunchKernelGGL((attn_fwd_kernel<HDV, BF>), grid, dim3(256), 0, st, p);    \
         if constexpr (KIND == 3) {                                                                            \
-            if constexpr (HDV >= 128) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 2, 4, 1>), grid, dim3(256), 0, st, p); \
-            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 0, 4, 1>), grid, dim3(256), 0, st, p);          \
+            if constexpr (HDV >= 128) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 2, BF, 1>), grid, dim3(256), 0, st, p); \
+            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 0, BF, 1>), grid, dim3(256), 0, st, p);          \
         }                                                                                                     \
-        if constexpr (KIND == 4 && HDV >= 128) hipLaunchKernelGGL((attn_bwd_dv2_kernel<HDV, 4>), grid, dim3(256), 0, st, p); \
-        if constexpr (KIND == 5) hipLaunchKernelGGL((attn_bwd_dq2_kernel<HDV, 4>), grid, dim3(256), 0, st, p); \
-        if constexpr (KIND == 6 && HDV >= 128) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 0, 4, 1>), grid, dim3(256), 0, st, p); \
+        if constexpr (KIND == 4 && HDV >= 128) hipLaunchKernelGGL((attn_bwd_dv2_kernel<HDV, BF>), grid, dim3(256), 0, st, p); \
+        if constexpr (KIND == 5) hipLaunchKernelGGL((attn_bwd_dq2_kernel<HDV, BF>), grid, dim3(256), 0, st, p); \
+        if constexpr (KIND == 6 && HDV >= 128) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 0, BF, 1>), grid, dim3(256), 0, st, p); \
         break;
     switch (hd) {
         ATTN_CASE16(16)
@@ -1247,7 +1270,7 @@ int launch_hd_st(const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
 template <int KIND>
 int launch_hd(const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
     if (p.in16) {
-        if constexpr (KIND == 0 || KIND == 3 || KIND == 4 || KIND == 5 || KIND == 6) return launch_hd_st<KIND>(p, hd, grid, st);
+        if constexpr (KIND == 0 || KIND == 3 || KIND == 4 || KIND == 5 || KIND == 6) return p.in16 == 2 ? launch_hd_st<KIND, 5>(p, hd, grid, st) : launch_hd_st<KIND, 4>(p, hd, grid, st);
         else return DS6G_ERR_ARG;
     }
     if (g_ds6g_bf16 == 3) return launch_hd_bf<KIND, 3>(p, hd, grid, st);
@@ -1331,6 +1354,15 @@ int ds6g_attention_fwd_bf16(const void* q, const void* k, const void* v, void* o
                             void* stream) {
     DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0);
     return attention_fwd_impl((const float*)q, (const float*)k, (const float*)v, 1, (float*)o, 1, lse, B, T, nh, hd, ld_qkv, ld,
+                              drop_p, seed, seed_off, ws, ws_bytes, stream);
+}
+
+// the same on f16 storage (o written as f16; P tiles rounded to f16 on their way into v_mfma_f32_32x32x16_f16)
+int ds6g_attention_fwd_f16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh, int hd,
+                           int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
+                           void* stream) {
+    DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0);
+    return attention_fwd_impl((const float*)q, (const float*)k, (const float*)v, 2, (float*)o, 2, lse, B, T, nh, hd, ld_qkv, ld,
                               drop_p, seed, seed_off, ws, ws_bytes, stream);
 }
 
@@ -1482,6 +1514,17 @@ int ds6g_attention_bwd_bf16io(const void* q, const void* k, const void* v, const
     DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0 && ld_dqkv % 4 == 0);
     return attention_bwd_impl((const float*)q, (const float*)k, (const float*)v, 1, (const float*)o, 1, (const float*)d_o, lse, delta,
                               (float*)dq, (float*)dk, (float*)dv, 1, B, T, nh, hd, ld_qkv, ld, ld_dqkv, drop_p, seed, seed_off, ws,
+                              ws_bytes, stream);
+}
+
+// the same on f16 storage (dS tiles handed over as f16)
+int ds6g_attention_bwd_f16io(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                             float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd, int ld_qkv, int ld,
+                             int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
+                             void* stream) {
+    DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0 && ld_dqkv % 4 == 0);
+    return attention_bwd_impl((const float*)q, (const float*)k, (const float*)v, 2, (const float*)o, 2, (const float*)d_o, lse, delta,
+                              (float*)dq, (float*)dk, (float*)dv, 2, B, T, nh, hd, ld_qkv, ld, ld_dqkv, drop_p, seed, seed_off, ws,
                               ws_bytes, stream);
 }
 

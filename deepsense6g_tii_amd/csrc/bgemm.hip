@@ -44,7 +44,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct BgemmParams {
-    const __bf16* a_src;
+    const __bf16* a_src;  // 16-bit storage, __bf16 or _Float16 (the pointers only address bytes)
     const __bf16* b_src;
     void* out;            // float* (fp32 output / split-K slabs) or __bf16*
     int N, H, W, C;       // input-side tensor (x / dx), NHWC
@@ -95,9 +95,11 @@ __device__ __forceinline__ unsigned lds_off(const void* p) { return (unsigned)(u
 // slower on every model shape but the 240-workgroup 16x16x256 layers (28.3 -> 23.7 us): the step is then paced by the producer
 // wave's own issue chain (8 pieces = 800 - 1 000 cycles, i.e. ~27 cycles per KiB and CU through the texture-address unit),
 // which is the same load-path limit seen from the other side (profiles/r04_bgemm_classic_vs_producer_consumer.txt).  Not kept.
-template <int MODE, int BM, int BN, int OUT16, int EPI>
+template <int MODE, int BM, int BN, int OUT16, int EPI, typename T16>
 __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
     BgemmParams p = pin;
+    typedef typename H16<T16>::x4 h4;
+    typedef typename H16<T16>::x8 h8;
     GCLK_DECL(g_bgemm_wg);
     if (EPI && p.drop_thr && p.salt) p.seed_off += *p.salt;
     if (MODE == B_DGRAD && pin.nclass > 1) {
@@ -354,34 +356,30 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
 #pragma unroll 8
             for (int k = 0; k < BK; ++k) {
                 const int pseg = (A_RB == 256) ? (seg ^ (k & 3)) : (seg ^ ((k >> 1) & 1));
-                csum += (float)*reinterpret_cast<const __bf16*>(Ac + k * A_RB + pseg * 64 + (tid & 31) * 2);
+                csum += (float)*reinterpret_cast<const T16*>(Ac + k * A_RB + pseg * 64 + (tid & 31) * 2);
             }
         }
-        bf16x8 af[4][TM], bfr[4][TN];
+        h8 af[4][TM], bfr[4][TN];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 if (A_T) {
-                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4*)(lds_void*)(Ac + t_addr(A_RB, wm * WR + i * 32, s, 0)));
-                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4*)(lds_void*)(Ac + t_addr(A_RB, wm * WR + i * 32, s, 1)));
+                    const h4 lo = ds_read_tr16((const T16*)nullptr, (lds_void*)(Ac + t_addr(A_RB, wm * WR + i * 32, s, 0)));
+                    const h4 hi = ds_read_tr16((const T16*)nullptr, (lds_void*)(Ac + t_addr(A_RB, wm * WR + i * 32, s, 1)));
                     af[s][i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 } else {
-                    af[s][i] = *reinterpret_cast<const bf16x8*>(Ac + ka_row + i * 32 * 128 + ((((unsigned)(2 * s + khalf)) ^ kswz) << 4));
+                    af[s][i] = *reinterpret_cast<const h8*>(Ac + ka_row + i * 32 * 128 + ((((unsigned)(2 * s + khalf)) ^ kswz) << 4));
                 }
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 if (B_T) {
-                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4*)(lds_void*)(Bc + t_addr(B_RB, wn * (BN / 2) + j * 32, s, 0)));
-                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4*)(lds_void*)(Bc + t_addr(B_RB, wn * (BN / 2) + j * 32, s, 1)));
+                    const h4 lo = ds_read_tr16((const T16*)nullptr, (lds_void*)(Bc + t_addr(B_RB, wn * (BN / 2) + j * 32, s, 0)));
+                    const h4 hi = ds_read_tr16((const T16*)nullptr, (lds_void*)(Bc + t_addr(B_RB, wn * (BN / 2) + j * 32, s, 1)));
                     bfr[s][j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 } else {
-                    bfr[s][j] = *reinterpret_cast<const bf16x8*>(Bc + kb_row + j * 32 * 128 + ((((unsigned)(2 * s + khalf)) ^ kswz) << 4));
+                    bfr[s][j] = *reinterpret_cast<const h8*>(Bc + kb_row + j * 32 * 128 + ((((unsigned)(2 * s + khalf)) ^ kswz) << 4));
                 }
             }
         }
@@ -391,7 +389,7 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][i], bfr[s][j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = mfma_32x32x16(af[s][i], bfr[s][j], acc[i][j]);
     };
 
     // two stages: the DMA of tile t+1 flies under the MFMAs of tile t; one wait + barrier per k-tile
@@ -492,9 +490,9 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
     // [BM/2 rows][BN/2 cols] so that global stores are 16-byte row pieces (the loop's last barrier has been passed by
     // every wave: the staging buffers are free)
     {
-        __bf16* outp = reinterpret_cast<__bf16*>(p.out);
+        T16* outp = reinterpret_cast<T16*>(p.out);
         constexpr int PR = WR, PC = BN / 2;
-        __bf16* patch = reinterpret_cast<__bf16*>(lds) + wave * PR * PC;
+        T16* patch = reinterpret_cast<T16*>(lds) + wave * PR * PC;
         const bool stats = !EPI && MODE == B_FWD && p.bn_partial != nullptr;
         float cs[TN], cq[TN];
 #pragma unroll
@@ -516,7 +514,7 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
                         if (p.drop_thr)
                             v = ds6g_keep(p.seed, p.seed_off + (uint64_t)((size_t)(row0 + dr) * p.Ng + col), p.drop_thr) ? v * p.drop_scale : 0.f;
                     }
-                    const __bf16 vb = (__bf16)v;
+                    const T16 vb = (T16)v;
                     patch[(i * 32 + 4 * khalf + dr) * PC + j * 32 + l31] = vb;
                     if (!EPI && MODE == B_FWD) {   // rows >= Mg are products of zero-filled im2col rows: they add 0
                         const float vr = (float)vb;
@@ -554,31 +552,31 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
             const int rl = idx / PPR, pc = idx - rl * PPR;
             const int grow = m0 + wm * PR + rl, gcol = n0 + wn * PC + pc * 8;
             if (grow < p.Mg && gcol < p.Ng) {
-                bf16x8 v = *reinterpret_cast<const bf16x8*>(patch + rl * PC + pc * 8);
+                h8 v = *reinterpret_cast<const h8*>(patch + rl * PC + pc * 8);
                 if (EPI && p.mask_src) {
                     // ReLU mask of the forward activation ([Mg][Ng], the output's own shape): applied here, where a lane holds
                     // 8 consecutive columns of one row - one 16-byte (bf16) or two 16-byte (fp32) loads instead of 8 scalar
                     // ones per lane in accumulator order (the masked dgrad ran 54.8 us against 27.7 us for the plain one)
                     const size_t e = (size_t)grow * p.Ng + gcol;
                     if (p.mask16) {
-                        const bf16x8 mv = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const __bf16*>(p.mask_src) + e);
+                        const h8 mv = *reinterpret_cast<const h8*>(reinterpret_cast<const T16*>(p.mask_src) + e);
 #pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = (float)mv[q] > 0.f ? v[q] : (__bf16)0.f;
+                        for (int q = 0; q < 8; ++q) v[q] = (float)mv[q] > 0.f ? v[q] : (T16)0.f;
                     } else {
                         const float* mp = reinterpret_cast<const float*>(p.mask_src) + e;
                         const f32x4 m0v = *reinterpret_cast<const f32x4*>(mp), m1v = *reinterpret_cast<const f32x4*>(mp + 4);
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            v[q] = m0v[q] > 0.f ? v[q] : (__bf16)0.f;
-                            v[4 + q] = m1v[q] > 0.f ? v[4 + q] : (__bf16)0.f;
+                            v[q] = m0v[q] > 0.f ? v[q] : (T16)0.f;
+                            v[4 + q] = m1v[q] > 0.f ? v[4 + q] : (T16)0.f;
                         }
                     }
                 }
-                bf16x8* dst = reinterpret_cast<bf16x8*>(outp + out_row(grow) * p.Ng + gcol);
+                h8* dst = reinterpret_cast<h8*>(outp + out_row(grow) * p.Ng + gcol);
                 if (p.accumulate) {
-                    const bf16x8 old = *dst;
+                    const h8 old = *dst;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (__bf16)((float)v[e] + (float)old[e]);
+                    for (int e = 0; e < 8; ++e) v[e] = (T16)((float)v[e] + (float)old[e]);
                 }
                 *dst = v;
             }
@@ -631,32 +629,32 @@ bool bgemm_wgrad_walk(BgemmParams& p) {
     return false;
 }
 
-template <int MODE, int OUT16, int EPI>
+template <int MODE, int OUT16, int EPI, typename T16>
 int launch_tiles(BgemmParams& p, int splits, int tile, hipStream_t st) {
     dim3 block(256);
     const int ny = p.nclass > 1 ? p.nclass : 1;
     if (tile == 0) {
         p.tiles_n = cdiv(p.Ng, 128);
         dim3 grid(cdiv(p.Mg, 128) * p.tiles_n, ny, splits);
-        hipLaunchKernelGGL((bgemm_kernel<MODE, 128, 128, OUT16, EPI>), grid, block, 0, st, p);
+        hipLaunchKernelGGL((bgemm_kernel<MODE, 128, 128, OUT16, EPI, T16>), grid, block, 0, st, p);
     } else {
         p.tiles_n = cdiv(p.Ng, 64);
         dim3 grid(cdiv(p.Mg, 64) * p.tiles_n, ny, splits);
-        hipLaunchKernelGGL((bgemm_kernel<MODE, 64, 64, OUT16, EPI>), grid, block, 0, st, p);
+        hipLaunchKernelGGL((bgemm_kernel<MODE, 64, 64, OUT16, EPI, T16>), grid, block, 0, st, p);
     }
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
 
-template <int MODE>
+template <int MODE, typename T16>
 int launch_bgemm(BgemmParams& p, int out16, int splits, int tile, hipStream_t st) {
     if ((size_t)p.Mg * p.Ng * 4 >= OOB_OFF) return DS6G_ERR_ARG;
     const bool epi = p.bias || p.relu || p.mask_src || p.drop_thr || p.residual;
     void* rec = ds6g_prof_open(30000 + 100 * out16 + 10 * MODE + tile, 2.0 * p.Mg * p.Ng * p.Kg, st);
     int rc;
-    if (MODE == B_WGRAD) rc = launch_tiles<MODE, 0, 0>(p, splits, tile, st);
-    else if (out16) rc = epi ? launch_tiles<MODE, 1, 1>(p, splits, tile, st) : launch_tiles<MODE, 1, 0>(p, splits, tile, st);
-    else rc = epi ? launch_tiles<MODE, 0, 1>(p, splits, tile, st) : launch_tiles<MODE, 0, 0>(p, splits, tile, st);
+    if (MODE == B_WGRAD) rc = launch_tiles<MODE, 0, 0, T16>(p, splits, tile, st);
+    else if (out16) rc = epi ? launch_tiles<MODE, 1, 1, T16>(p, splits, tile, st) : launch_tiles<MODE, 1, 0, T16>(p, splits, tile, st);
+    else rc = epi ? launch_tiles<MODE, 0, 1, T16>(p, splits, tile, st) : launch_tiles<MODE, 0, 0, T16>(p, splits, tile, st);
     ds6g_prof_close(rec, st);
     return rc;
 }
@@ -667,6 +665,7 @@ int pick_tile(int Mg, int Ng, long splits) {
     return ((long)cdiv(Mg, 128) * cdiv(Ng, 128) * splits >= g_bg_min_blocks && Mg > 64 && Ng > 64) ? 0 : 1;
 }
 
+template <typename T16>
 int run_wgrad(BgemmParams& p, float* dw, int accumulate, float* dbias, float* ws, size_t ws_bytes, hipStream_t st) {
     const long out_elems = (long)p.Mg * p.Ng;
     DS6G_CHECK_ARG(out_elems % 4 == 0 && p.Mg % 4 == 0);
@@ -693,11 +692,11 @@ int run_wgrad(BgemmParams& p, float* dw, int accumulate, float* dbias, float* ws
     }
     if (splits == 1 && !accumulate && !dbias) {
         p.out = dw;
-        return launch_bgemm<B_WGRAD>(p, 0, 1, tile, st);
+        return launch_bgemm<B_WGRAD, T16>(p, 0, 1, tile, st);
     }
     DS6G_CHECK_ARG(ws != nullptr && (size_t)splits * slab_elems * sizeof(float) <= ws_bytes);
     p.out = ws;
-    const int rc = launch_bgemm<B_WGRAD>(p, 0, (int)splits, tile, st);
+    const int rc = launch_bgemm<B_WGRAD, T16>(p, 0, (int)splits, tile, st);
     if (rc) return rc;
     return ds6g_internal_splitk_reduce(ws, dw, out_elems / 4, dbias, dbias ? p.Mg / 4 : 0, (int)splits, (size_t)slab_elems,
                                        accumulate, accumulate, st);
@@ -714,7 +713,8 @@ extern "C" {
 
 // y = conv(x, w): x [N][H][W][C] bf16, w [K][R][S][C] bf16 (the bf16 weight shadow), y [N][Ho][Wo][K] bf16 (out16) or fp32.
 // C % 64 == 0, K % 8 == 0.
-int ds6g_bf16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
+extern "C++" template <typename T16>
+static int h16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
                          int stride, int pad, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && w && y && C % BK == 0 && K % 8 == 0 && N > 0);
@@ -724,14 +724,23 @@ int ds6g_bf16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N
     p.a_src = (const __bf16*)x; p.b_src = (const __bf16*)w; p.out = y;
     p.a_bytes = (unsigned)((size_t)N * H * W * C * 2); p.b_bytes = (unsigned)((size_t)K * R * S * C * 2);
     p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
-    return launch_bgemm<B_FWD>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
+    return launch_bgemm<B_FWD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
+}
+int ds6g_bf16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
+                         int stride, int pad, void* stream) {
+    return h16_conv2d_fwd<__bf16>(x, w, y, out16, N, H, W, C, K, R, S, stride, pad, stream);
+}
+int ds6g_f16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
+                        int stride, int pad, void* stream) {
+    return h16_conv2d_fwd<_Float16>(x, w, y, out16, N, H, W, C, K, R, S, stride, pad, stream);
 }
 
 // y = conv(x, w) as above with a bf16 output, plus the train-mode BatchNorm statistics of y (batch mean / invstd, running
 // statistics updated in place when given) from per-tile column partials written by the conv's epilogue: the statistics are
 // those of the STORED bf16 tensor (what ds6g_bf16_bn_stats would compute), without a pass over it.
 // ws: >= ds6g_bf16_conv_bnstats_workspace_bytes(N * Ho * Wo, K).
-int ds6g_bf16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
+extern "C++" template <typename T16>
+static int h16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
                                  int stride, int pad, float eps, float momentum, float* mean, float* invstd,
                                  float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
@@ -746,17 +755,31 @@ int ds6g_bf16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, i
     const int nblk = cdiv(p.Mg, tile == 0 ? 128 : 64);
     DS6G_CHECK_ARG(ws_bytes >= (size_t)nblk * 2 * K * sizeof(double));
     p.bn_partial = (double*)ws;
-    const int rc = launch_bgemm<B_FWD>(p, 1, 1, tile, (hipStream_t)stream);
+    const int rc = launch_bgemm<B_FWD, T16>(p, 1, 1, tile, (hipStream_t)stream);
     if (rc) return rc;
     return ds6g_internal_bn_stats_finalize(p.bn_partial, nblk, (long)p.Mg, K, eps, momentum, mean, invstd, running_mean,
                                            running_var, (hipStream_t)stream);
 }
+int ds6g_bf16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
+                                 int stride, int pad, float eps, float momentum, float* mean, float* invstd,
+                                 float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream) {
+    return h16_conv2d_fwd_bnstats<__bf16>(x, w, y, N, H, W, C, K, R, S, stride, pad, eps, momentum, mean, invstd, running_mean,
+                                          running_var, ws, ws_bytes, stream);
+}
+int ds6g_f16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
+                                int stride, int pad, float eps, float momentum, float* mean, float* invstd, float* running_mean,
+                                float* running_var, void* ws, size_t ws_bytes, void* stream) {
+    return h16_conv2d_fwd_bnstats<_Float16>(x, w, y, N, H, W, C, K, R, S, stride, pad, eps, momentum, mean, invstd,
+                                            running_mean, running_var, ws, ws_bytes, stream);
+}
 
 size_t ds6g_bf16_conv_bnstats_workspace_bytes(long M, int K) { return (size_t)cdiv(M, 64) * 2 * K * sizeof(double); }
+size_t ds6g_f16_conv_bnstats_workspace_bytes(long M, int K) { return ds6g_bf16_conv_bnstats_workspace_bytes(M, K); }
 
 // dx (+)= conv^T(dy, w): dy bf16, w bf16, dx bf16 / fp32.  K % 64 == 0, C % 8 == 0; stride 1, or 2 with even H, W (the four
 // input-pixel parity classes of a stride-2 layer run as one launch).
-int ds6g_bf16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R,
+extern "C++" template <typename T16>
+static int h16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R,
                            int S, int stride, int pad, int accumulate, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(dy && w && dx && K % BK == 0 && C % 8 == 0 && (stride == 1 || (stride == 2 && H % 2 == 0 && W % 2 == 0)));
@@ -770,14 +793,23 @@ int ds6g_bf16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, i
         p.hstep = 2; p.Hs = H / 2; p.wstep = 2; p.Ws = W / 2; p.rstep = 2; p.sstep = 2;
         p.nr = (R + 1) / 2; p.ns = (S + 1) / 2;
         p.Mg = N * p.Hs * p.Ws; p.Ng = C; p.Kg = p.nr * p.ns * K;   // the largest class (tile choice); classes derive their own
-        return launch_bgemm<B_DGRAD>(p, out16, 1, pick_tile(p.Mg, p.Ng, 4), (hipStream_t)stream);
+        return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 4), (hipStream_t)stream);
     }
     p.Mg = N * H * W; p.Ng = C; p.Kg = R * S * K;
-    return launch_bgemm<B_DGRAD>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
+    return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
+}
+int ds6g_bf16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R, int S,
+                           int stride, int pad, int accumulate, void* stream) {
+    return h16_conv2d_dgrad<__bf16>(dy, w, dx, out16, N, H, W, C, K, R, S, stride, pad, accumulate, stream);
+}
+int ds6g_f16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R, int S,
+                          int stride, int pad, int accumulate, void* stream) {
+    return h16_conv2d_dgrad<_Float16>(dy, w, dx, out16, N, H, W, C, K, R, S, stride, pad, accumulate, stream);
 }
 
 // dw (+)= dy^T im2col(x): x, dy bf16 -> dw fp32 [K][R][S][C] (the gradient arena).  ws: split-K slabs.
-int ds6g_bf16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
+extern "C++" template <typename T16>
+static int h16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
                            int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && dy && dw && C % 8 == 0 && K % 8 == 0);
@@ -787,12 +819,21 @@ int ds6g_bf16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int 
     p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)x;
     p.a_bytes = (unsigned)((size_t)N * p.Ho * p.Wo * K * 2); p.b_bytes = (unsigned)((size_t)N * H * W * C * 2);
     p.Mg = K; p.Ng = R * S * C; p.Kg = N * p.Ho * p.Wo;
-    return run_wgrad(p, dw, accumulate, nullptr, ws, ws_bytes, (hipStream_t)stream);
+    return run_wgrad<T16>(p, dw, accumulate, nullptr, ws, ws_bytes, (hipStream_t)stream);
+}
+int ds6g_bf16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
+                           int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
+    return h16_conv2d_wgrad<__bf16>(x, dy, dw, N, H, W, C, K, R, S, stride, pad, accumulate, ws, ws_bytes, stream);
+}
+int ds6g_f16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S, int stride,
+                          int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
+    return h16_conv2d_wgrad<_Float16>(x, dy, dw, N, H, W, C, K, R, S, stride, pad, accumulate, ws, ws_bytes, stream);
 }
 
 // y[M][N] = residual + dropout(act(x[M][K] @ w[N][K]^T + bias)): x, w bf16; bias, residual fp32; y bf16 (out16) or fp32.
 // K % 64 == 0, N % 8 == 0.
-int ds6g_bf16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
+extern "C++" template <typename T16>
+static int h16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
                          const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && w && y && K % BK == 0 && N % 8 == 0 && M > 0 && drop_p >= 0.f && drop_p < 1.f);
@@ -806,12 +847,21 @@ int ds6g_bf16_linear_fwd(const void* x, const void* w, const float* bias, void* 
     p.seed = seed; p.seed_off = seed_off; p.salt = g_ds6g_salt;
     p.a_bytes = (unsigned)((size_t)M * K * 2); p.b_bytes = (unsigned)((size_t)N * K * 2);
     p.Mg = M; p.Ng = N; p.Kg = K;
-    return launch_bgemm<B_FWD>(p, out16, 1, pick_tile(M, N, 1), (hipStream_t)stream);
+    return launch_bgemm<B_FWD, T16>(p, out16, 1, pick_tile(M, N, 1), (hipStream_t)stream);
+}
+int ds6g_bf16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
+                         const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
+    return h16_linear_fwd<__bf16>(x, w, bias, y, out16, M, N, K, relu, residual, drop_p, seed, seed_off, stream);
+}
+int ds6g_f16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
+                        const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
+    return h16_linear_fwd<_Float16>(x, w, bias, y, out16, M, N, K, relu, residual, drop_p, seed, seed_off, stream);
 }
 
 // dx[M][K] (+)= (dy[M][N] @ w[N][K]) * (mask_src > 0): dy, w bf16; mask_src [M][K] bf16 (mask16) or fp32, bf16 output only;
 // dx bf16 (out16) or fp32.  N % 64 == 0, K % 8 == 0.
-int ds6g_bf16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
+extern "C++" template <typename T16>
+static int h16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
                            int mask16, int accumulate, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(dy && w && dx && N % BK == 0 && K % 8 == 0);
@@ -823,11 +873,20 @@ int ds6g_bf16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, i
     p.accumulate = accumulate;
     p.a_bytes = (unsigned)((size_t)M * N * 2); p.b_bytes = (unsigned)((size_t)N * K * 2);
     p.Mg = M; p.Ng = K; p.Kg = N;
-    return launch_bgemm<B_DGRAD>(p, out16, 1, pick_tile(M, K, 1), (hipStream_t)stream);
+    return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(M, K, 1), (hipStream_t)stream);
+}
+int ds6g_bf16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
+                           int mask16, int accumulate, void* stream) {
+    return h16_linear_dgrad<__bf16>(dy, w, dx, out16, M, N, K, mask_src, mask16, accumulate, stream);
+}
+int ds6g_f16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
+                          int mask16, int accumulate, void* stream) {
+    return h16_linear_dgrad<_Float16>(dy, w, dx, out16, M, N, K, mask_src, mask16, accumulate, stream);
 }
 
 // dw[N][K] (+)= dy[M][N]^T @ x[M][K] (fp32, the gradient arena); dbias[N] (+)= column sums of dy (nullable): x, dy bf16.
-int ds6g_bf16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
+extern "C++" template <typename T16>
+static int h16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
                            float* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && dy && dw && K % 8 == 0 && N % 8 == 0);
@@ -837,7 +896,15 @@ int ds6g_bf16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbia
     p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)x;
     p.a_bytes = (unsigned)((size_t)M * N * 2); p.b_bytes = (unsigned)((size_t)M * K * 2);
     p.Mg = N; p.Ng = K; p.Kg = M;
-    return run_wgrad(p, dw, accumulate, dbias, ws, ws_bytes, (hipStream_t)stream);
+    return run_wgrad<T16>(p, dw, accumulate, dbias, ws, ws_bytes, (hipStream_t)stream);
+}
+int ds6g_bf16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
+                           float* ws, size_t ws_bytes, void* stream) {
+    return h16_linear_wgrad<__bf16>(x, dy, dw, dbias, M, N, K, accumulate, ws, ws_bytes, stream);
+}
+int ds6g_f16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
+                          float* ws, size_t ws_bytes, void* stream) {
+    return h16_linear_wgrad<_Float16>(x, dy, dw, dbias, M, N, K, accumulate, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

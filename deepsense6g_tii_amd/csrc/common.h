@@ -94,10 +94,34 @@ __device__ __forceinline__ V vsub(V a, V b) {
 }
 #ifdef __HIPCC__
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+// vectors of a 16-bit storage type H (__bf16 or _Float16): the bf16- and f16-storage kernels are one template each
+template <typename H> struct H16 {
+    typedef H x4 __attribute__((ext_vector_type(4)));
+    typedef H x8 __attribute__((ext_vector_type(8)));
+};
+// v_mfma_f32_32x32x16_{bf16,f16}: same shape, same cycles; the overload picks the instruction of the storage type
+__device__ __forceinline__ f32x16 mfma_32x32x16(const bf16x8 a, const bf16x8 b, const f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma_32x32x16(const f16x8 a, const f16x8 b, const f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+// ds_read_b64_tr_b16 of a 16-bit LDS image (the transposed read does not depend on the element type)
+typedef __attribute__((address_space(3))) void lds16_void;
+__device__ __forceinline__ H16<__bf16>::x4 ds_read_tr16(const __bf16*, lds16_void* a) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) H16<__bf16>::x4*)a);
+}
+__device__ __forceinline__ f16x4 ds_read_tr16(const _Float16*, lds16_void* a) {
+    typedef __fp16 fp16x4_ __attribute__((ext_vector_type(4)));
+    return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4_*)a));
+}
 #endif
 
 // process-wide matrix-core mode (ds6g_set_compute_mode): 0 = exact fp32 MFMA, 1 = bf16 operands / fp32 accumulate,
-// 2 = split bf16 (hi*hi + hi*lo + lo*hi, fp32 accumulate), 3 = three-way split bf16 (six products, fp32-grade)
+// 2 = split bf16 (hi*hi + hi*lo + lo*hi, fp32 accumulate), 3 = three-way split bf16 (six products, fp32-grade).  Mode 5
+// (f16 storage) leaves this at 0: every fp32-storage kernel runs exactly as in mode 0.
 extern int g_ds6g_bf16;
 
 #ifdef __HIPCC__
@@ -122,9 +146,17 @@ __device__ __forceinline__ void st4(float* p, const f32x4 v) { *reinterpret_cast
 __device__ __forceinline__ void st4(__bf16* p, const f32x4 v) {
     *reinterpret_cast<bf16x4_t*>(p) = bf16x4_t{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
 }
+__device__ __forceinline__ f32x4 ld4(const _Float16* p) {
+    const f16x4 t = *reinterpret_cast<const f16x4*>(p);
+    return f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+}
+// round to nearest even; a value beyond the f16 range becomes +-inf (what the loss scaler looks for), never a clamp
+__device__ __forceinline__ void st4(_Float16* p, const f32x4 v) {
+    *reinterpret_cast<f16x4*>(p) = f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+}
 // gradient of a 3x3 / stride 2 / pad 1 max-pool gathered on the fly: row = (n*H + h)*W + w of the pool INPUT; the up to
 // four windows covering that pixel contribute where their stored argmax (r*3 + s, one byte per channel) points at it
-// (dp: fp32, or bf16 when dp16)
+// (dp: fp32, or bf16 when dp16 == 1, f16 when dp16 == 2)
 struct PoolGrad { const void* dp; const uint8_t* idx; int H, W, Ho, Wo; int dp16; };
 __device__ __forceinline__ f32x4 pooled_grad(const PoolGrad& pg, long row, int c4, int C) {
     const int w = (int)(row % pg.W);
@@ -140,7 +172,8 @@ __device__ __forceinline__ f32x4 pooled_grad(const PoolGrad& pg, long row, int c
             const int s = w - (ow * 2 - 1);
             const long o = ((n * pg.Ho + oh) * pg.Wo + ow) * C + c4;
             const uint32_t pk = *reinterpret_cast<const uint32_t*>(pg.idx + o);
-            const f32x4 g = pg.dp16 ? ld4(reinterpret_cast<const __bf16*>(pg.dp) + o) : ld4(reinterpret_cast<const float*>(pg.dp) + o);
+            const f32x4 g = pg.dp16 == 2 ? ld4(reinterpret_cast<const _Float16*>(pg.dp) + o)
+                            : pg.dp16 ? ld4(reinterpret_cast<const __bf16*>(pg.dp) + o) : ld4(reinterpret_cast<const float*>(pg.dp) + o);
             const uint32_t me = (uint32_t)(r * 3 + s);
 #pragma unroll
             for (int j = 0; j < 4; ++j)

@@ -231,8 +231,6 @@ int bn_geometry(long M, int C, int* rows_per_block, int* nblk) {
 // ------------------------------------ LayerNorm ----------------------------------------------
 // one wave per row; a lane owns columns 4*lane + 256*j + {0..3} (16-B accesses) when C >= 256, else the
 // scalar columns lane + 64*j.  C in {64,128,256,512}.
-typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
-
 template <int C>
 struct LnRow {
     static constexpr bool VEC = C >= 256;
@@ -261,12 +259,15 @@ struct LnRow {
         }
     }
     __device__ static int col(int e, int lane) { return VEC ? 4 * lane + 256 * (e >> 2) + (e & 3) : lane + 64 * e; }
-    // bf16 rows (the bf16-storage path: GEMM-facing tensors are bf16, the arithmetic here stays fp32), same column map
-    __device__ static void load(float* v, const __bf16* row, int lane) {
+    // 16-bit rows (the bf16- / f16-storage paths: GEMM-facing tensors are 16-bit, the arithmetic here stays fp32), same
+    // column map
+    template <typename T16>
+    __device__ static void load(float* v, const T16* row, int lane) {
+        typedef typename H16<T16>::x4 h4;
         if (VEC) {
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
-                const bf16x4_ t = *reinterpret_cast<const bf16x4_*>(row + 4 * lane + 256 * j);
+                const h4 t = *reinterpret_cast<const h4*>(row + 4 * lane + 256 * j);
                 v[4 * j] = (float)t[0]; v[4 * j + 1] = (float)t[1]; v[4 * j + 2] = (float)t[2]; v[4 * j + 3] = (float)t[3];
             }
         } else {
@@ -274,15 +275,17 @@ struct LnRow {
             for (int j = 0; j < NV; ++j) v[j] = (float)row[lane + 64 * j];
         }
     }
-    __device__ static void store(const float* v, __bf16* row, int lane) {
+    template <typename T16>
+    __device__ static void store(const float* v, T16* row, int lane) {
+        typedef typename H16<T16>::x4 h4;
         if (VEC) {
 #pragma unroll
             for (int j = 0; j < NV; ++j)
-                *reinterpret_cast<bf16x4_*>(row + 4 * lane + 256 * j) =
-                    bf16x4_{(__bf16)v[4 * j], (__bf16)v[4 * j + 1], (__bf16)v[4 * j + 2], (__bf16)v[4 * j + 3]};
+                *reinterpret_cast<h4*>(row + 4 * lane + 256 * j) =
+                    h4{(T16)v[4 * j], (T16)v[4 * j + 1], (T16)v[4 * j + 2], (T16)v[4 * j + 3]};
         } else {
 #pragma unroll
-            for (int j = 0; j < NV; ++j) row[lane + 64 * j] = (__bf16)v[j];
+            for (int j = 0; j < NV; ++j) row[lane + 64 * j] = (T16)v[j];
         }
     }
 };
@@ -587,11 +590,20 @@ int ds6g_bn_stats(const float* x, long M, int C, float eps, float momentum, floa
     return bn_stats_run<float>(x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
 }
 // bf16-storage path: the conv output is bf16; statistics, running stats and all arithmetic stay fp32
-int ds6g_bf16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd,
+extern "C++" template <typename T16>
+static int h16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd,
                        float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    return bn_stats_run<__bf16>((const __bf16*)x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
+    return bn_stats_run<T16>((const T16*)x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
                                 stream);
+}
+int ds6g_bf16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd, float* running_mean,
+                       float* running_var, void* ws, size_t ws_bytes, void* stream) {
+    return h16_bn_stats<__bf16>(x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
+}
+int ds6g_f16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd, float* running_mean,
+                      float* running_var, void* ws, size_t ws_bytes, void* stream) {
+    return h16_bn_stats<_Float16>(x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
 }
 
 int ds6g_bn_eval_prepare(const float* running_mean, const float* running_var, int C, float eps, float* mean,
@@ -609,11 +621,20 @@ int ds6g_bn_apply(const float* x, const float* mean, const float* invstd, const 
     DS6G_ENTER();
     return bn_apply_run<float>(x, mean, invstd, gamma, beta, residual, y, M, C, relu, stream);
 }
-int ds6g_bf16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+extern "C++" template <typename T16>
+static int h16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                        const void* residual, void* y, long M, int C, int relu, void* stream) {
     DS6G_ENTER();
-    return bn_apply_run<__bf16>((const __bf16*)x, mean, invstd, gamma, beta, (const __bf16*)residual, (__bf16*)y, M, C, relu,
+    return bn_apply_run<T16>((const T16*)x, mean, invstd, gamma, beta, (const T16*)residual, (T16*)y, M, C, relu,
                                 stream);
+}
+int ds6g_bf16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                       const void* residual, void* y, long M, int C, int relu, void* stream) {
+    return h16_bn_apply<__bf16>(x, mean, invstd, gamma, beta, residual, y, M, C, relu, stream);
+}
+int ds6g_f16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                      const void* residual, void* y, long M, int C, int relu, void* stream) {
+    return h16_bn_apply<_Float16>(x, mean, invstd, gamma, beta, residual, y, M, C, relu, stream);
 }
 
 int ds6g_bn_bwd(const float* dy, const float* y_mask, const float* x, const float* mean, const float* invstd,
@@ -626,15 +647,28 @@ int ds6g_bn_bwd(const float* dy, const float* y_mask, const float* x, const floa
                                     accumulate_param_grads, ws, ws_bytes, stream);
 }
 // bf16-storage path: dy / y_mask / x / dx / dres bf16 (dgamma / dbeta and the reductions fp32 / fp64)
-int ds6g_bf16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
+extern "C++" template <typename T16>
+static int h16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
                      const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres, long M,
                      int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(!(y_mask && relu_beta));
     DS6G_CHECK_ARG(dy && x && mean && invstd && gamma && dx && dgamma && dbeta && ws);
-    return bn_bwd_run<__bf16, __bf16>((const __bf16*)dy, PoolGrad{}, (const __bf16*)y_mask, (const __bf16*)x, mean, invstd,
-                                      gamma, relu_beta, (__bf16*)dx, dgamma, dbeta, (__bf16*)dres, M, C,
+    return bn_bwd_run<T16, T16>((const T16*)dy, PoolGrad{}, (const T16*)y_mask, (const T16*)x, mean, invstd,
+                                      gamma, relu_beta, (T16*)dx, dgamma, dbeta, (T16*)dres, M, C,
                                       accumulate_param_grads, ws, ws_bytes, stream);
+}
+int ds6g_bf16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
+                     const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres, long M,
+                     int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
+    return h16_bn_bwd<__bf16>(dy, y_mask, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, dres, M, C,
+                              accumulate_param_grads, ws, ws_bytes, stream);
+}
+int ds6g_f16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
+                    const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres, long M,
+                    int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
+    return h16_bn_bwd<_Float16>(dy, y_mask, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, dres, M, C,
+                                accumulate_param_grads, ws, ws_bytes, stream);
 }
 
 // BN -> ReLU -> 3x3/2 max-pool (the ResNet stem, model2_seq.py:495-500 via torchvision) backward in one pass over x: the
@@ -667,18 +701,40 @@ int ds6g_bn_bwd_maxpool_bf16in(const void* dpool, const uint8_t* idx, const floa
     return bn_bwd_maxpool_impl(dpool, 1, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
                                accumulate_param_grads, ws, ws_bytes, stream);
 }
+// the same with an f16 pool gradient (f16-storage path)
+int ds6g_bn_bwd_maxpool_f16in(const void* dpool, const uint8_t* idx, const float* x, const float* mean,
+                              const float* invstd, const float* gamma, const float* relu_beta, float* dx, float* dgamma,
+                              float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
+                              size_t ws_bytes, void* stream) {
+    DS6G_ENTER();
+    return bn_bwd_maxpool_impl(dpool, 2, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
+                               accumulate_param_grads, ws, ws_bytes, stream);
+}
 
 // bf16 stem (csrc/stem.hip): conv output x and its gradient dx are bf16 too
-int ds6g_bf16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean,
+extern "C++" template <typename T16>
+static int h16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean,
                                   const float* invstd, const float* gamma, const float* relu_beta, void* dx, float* dgamma,
                                   float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
                                   size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(dpool && idx && x && mean && invstd && gamma && relu_beta && dx && dgamma && dbeta && ws);
     DS6G_CHECK_ARG(N > 0 && H > 0 && W > 0 && C % 4 == 0);
-    const PoolGrad pg{dpool, idx, H, W, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1, 1};
-    return bn_bwd_run<__bf16, __bf16>(nullptr, pg, nullptr, (const __bf16*)x, mean, invstd, gamma, relu_beta, (__bf16*)dx,
+    const PoolGrad pg{dpool, idx, H, W, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1, __is_same(T16, _Float16) ? 2 : 1};
+    return bn_bwd_run<T16, T16>(nullptr, pg, nullptr, (const T16*)x, mean, invstd, gamma, relu_beta, (T16*)dx,
                                       dgamma, dbeta, nullptr, (long)N * H * W, C, accumulate_param_grads, ws, ws_bytes, stream);
+}
+int ds6g_bf16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean, const float* invstd,
+                                  const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, int N,
+                                  int H, int W, int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
+    return h16_stem_bn_bwd_maxpool<__bf16>(dpool, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
+                                           accumulate_param_grads, ws, ws_bytes, stream);
+}
+int ds6g_f16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean, const float* invstd,
+                                 const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, int N,
+                                 int H, int W, int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
+    return h16_stem_bn_bwd_maxpool<_Float16>(dpool, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
+                                             accumulate_param_grads, ws, ws_bytes, stream);
 }
 
 int ds6g_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
@@ -690,12 +746,21 @@ int ds6g_layernorm_fwd(const float* x, const float* gamma, const float* beta, fl
 }
 
 // bf16-storage path: the normalised rows feed a GEMM and are written as bf16 (statistics and arithmetic fp32)
-int ds6g_layernorm_fwd_bf16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+extern "C++" template <typename T16>
+static int layernorm_fwd_h16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                int M, int C, float eps, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && gamma && beta && y && mean && rstd && M > 0);
     DS6G_CHECK_ARG(C % 64 == 0 && C <= 512);
-    return ln_fwd_launch<__bf16>(x, gamma, beta, (__bf16*)y, mean, rstd, M, C, eps, (hipStream_t)stream);
+    return ln_fwd_launch<T16>(x, gamma, beta, (T16*)y, mean, rstd, M, C, eps, (hipStream_t)stream);
+}
+int ds6g_layernorm_fwd_bf16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M,
+                               int C, float eps, void* stream) {
+    return layernorm_fwd_h16out<__bf16>(x, gamma, beta, y, mean, rstd, M, C, eps, stream);
+}
+int ds6g_layernorm_fwd_f16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M,
+                              int C, float eps, void* stream) {
+    return layernorm_fwd_h16out<_Float16>(x, gamma, beta, y, mean, rstd, M, C, eps, stream);
 }
 
 size_t ds6g_layernorm_bwd_workspace_bytes(int M, int C) { return (size_t)cdiv(M, LN_BWD_ROWS) * 2 * C * sizeof(float); }
@@ -712,18 +777,33 @@ int ds6g_layernorm_bwd(const float* dy, const float* x, const float* mean, const
 
 // bf16-storage path: dy is a GEMM output stored as bf16 (dy16) or fp32; dx (the residual-stream gradient) stays fp32;
 // dx_drop (nullable) = dropout(dx) is the next GEMM's operand and is written as bf16 (with drop_p = 0: a bf16 copy of dx)
-int ds6g_layernorm_bwd_bf16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
+extern "C++" template <typename T16>
+static int layernorm_bwd_h16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
                             const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
                             int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off,
                             void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     if (dy16)
-        return ln_bwd_launch<__bf16, __bf16>((const __bf16*)dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C,
-                                             accumulate_param_grads, (__bf16*)dx_drop, drop_p, seed, seed_off, ws, ws_bytes,
+        return ln_bwd_launch<T16, T16>((const T16*)dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C,
+                                             accumulate_param_grads, (T16*)dx_drop, drop_p, seed, seed_off, ws, ws_bytes,
                                              (hipStream_t)stream);
-    return ln_bwd_launch<float, __bf16>((const float*)dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C,
-                                        accumulate_param_grads, (__bf16*)dx_drop, drop_p, seed, seed_off, ws, ws_bytes,
+    return ln_bwd_launch<float, T16>((const float*)dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C,
+                                        accumulate_param_grads, (T16*)dx_drop, drop_p, seed, seed_off, ws, ws_bytes,
                                         (hipStream_t)stream);
+}
+int ds6g_layernorm_bwd_bf16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd, const float* gamma,
+                            const float* add, float* dx, float* dgamma, float* dbeta, int M, int C, int accumulate_param_grads,
+                            void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
+                            void* stream) {
+    return layernorm_bwd_h16<__bf16>(dy, dy16, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C, accumulate_param_grads,
+                                     dx_drop, drop_p, seed, seed_off, ws, ws_bytes, stream);
+}
+int ds6g_layernorm_bwd_f16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd, const float* gamma,
+                           const float* add, float* dx, float* dgamma, float* dbeta, int M, int C, int accumulate_param_grads,
+                           void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
+                           void* stream) {
+    return layernorm_bwd_h16<_Float16>(dy, dy16, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C, accumulate_param_grads,
+                                       dx_drop, drop_p, seed, seed_off, ws, ws_bytes, stream);
 }
 
 constexpr int COLSUM_ROWS = 32;

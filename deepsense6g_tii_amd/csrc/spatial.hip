@@ -439,15 +439,24 @@ int ds6g_pack_input(const float* src, float* dst, int B, int Cs, int H, int W, i
 }
 
 // the same with a bf16 destination [B * frames][H][W][4] (the bf16 stem's input: csrc/stem.hip)
-int ds6g_pack_input_bf16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
+extern "C++" template <typename T16>
+static int pack_input_h16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
                          int normalize_imagenet, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(src && dst && Cs >= 1 && Cs <= 4 && t >= 0 && t < frames_per_sample);
     DS6G_CHECK_ARG(!normalize_imagenet || Cs == 3);
-    hipLaunchKernelGGL(pack_input_kernel<__bf16>, dim3(grid1((long)B * H * W)), dim3(256), 0, (hipStream_t)stream, src,
-                       (__bf16*)dst, B, Cs, H * W, 4, frames_per_sample, t, normalize_imagenet);
+    hipLaunchKernelGGL(pack_input_kernel<T16>, dim3(grid1((long)B * H * W)), dim3(256), 0, (hipStream_t)stream, src,
+                       (T16*)dst, B, Cs, H * W, 4, frames_per_sample, t, normalize_imagenet);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
+}
+int ds6g_pack_input_bf16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
+                         int normalize_imagenet, void* stream) {
+    return pack_input_h16<__bf16>(src, dst, B, Cs, H, W, frames_per_sample, t, normalize_imagenet, stream);
+}
+int ds6g_pack_input_f16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
+                        int normalize_imagenet, void* stream) {
+    return pack_input_h16<_Float16>(src, dst, B, Cs, H, W, frames_per_sample, t, normalize_imagenet, stream);
 }
 
 int ds6g_pad_channels(const float* src, float* dst, long rows, int cin, int cout, int unpad, int accumulate,
@@ -627,88 +636,160 @@ int ds6g_batch_sum(const float* src, float* out, long n, int count, long stride,
 }
 
 // ---- bf16-storage path: the same kernels on bf16 feature maps (tokens, pos_emb, pooled vectors and all arithmetic fp32) ----
-int ds6g_bn_relu_maxpool3x3s2_fwd_bf16out(const float* x, const float* mean, const float* invstd, const float* gamma,
+extern "C++" template <typename T16>
+static int bn_relu_maxpool3x3s2_fwd_h16out(const float* x, const float* mean, const float* invstd, const float* gamma,
                                           const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C,
                                           void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && mean && invstd && gamma && beta && y && idx && C % 4 == 0 && N > 0 && H > 0 && W > 0);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL((maxpool_fwd_kernel<__bf16>), dim3(grid1((long)N * Ho * Wo * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, x, (__bf16*)y, idx, N, H, W, C, Ho, Wo, mean, invstd, gamma, beta);
+    hipLaunchKernelGGL((maxpool_fwd_kernel<T16>), dim3(grid1((long)N * Ho * Wo * (C / 4))), dim3(256), 0,
+                       (hipStream_t)stream, x, (T16*)y, idx, N, H, W, C, Ho, Wo, mean, invstd, gamma, beta);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_bn_relu_maxpool3x3s2_fwd_bf16out(const float* x, const float* mean, const float* invstd, const float* gamma,
+                                          const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
+    return bn_relu_maxpool3x3s2_fwd_h16out<__bf16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
+}
+int ds6g_bn_relu_maxpool3x3s2_fwd_f16out(const float* x, const float* mean, const float* invstd, const float* gamma,
+                                         const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
+    return bn_relu_maxpool3x3s2_fwd_h16out<_Float16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
+}
 
 // bf16 stem (csrc/stem.hip): the conv output x is bf16 as well
-int ds6g_bf16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
+extern "C++" template <typename T16>
+static int h16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
                                        const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && mean && invstd && gamma && beta && y && idx && C % 4 == 0 && N > 0 && H > 0 && W > 0);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL((maxpool_fwd_kernel<__bf16, __bf16>), dim3(grid1((long)N * Ho * Wo * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, (const __bf16*)x, (__bf16*)y, idx, N, H, W, C, Ho, Wo, mean, invstd, gamma, beta);
+    hipLaunchKernelGGL((maxpool_fwd_kernel<T16, T16>), dim3(grid1((long)N * Ho * Wo * (C / 4))), dim3(256), 0,
+                       (hipStream_t)stream, (const T16*)x, (T16*)y, idx, N, H, W, C, Ho, Wo, mean, invstd, gamma, beta);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_bf16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
+                                       const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
+    return h16_stem_bn_relu_maxpool_fwd<__bf16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
+}
+int ds6g_f16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
+                                      const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
+    return h16_stem_bn_relu_maxpool_fwd<_Float16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
+}
 
-int ds6g_bf16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
+extern "C++" template <typename T16>
+static int h16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
                                  int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed,
                                  uint64_t seed_off, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(feat && pos_emb && tokens && C % 4 == 0 && H % 8 == 0 && N % frames_per_sample == 0);
-    hipLaunchKernelGGL((avgpool_tokens_fwd_kernel<__bf16>), dim3(grid1((long)N * 64 * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, (const __bf16*)feat, pos_emb, tokens, N, H, C, frames_per_sample, mod_off, T,
+    hipLaunchKernelGGL((avgpool_tokens_fwd_kernel<T16>), dim3(grid1((long)N * 64 * (C / 4))), dim3(256), 0,
+                       (hipStream_t)stream, (const T16*)feat, pos_emb, tokens, N, H, C, frames_per_sample, mod_off, T,
                        ds6g_drop_threshold(drop_p), 1.f / (1.f - drop_p), seed, seed_off, g_ds6g_salt);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_bf16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
+                                 int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed, uint64_t seed_off,
+                                 void* stream) {
+    return h16_avgpool_tokens_fwd<__bf16>(feat, pos_emb, tokens, N, H, C, frames_per_sample, mod_off, T, drop_p, seed, seed_off,
+                                          stream);
+}
+int ds6g_f16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
+                                int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed, uint64_t seed_off,
+                                void* stream) {
+    return h16_avgpool_tokens_fwd<_Float16>(feat, pos_emb, tokens, N, H, C, frames_per_sample, mod_off, T, drop_p, seed,
+                                            seed_off, stream);
+}
 
-int ds6g_bf16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
+extern "C++" template <typename T16>
+static int h16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
                                  int frames_per_sample, int mod_off, int T, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(dtok && dfeat && C % 4 == 0 && H % 8 == 0);
-    hipLaunchKernelGGL((avgpool_tokens_bwd_kernel<__bf16>), dim3(grid1((long)N * H * H * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, dtok, (const __bf16*)dfeat_in, (__bf16*)dfeat, N, H, C, frames_per_sample, mod_off, T);
+    hipLaunchKernelGGL((avgpool_tokens_bwd_kernel<T16>), dim3(grid1((long)N * H * H * (C / 4))), dim3(256), 0,
+                       (hipStream_t)stream, dtok, (const T16*)dfeat_in, (T16*)dfeat, N, H, C, frames_per_sample, mod_off, T);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_bf16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
+                                 int frames_per_sample, int mod_off, int T, void* stream) {
+    return h16_avgpool_tokens_bwd<__bf16>(dtok, dfeat_in, dfeat, N, H, C, frames_per_sample, mod_off, T, stream);
+}
+int ds6g_f16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
+                                int frames_per_sample, int mod_off, int T, void* stream) {
+    return h16_avgpool_tokens_bwd<_Float16>(dtok, dfeat_in, dfeat, N, H, C, frames_per_sample, mod_off, T, stream);
+}
 
-int ds6g_bf16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C,
+extern "C++" template <typename T16>
+static int h16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C,
                                int frames_per_sample, int mod_off, int T, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(feat && tokens && out && C % 4 == 0 && H % 8 == 0);
-    hipLaunchKernelGGL((upsample_add_fwd_kernel<__bf16>), dim3(grid1((long)N * H * H * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, (const __bf16*)feat, tokens, (__bf16*)out, N, H, C, frames_per_sample, mod_off, T);
+    hipLaunchKernelGGL((upsample_add_fwd_kernel<T16>), dim3(grid1((long)N * H * H * (C / 4))), dim3(256), 0,
+                       (hipStream_t)stream, (const T16*)feat, tokens, (T16*)out, N, H, C, frames_per_sample, mod_off, T);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_bf16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C, int frames_per_sample,
+                               int mod_off, int T, void* stream) {
+    return h16_upsample_add_fwd<__bf16>(feat, tokens, out, N, H, C, frames_per_sample, mod_off, T, stream);
+}
+int ds6g_f16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C, int frames_per_sample,
+                              int mod_off, int T, void* stream) {
+    return h16_upsample_add_fwd<_Float16>(feat, tokens, out, N, H, C, frames_per_sample, mod_off, T, stream);
+}
 
-int ds6g_bf16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
+extern "C++" template <typename T16>
+static int h16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
                                int T, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(dout && dtok && C % 4 == 0 && H % 8 == 0 && 5 * (H / 8) <= UPB_MAXWIN && N > 0);
-    hipLaunchKernelGGL((upsample_add_bwd_kernel<__bf16>), dim3(N * 64), dim3(256), 0, (hipStream_t)stream,
-                       (const __bf16*)dout, dtok, N, H, C, frames_per_sample, mod_off, T);
+    hipLaunchKernelGGL((upsample_add_bwd_kernel<T16>), dim3(N * 64), dim3(256), 0, (hipStream_t)stream,
+                       (const T16*)dout, dtok, N, H, C, frames_per_sample, mod_off, T);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_bf16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off, int T,
+                               void* stream) {
+    return h16_upsample_add_bwd<__bf16>(dout, dtok, N, H, C, frames_per_sample, mod_off, T, stream);
+}
+int ds6g_f16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off, int T,
+                              void* stream) {
+    return h16_upsample_add_bwd<_Float16>(dout, dtok, N, H, C, frames_per_sample, mod_off, T, stream);
+}
 
-int ds6g_bf16_global_pool(const void* feat, float* pooled, int N, int C, void* stream) {
+extern "C++" template <typename T16>
+static int h16_global_pool(const void* feat, float* pooled, int N, int C, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(feat && pooled && C % 4 == 0);
-    hipLaunchKernelGGL((global_pool_kernel<__bf16>), dim3(grid1((long)N * (C / 4))), dim3(256), 0, (hipStream_t)stream,
-                       (const __bf16*)feat, pooled, N, C);
+    hipLaunchKernelGGL((global_pool_kernel<T16>), dim3(grid1((long)N * (C / 4))), dim3(256), 0, (hipStream_t)stream,
+                       (const T16*)feat, pooled, N, C);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_bf16_global_pool(const void* feat, float* pooled, int N, int C, void* stream) {
+    return h16_global_pool<__bf16>(feat, pooled, N, C, stream);
+}
+int ds6g_f16_global_pool(const void* feat, float* pooled, int N, int C, void* stream) {
+    return h16_global_pool<_Float16>(feat, pooled, N, C, stream);
+}
 
-int ds6g_bf16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream) {
+extern "C++" template <typename T16>
+static int h16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(dfused && dfeat && C % 4 == 0);
-    hipLaunchKernelGGL((head_bwd_kernel<__bf16>), dim3(grid1((long)N * 64 * (C / 4))), dim3(256), 0, (hipStream_t)stream,
-                       dfused, (__bf16*)dfeat, N, C, frames_per_sample);
+    hipLaunchKernelGGL((head_bwd_kernel<T16>), dim3(grid1((long)N * 64 * (C / 4))), dim3(256), 0, (hipStream_t)stream,
+                       dfused, (T16*)dfeat, N, C, frames_per_sample);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
+}
+int ds6g_bf16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream) {
+    return h16_head_bwd<__bf16>(dfused, dfeat, N, C, frames_per_sample, stream);
+}
+int ds6g_f16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream) {
+    return h16_head_bwd<_Float16>(dfused, dfeat, N, C, frames_per_sample, stream);
 }
 
 }  // extern "C"

@@ -37,16 +37,17 @@ constexpr int WROW = 7 * 8 * 4;             // padded filter row: [r 7][s' 8][c 
 __device__ __forceinline__ unsigned lds_off(const void* p) { return (unsigned)(unsigned long)(lds_void*)p; }
 
 // fp32 master filter [64][7][7][cin] (OHWI, the arena layout) -> bf16 [64][7][8][4]: tap s' = s + 1, tap 0 and channels >= cin zero
-__global__ __launch_bounds__(256) void stem_pack_weights_kernel(const float* __restrict__ w, __bf16* __restrict__ w16, int cin) {
+template <typename T16>
+__global__ __launch_bounds__(256) void stem_pack_weights_kernel(const float* __restrict__ w, T16* __restrict__ w16, int cin) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= KO * WROW) return;
     const int c = i & 3, sp = (i >> 2) & 7, r = (i >> 5) % 7, o = i / WROW;
     float v = 0.f;
     if (sp >= 1 && c < cin) v = w[((o * 7 + r) * 7 + (sp - 1)) * cin + c];
-    w16[i] = (__bf16)v;
+    w16[i] = (T16)v;
 }
 
-struct StemParams {
+struct StemParams {   // 16-bit tensors: __bf16 or _Float16 storage (the kernels' template argument)
     const __bf16* x;      // [N][H][W][4]
     const __bf16* w16;    // [64][7][8][4]
     __bf16* y;            // [N][Ho][Wo][64]      (forward)
@@ -90,9 +91,11 @@ __device__ __forceinline__ void tile_coords(const StemParams& p, int t, int& n, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+template <typename T16>
 __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
+    typedef typename H16<T16>::x8 h8;
     __shared__ __attribute__((aligned(1024))) unsigned char patch[2][PATCH_BYTES];
-    __shared__ __attribute__((aligned(16))) __bf16 outp[4][32 * KO];     // wave-private output patches [32 px][64 ch]
+    __shared__ __attribute__((aligned(16))) T16 outp[4][32 * KO];     // wave-private output patches [32 px][64 ch]
     __shared__ float red[4][2][KO];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, khalf = lane >> 5;
@@ -100,14 +103,14 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
     const PatchLane pl(tid);
 
     // the wave's 28 weight fragments: output channel nt * 32 + l31, k-step (r, jj): taps s' = 4 jj + 2 khalf, +1 (x 4 channels)
-    bf16x8 bw[7][2][2];
+    h8 bw[7][2][2];
 #pragma unroll
     for (int r = 0; r < 7; ++r)
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
-                bw[r][jj][nt] = *reinterpret_cast<const bf16x8*>(p.w16 + (nt * 32 + l31) * WROW + (r * 8 + 4 * jj + 2 * khalf) * 4);
+                bw[r][jj][nt] = *reinterpret_cast<const h8*>(p.w16 + (nt * 32 + l31) * WROW + (r * 8 + 4 * jj + 2 * khalf) * 4);
 
     // this lane's pixel of the wave's 32-pixel M tile (output rows 2 wave, 2 wave + 1 of the tile): piece (2 oy, ox) of the patch
     const int oy_rel = 2 * wave + (l31 >> 4), ox = l31 & 15;
@@ -141,18 +144,18 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
         for (int r = 0; r < 7; ++r)
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8*>(P + a_base + (unsigned)((r * PP + 2 * jj) * 16));
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bw[r][jj][0], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bw[r][jj][1], acc[1], 0, 0, 0);
+                const h8 a = *reinterpret_cast<const h8*>(P + a_base + (unsigned)((r * PP + 2 * jj) * 16));
+                acc[0] = mfma_32x32x16(a, bw[r][jj][0], acc[0]);
+                acc[1] = mfma_32x32x16(a, bw[r][jj][1], acc[1]);
             }
         // D[pixel][channel]: channel = nt * 32 + l31, pixel = (reg & 3) + 8 (reg >> 2) + 4 khalf of the wave's 32
-        __bf16* op = outp[wave];
+        T16* op = outp[wave];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int px = (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                const __bf16 vb = (__bf16)acc[nt][r];
+                const T16 vb = (T16)acc[nt][r];
                 op[px * KO + nt * 32 + l31] = vb;
                 const float vr = (float)vb;
                 cs[nt] += vr;
@@ -163,9 +166,9 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int idx = it * 64 + lane, px = idx >> 3, pc = idx & 7;
-            const bf16x8 v = *reinterpret_cast<const bf16x8*>(op + px * KO + pc * 8);
+            const h8 v = *reinterpret_cast<const h8*>(op + px * KO + pc * 8);
             const size_t o = (((size_t)n * p.Ho + oy0 + (px >> 4)) * p.Wo + ox0 + (px & 15)) * KO + pc * 8;
-            *reinterpret_cast<bf16x8*>(p.y + o) = v;
+            *reinterpret_cast<h8*>(p.y + o) = v;
         }
         buf ^= 1;
     }
@@ -189,7 +192,10 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // weight gradient: per workgroup tile, A = dy^T (64 channels x 128 pixels), B = patch im2col (128 pixels x 7 x 32)
+template <typename T16>
 __global__ __launch_bounds__(256, 2) void stem_wgrad_kernel(const StemParams p) {
+    typedef typename H16<T16>::x4 h4;
+    typedef typename H16<T16>::x8 h8;
     __shared__ __attribute__((aligned(1024))) unsigned char patch[2][PATCH_BYTES];
     __shared__ __attribute__((aligned(1024))) unsigned char dyt[2][TH * TW * KO * 2];   // [128 px][64 ch] bf16, 128-B rows
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -256,16 +262,16 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_kernel(const StemParams p) 
         const unsigned char* D = dyt[buf];
 #pragma unroll
         for (int s = 0; s < TH; ++s) {     // k-step s = output row s of the tile (16 pixels)
-            const bf16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(lds_void*)(D + a_addr(s, 0)));
-            const bf16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(lds_void*)(D + a_addr(s, 1)));
-            const bf16x8 a = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7);
+            const h4 alo = ds_read_tr16((const T16*)nullptr, (lds_void*)(D + a_addr(s, 0)));
+            const h4 ahi = ds_read_tr16((const T16*)nullptr, (lds_void*)(D + a_addr(s, 1)));
+            const h8 a = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (j < nr) {
-                    const bf16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(lds_void*)(P + b_addr(s, 0, r0 + j)));
-                    const bf16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(lds_void*)(P + b_addr(s, 1, r0 + j)));
-                    const bf16x8 b = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
+                    const h4 blo = ds_read_tr16((const T16*)nullptr, (lds_void*)(P + b_addr(s, 0, r0 + j)));
+                    const h4 bhi = ds_read_tr16((const T16*)nullptr, (lds_void*)(P + b_addr(s, 1, r0 + j)));
+                    const h8 b = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    acc[j] = mfma_32x32x16(a, b, acc[j]);
                 }
             }
         }
@@ -326,34 +332,49 @@ size_t ds6g_bf16_stem_workspace_bytes(void) {
     const size_t wg = (size_t)STEM_GRID_WGRAD * KO * 7 * 32 * sizeof(float);
     return fwd > wg ? fwd : wg;
 }
+size_t ds6g_f16_stem_workspace_bytes(void) { return ds6g_bf16_stem_workspace_bytes(); }
 
 // y = conv7x7/2(x, w) on bf16 storage + the train-mode BatchNorm statistics of y.  x [N][H][W][4] bf16 (channels >= cin
 // zero), w: the fp32 master filter [64][7][7][cin] (OHWI), y [N][H/2][W/2][64] bf16; H % 16 == 0, W % 32 == 0.
 // mean == NULL: convolution only (eval mode: the caller applies running statistics).
-int ds6g_bf16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
+extern "C++" template <typename T16>
+static int h16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
                        float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
                        void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && w && y && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_bf16_stem_workspace_bytes());
     StemParams p{};
     DS6G_CHECK_ARG(stem_geometry(p, N, H, W) == DS6G_OK);
-    __bf16* w16 = (__bf16*)ws;
-    p.x = (const __bf16*)x; p.w16 = w16; p.y = (__bf16*)y;
+    T16* w16 = (T16*)ws;
+    p.x = (const __bf16*)x; p.w16 = (const __bf16*)w16; p.y = (__bf16*)y;
     p.bn_partial = (double*)((char*)ws + (((size_t)KO * WROW * 2 + 1023) & ~(size_t)1023));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(stem_pack_weights_kernel, dim3(cdiv(KO * WROW, 256)), dim3(256), 0, st, w, w16, cin);
+    hipLaunchKernelGGL(stem_pack_weights_kernel<T16>, dim3(cdiv(KO * WROW, 256)), dim3(256), 0, st, w, w16, cin);
     DS6G_LAUNCH_CHECK();
     const int grid = p.ntiles < STEM_GRID_FWD ? p.ntiles : STEM_GRID_FWD;
-    hipLaunchKernelGGL(stem_fwd_kernel, dim3(grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(stem_fwd_kernel<T16>, dim3(grid), dim3(256), 0, st, p);
     DS6G_LAUNCH_CHECK();
     if (!mean) return DS6G_OK;
     DS6G_CHECK_ARG(invstd);
     return ds6g_internal_bn_stats_finalize(p.bn_partial, grid, (long)N * p.Ho * p.Wo, KO, eps, momentum, mean, invstd,
                                            running_mean, running_var, st);
 }
+int ds6g_bf16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
+                       float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
+                       void* stream) {
+    return h16_stem_fwd<__bf16>(x, w, cin, y, N, H, W, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
+                                stream);
+}
+int ds6g_f16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
+                      float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
+                      void* stream) {
+    return h16_stem_fwd<_Float16>(x, w, cin, y, N, H, W, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
+                                  stream);
+}
 
 // dw[64][7][7][cin] (+)= weight gradient of the same convolution from x [N][H][W][4] bf16 and dy [N][H/2][W/2][64] bf16
-int ds6g_bf16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
+extern "C++" template <typename T16>
+static int h16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
                          size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && dy && dw && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_bf16_stem_workspace_bytes());
@@ -362,11 +383,19 @@ int ds6g_bf16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int 
     p.x = (const __bf16*)x; p.dy = (const __bf16*)dy; p.slabs = (float*)ws;
     hipStream_t st = (hipStream_t)stream;
     const int grid = p.ntiles < STEM_GRID_WGRAD ? p.ntiles : STEM_GRID_WGRAD;
-    hipLaunchKernelGGL(stem_wgrad_kernel, dim3(grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(stem_wgrad_kernel<T16>, dim3(grid), dim3(256), 0, st, p);
     DS6G_LAUNCH_CHECK();
     hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3(KO * 7), dim3(256), 0, st, (const float*)ws, grid, dw, cin, accumulate);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
+}
+int ds6g_bf16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
+                         size_t ws_bytes, void* stream) {
+    return h16_stem_wgrad<__bf16>(x, dy, dw, cin, N, H, W, accumulate, ws, ws_bytes, stream);
+}
+int ds6g_f16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
+                        size_t ws_bytes, void* stream) {
+    return h16_stem_wgrad<_Float16>(x, dy, dw, cin, N, H, W, accumulate, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

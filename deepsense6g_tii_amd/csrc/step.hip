@@ -11,11 +11,15 @@ thread_local const uint64_t* g_ds6g_salt = nullptr;
 
 namespace {
 
-// loss = mean_i ce_i (1-p_t)^gamma (alpha t + (1-alpha)(1-t));  dlogits_i = dloss/dx_i * upstream
+// loss = mean_i ce_i (1-p_t)^gamma (alpha t + (1-alpha)(1-t));  dlogits_i = dloss/dx_i * upstream (DEV: * *upstream_dev,
+// the dynamic loss scale read at run time; the reported loss is never scaled)
+template <bool DEV>
 __global__ __launch_bounds__(256) void focal_kernel(const float* __restrict__ x, const float* __restrict__ t,
                                                     float* __restrict__ loss, float* __restrict__ dx, int n,
-                                                    float alpha, float gamma, float upstream) {
+                                                    float alpha, float gamma, float upstream,
+                                                    const float* __restrict__ upstream_dev) {
     __shared__ float red[4];
+    if (DEV) upstream *= *upstream_dev;
     float acc = 0.f;
     const float inv_n = 1.0f / (float)n;
     for (int i = threadIdx.x; i < n; i += 256) {
@@ -59,6 +63,95 @@ __global__ void adamw_advance_kernel(AdamDev* st, float beta1, float beta2) {
     st->bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
 }
 
+// Dynamic loss scaling (train.DynamicLossScaler): a 32-byte device block, every field read and written on the device only
+struct LossScaleDev {
+    float scale;      // S: the focal loss's upstream factor
+    int clean;        // finite steps since the last growth / backoff
+    int found_inf;    // the last check saw a non-finite gradient: the AdamW step is skipped
+    float coef;       // AdamW gradient coefficient: clip(unscaled norm) / S
+    float norm;       // unscaled total gradient norm of the last check (pre_scale applied)
+    float pad[3];
+};
+
+// check: sum of squares (double, per-block partials, last block adds them in index order - grad_norm_kernel's scheme) and
+// a per-block non-finite flag over the gradient arena; the last block writes found_inf, the unscaled norm and the AdamW
+// coefficient 1/S (times the clip coefficient of the unscaled norm when max_norm > 0).  ws: [0] counter (zero on entry,
+// re-zeroed on exit), double partials from byte 8, then one unsigned flag per block.
+__global__ __launch_bounds__(256) void loss_scale_check_kernel(const float* __restrict__ g, long n4, float max_norm,
+                                                               float pre_scale, LossScaleDev* __restrict__ st,
+                                                               unsigned* __restrict__ counter, double* __restrict__ partial,
+                                                               unsigned* __restrict__ flags) {
+    __shared__ double red[4];
+    __shared__ unsigned bad[4];
+    __shared__ bool last;
+    double acc = 0.0;
+    unsigned nonfinite = 0u;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(g + i * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nonfinite |= (unsigned)!__builtin_isfinite(v[j]);
+        acc += (double)(v[0] * v[0] + v[1] * v[1]) + (double)(v[2] * v[2] + v[3] * v[3]);
+    }
+    acc = wave_reduce_sum_d(acc);
+    const unsigned wbad = __ballot(nonfinite != 0u) != 0ull ? 1u : 0u;
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = acc; bad[threadIdx.x >> 6] = wbad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        flags[blockIdx.x] = bad[0] | bad[1] | bad[2] | bad[3];
+        __threadfence();
+        last = atomicAdd(counter, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    double tot = 0.0;
+    unsigned any = 0u;
+    for (unsigned i = threadIdx.x; i < gridDim.x; i += 256) {
+        tot += __builtin_nontemporal_load(partial + i);
+        any |= __builtin_nontemporal_load(flags + i);
+    }
+    tot = wave_reduce_sum_d(tot);
+    const unsigned wany = __ballot(any != 0u) != 0ull ? 1u : 0u;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = tot; bad[threadIdx.x >> 6] = wany; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned found = bad[0] | bad[1] | bad[2] | bad[3];
+        const float inv_s = 1.f / st->scale;
+        const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3])) * pre_scale * inv_s;
+        float coef = inv_s;
+        if (max_norm > 0.f) {
+            const float c = max_norm / (norm + 1e-6f);
+            coef *= c < 1.f ? c : 1.f;
+        }
+        st->found_inf = (int)found;
+        st->norm = found ? __builtin_inff() : norm;
+        st->coef = found ? 0.f : coef;
+        *counter = 0u;
+    }
+}
+
+// update (one thread, after the check, before the AdamW step): on a non-finite gradient the scale backs off and the AdamW
+// step count / bias corrections stay; otherwise they advance as adamw_advance_kernel does and every growth_interval clean
+// steps the scale grows
+__global__ void loss_scale_update_kernel(LossScaleDev* st, AdamDev* ad, float beta1, float beta2, float backoff, float growth,
+                                         int growth_interval) {
+    if (st->found_inf) {
+        st->scale *= backoff;
+        st->clean = 0;
+        return;
+    }
+    const int step = ad->step + 1;
+    ad->step = step;
+    ad->bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    ad->bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    if (++st->clean >= growth_interval) {
+        st->scale *= growth;
+        st->clean = 0;
+    }
+}
+
 // sum of squares of n4*4 floats: per-block double partials, the LAST block to finish (device-scope counter) adds them in
 // index order (deterministic) and writes out[0] = ||g||_2, out[1] = min(1, max_norm / (||g||_2 + 1e-6)) - the
 // clip coefficient of torch.nn.utils.clip_grad_norm_ (train2_seq_30to5.py:120), applied by adamw_kernel through
@@ -100,11 +193,24 @@ __global__ __launch_bounds__(256) void grad_norm_kernel(const float* __restrict_
     }
 }
 
+// SKIP: the loss scaler's found_inf decides at run time; a skipped step leaves p, m, v untouched and still moves the EMA
+// shadow towards the unchanged p (scaler.step(opt); ema.update() of torch.amp.GradScaler, train2_seq.py:127-134)
+template <bool SKIP>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     float* __restrict__ shadow, long n4, AdamArgs a,
                                                     const float* __restrict__ grad_scale_dev,
-                                                    const AdamDev* __restrict__ dev) {
+                                                    const AdamDev* __restrict__ dev, const int* __restrict__ skip_dev) {
+    if (SKIP && *skip_dev) {
+        if (!shadow) return;
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+            const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i * 4);
+            f32x4 sv = *reinterpret_cast<f32x4*>(shadow + i * 4);
+            sv = (1.f - a.ema_decay) * pv + a.ema_decay * sv;
+            *reinterpret_cast<f32x4*>(shadow + i * 4) = sv;
+        }
+        return;
+    }
     if (grad_scale_dev) a.grad_scale *= *grad_scale_dev;
     if (dev) { a.lr = dev->lr; a.bc1 = dev->bc1; a.bc2_sqrt = dev->bc2_sqrt; }
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -131,8 +237,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
-// dst[i] = bf16(src[i]) (RNE): the bf16 shadow of the parameter arena, refreshed once per training forward of the
-// bf16-storage path (fp32 master weights stay in the arena)
+// dst[i] = bf16(src[i]) / f16(src[i]) (RNE): the 16-bit shadow of the parameter arena, refreshed once per training forward
+// of the 16-bit storage paths (fp32 master weights stay in the arena); an f16 value beyond 65504 becomes inf
 // resident for `ticks` of the 100 MHz real-time counter (ds6g_debug_occupy_cus); touches its dynamic LDS so the allocation is real
 __global__ __launch_bounds__(256) void occupy_kernel(unsigned long long ticks) {
     extern __shared__ unsigned char occ_lds[];
@@ -141,11 +247,12 @@ __global__ __launch_bounds__(256) void occupy_kernel(unsigned long long ticks) {
     while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
 }
 
-__global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long n4) {
-    typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
+template <typename T16>
+__global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ src, T16* __restrict__ dst, long n4) {
+    typedef typename H16<T16>::x4 h4;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(src + i * 4);
-        *reinterpret_cast<bf16x4_*>(dst + i * 4) = bf16x4_{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+        *reinterpret_cast<h4*>(dst + i * 4) = h4{(T16)v[0], (T16)v[1], (T16)v[2], (T16)v[3]};
     }
 }
 
@@ -227,8 +334,52 @@ int ds6g_focal_loss(const float* logits, const float* target, float* loss, float
                     float gamma, float upstream, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(logits && target && loss && n > 0);
-    hipLaunchKernelGGL(focal_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, dlogits, n,
-                       alpha, gamma, upstream);
+    hipLaunchKernelGGL(focal_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, dlogits, n,
+                       alpha, gamma, upstream, (const float*)nullptr);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+// the same with dlogits additionally multiplied by the loss scale held in `scaler_state` (read at run time)
+int ds6g_focal_loss_scaled(const float* logits, const float* target, float* loss, float* dlogits, int n, float alpha,
+                           float gamma, const void* scaler_state, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(logits && target && loss && dlogits && scaler_state && n > 0);
+    hipLaunchKernelGGL(focal_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, dlogits, n,
+                       alpha, gamma, 1.f, (const float*)scaler_state);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+size_t ds6g_loss_scaler_state_bytes(void) { return sizeof(LossScaleDev); }
+
+// check the (scaled) gradient arena: found_inf, unscaled norm, AdamW coefficient (see loss_scale_check_kernel); max_norm <= 0:
+// no clip.  ws: >= ds6g_loss_scale_check_workspace_bytes(n), first 4 bytes zero on first use (the kernel leaves them zero).
+size_t ds6g_loss_scale_check_workspace_bytes(long n) {
+    const long n4 = n / 4;
+    const long grid = (n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024;
+    return 8 + (size_t)grid * (sizeof(double) + sizeof(unsigned));
+}
+int ds6g_loss_scale_check(const float* g, long n, float max_norm, float pre_scale, void* scaler_state, void* ws,
+                          size_t ws_bytes, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(g && scaler_state && ws && n > 0 && n % 4 == 0);
+    const long n4 = n / 4;
+    const int grid = (int)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
+    if (ws_bytes < ds6g_loss_scale_check_workspace_bytes(n)) return DS6G_ERR_WORKSPACE;
+    double* partial = (double*)((char*)ws + 8);
+    hipLaunchKernelGGL(loss_scale_check_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, n4, max_norm, pre_scale,
+                       (LossScaleDev*)scaler_state, (unsigned*)ws, partial, (unsigned*)(partial + grid));
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+// one thread: backoff on found_inf, else advance the AdamW state (adam_state, as ds6g_adamw_state_advance) and grow the
+// scale every growth_interval clean steps
+int ds6g_loss_scale_update(void* scaler_state, void* adam_state, float beta1, float beta2, float backoff, float growth,
+                           int growth_interval, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(scaler_state && adam_state && growth_interval >= 1 && backoff > 0.f && growth >= 1.f);
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (LossScaleDev*)scaler_state,
+                       (AdamDev*)adam_state, beta1, beta2, backoff, growth, growth_interval);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
@@ -248,8 +399,8 @@ int ds6g_adamw_step(float* p, const float* g, float* m, float* v, float* shadow,
     a.ema_decay = ema_decay; a.grad_scale = grad_scale;
     const long n4 = n / 4;
     const int grid = (int)(n4 + 255) / 256 < 4096 ? (int)((n4 + 255) / 256) : 4096;
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n4, a,
-                       grad_scale_dev, (const AdamDev*)nullptr);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n4, a,
+                       grad_scale_dev, (const AdamDev*)nullptr, (const int*)nullptr);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
@@ -274,8 +425,26 @@ int ds6g_adamw_step_dev(float* p, const float* g, float* m, float* v, float* sha
     a.ema_decay = ema_decay; a.grad_scale = grad_scale;
     const long n4 = n / 4;
     const int grid = (int)(n4 + 255) / 256 < 4096 ? (int)((n4 + 255) / 256) : 4096;
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n4, a, grad_scale_dev,
-                       (const AdamDev*)state);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n4, a, grad_scale_dev,
+                       (const AdamDev*)state, (const int*)nullptr);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+// ds6g_adamw_step_dev under the loss scaler: the gradient coefficient (1/S, times the clip coefficient) and the skip decision
+// come from `scaler_state` (ds6g_loss_scale_check); a skipped step only moves the EMA shadow
+int ds6g_adamw_step_scaled(float* p, const float* g, float* m, float* v, float* shadow, long n, const void* state,
+                           const void* scaler_state, float beta1, float beta2, float eps, float wd, float ema_decay,
+                           float grad_scale, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(p && g && m && v && state && scaler_state && n % 4 == 0);
+    AdamArgs a;
+    a.lr = 0.f; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd; a.bc1 = 1.f; a.bc2_sqrt = 1.f;
+    a.ema_decay = ema_decay; a.grad_scale = grad_scale;
+    const LossScaleDev* sc = (const LossScaleDev*)scaler_state;
+    const long n4 = n / 4;
+    const int grid = (int)(n4 + 255) / 256 < 4096 ? (int)((n4 + 255) / 256) : 4096;
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n4, a, &sc->coef,
+                       (const AdamDev*)state, &sc->found_inf);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
@@ -330,15 +499,18 @@ int ds6g_small_linear_bwd(const float* dy, const float* y_mask, const float* x, 
 }
 
 // dst (bf16) = src (fp32), n % 4 == 0, both 8-byte aligned
-int ds6g_cast_f32_bf16(const float* src, void* dst, long n, void* stream) {
+extern "C++" template <typename T16>
+static int cast_f32_h16(const float* src, void* dst, long n, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(src && dst && n > 0 && n % 4 == 0);
     const long n4 = n / 4;
     const int grid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-    hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (__bf16*)dst, n4);
+    hipLaunchKernelGGL(cast_bf16_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (T16*)dst, n4);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_cast_f32_bf16(const float* src, void* dst, long n, void* stream) { return cast_f32_h16<__bf16>(src, dst, n, stream); }
+int ds6g_cast_f32_f16(const float* src, void* dst, long n, void* stream) { return cast_f32_h16<_Float16>(src, dst, n, stream); }
 
 // Multi-GPU rehearsal on one GPU (tests/test_dp_gpu.py, tools/coresidency.py): `workgroups` workgroups of 256 threads, each
 // holding `lds_bytes` of LDS, stay resident for `microseconds` (100 MHz real-time counter; every wave leaves when the time is
@@ -364,11 +536,15 @@ int ds6g_set_dropout_salt(const uint64_t* dev_ptr) {
 
 int ds6g_version(void) { return 2; }
 
+// 0 - 3: g_ds6g_bf16 (the operand mode of the fp32-storage kernels); 5: f16 storage, whose fp32-storage kernels run in
+// operand mode 0 - the storage type is kept apart (g_ds6g_storage) so that no reader of g_ds6g_bf16 sees a 5; 4: unused
+int g_ds6g_storage = 0;
 int ds6g_set_compute_mode(int mode) {
-    if (mode < 0 || mode > 3) return DS6G_ERR_ARG;
-    g_ds6g_bf16 = mode;
+    if (mode < 0 || (mode > 3 && mode != 5)) return DS6G_ERR_ARG;
+    g_ds6g_storage = mode == 5 ? 5 : 0;
+    g_ds6g_bf16 = mode == 5 ? 0 : mode;
     return 0;
 }
-int ds6g_get_compute_mode(void) { return g_ds6g_bf16; }
+int ds6g_get_compute_mode(void) { return g_ds6g_storage == 5 ? 5 : g_ds6g_bf16; }
 
 }  // extern "C"

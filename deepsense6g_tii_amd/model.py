@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import math
 import os
+from functools import partial
 from types import SimpleNamespace
 from typing import NamedTuple
 
@@ -34,6 +35,8 @@ from ._lib import lib
 
 F32 = torch.float32
 BF16 = torch.bfloat16
+F16 = torch.float16
+_H16 = (BF16, F16)   # the 16-bit storage dtypes of the walk (compute modes "bf16" and "f16")
 STAGE_WIDTH = (64, 128, 256, 512)
 RESNET_LAYERS = {"resnet34": (3, 4, 6, 3), "resnet18": (2, 2, 2, 2)}
 
@@ -204,6 +207,12 @@ _F32_OPS = SimpleNamespace(dtype=F32, ln_fwd=ops.layernorm_fwd, ln_bwd=ops.layer
 _BF16_OPS = SimpleNamespace(dtype=BF16, ln_fwd=ops.layernorm_fwd_bf16, ln_bwd=ops.layernorm_bwd_bf16,
                             lin_fwd=ops.bf16_linear_fwd, lin_dgrad=ops.bf16_linear_dgrad, lin_wgrad=ops.bf16_linear_wgrad,
                             attn_fwd=ops.attention_fwd_bf16, attn_bwd=ops.attention_bwd_bf16io)
+# f16 storage: the same kernels' f16 twins (the ops wrappers dispatch by operand dtype; LayerNorm is told its output dtype)
+_F16_OPS = SimpleNamespace(dtype=F16, ln_fwd=partial(ops.layernorm_fwd_bf16, dtype=F16),
+                           ln_bwd=partial(ops.layernorm_bwd_bf16, dtype=F16), lin_fwd=ops.bf16_linear_fwd,
+                           lin_dgrad=ops.bf16_linear_dgrad, lin_wgrad=ops.bf16_linear_wgrad, attn_fwd=ops.attention_fwd_bf16,
+                           attn_bwd=ops.attention_bwd_bf16io)
+_OPS16 = {BF16: _BF16_OPS, F16: _F16_OPS}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -274,6 +283,7 @@ class TransFuser(nn.Module):
         self.bf16_stems = os.environ.get("DS6G_BF16_STEMS", "1") != "0"   # 7x7 stems on bf16 storage too (csrc/stem.hip)
         self._arena16 = None
         self._use16 = False
+        self._dt16 = BF16      # the walk's 16-bit storage dtype (bf16 in mode "bf16", f16 in mode "f16")
         self._anchor = None
         self._arena = None
         self._wfast = None     # parameter-pointer table of the walk in flight (see _run_forward)
@@ -484,11 +494,13 @@ class TransFuser(nn.Module):
         over the arena (0.47 GB of traffic, ~0.1 ms: 0.3 % of a step), so it can never be stale whatever touched the
         parameters (optimizer, load_state_dict, in-place edits).  Off when the parameters were re-pointed away from the
         arena (EMA shadow applied): the fp32-storage kernels then run, reading the live pointers."""
-        self._use16 = bool(self.bf16_storage and self._arena is not None and lib().get_compute_mode() == 1
+        mode = lib().get_compute_mode()
+        self._use16 = bool(self.bf16_storage and self._arena is not None and mode in (1, 5)
                            and self.fuse_qkv and self.params_in_arena())
         if self._use16:
-            if self._arena16 is None:
-                self._arena16 = torch.empty(self._arena.numel(), dtype=torch.bfloat16, device=self.device)
+            self._dt16 = F16 if mode == 5 else BF16
+            if self._arena16 is None or self._arena16.dtype != self._dt16:   # (re)allocated when the mode changes
+                self._arena16 = torch.empty(self._arena.numel(), dtype=self._dt16, device=self.device)
             ops.cast_bf16(self._arena, out=self._arena16)
 
     def _begin_backward(self):
@@ -632,8 +644,9 @@ class TransFuser(nn.Module):
         run.graph = graph
         return run
 
-    def train_step_loss(self, image_list, lidar_list, radar_list, gps, target, alpha=0.25, gamma=2.0):
-        """Fused forward -> sigmoid focal loss -> backward without autograd (the harness path).
+    def train_step_loss(self, image_list, lidar_list, radar_list, gps, target, alpha=0.25, gamma=2.0, loss_scaler=None):
+        """Fused forward -> sigmoid focal loss -> backward without autograd (the harness path).  loss_scaler (a
+        train.DynamicLossScaler): the backward starts from dlogits * S, S read on the device; the returned loss is unscaled.
         Returns (loss tensor [1], logits)."""
         images, lidars, radars, gps = self._inputs(image_list, lidar_list, radar_list, gps)
         if target.dim() == 1:  # class-index target (temp_coef = 0 path, train2_seq.py:124 -> FocalLoss :297-298)
@@ -644,8 +657,12 @@ class TransFuser(nn.Module):
             raise ValueError(f"focal-loss target shape {tuple(target.shape)} != logits shape {tuple(logits.shape)}")
         loss = torch.empty(1, dtype=F32, device=self.device)
         dlogits = torch.empty_like(logits)
-        lib().focal_loss(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), dlogits.data_ptr(), logits.numel(),
-                         alpha, gamma, 1.0, ops._stream())
+        if loss_scaler is not None:
+            lib().focal_loss_scaled(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), dlogits.data_ptr(), logits.numel(),
+                                    alpha, gamma, loss_scaler.state.data_ptr(), ops._stream())
+        else:
+            lib().focal_loss(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), dlogits.data_ptr(), logits.numel(),
+                             alpha, gamma, 1.0, ops._stream())
         self._run_backward(tape, dlogits)
         return loss, logits
 
@@ -658,7 +675,7 @@ class TransFuser(nn.Module):
 
     def _bn_fwd(self, bn, x, relu, residual, train):
         """BatchNorm (+ residual, + ReLU) of an fp32 or bf16 feature map; statistics fp32 -> (y, (mean, invstd))"""
-        f16 = x.dtype == BF16
+        f16 = x.dtype in _H16
         C = x.shape[-1]
         M = x.numel() // C
         stats = torch.empty(2, C, dtype=F32, device=x.device)
@@ -681,10 +698,11 @@ class TransFuser(nn.Module):
             # are bf16; the conv's epilogue delivers the BatchNorm statistics
             B, S = frames[0].shape[0], len(frames)
             H, W = frames[0].shape[2:]
-            x16 = torch.empty((B * S, H, W, 4), dtype=torch.bfloat16, device=self.device)
+            x16 = torch.empty((B * S, H, W, 4), dtype=self._dt16, device=self.device)
+            pack = L.pack_input_bf16 if self._dt16 == BF16 else L.pack_input_f16
             for t, f in enumerate(frames):
                 assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
-                L.pack_input_bf16(f.data_ptr(), x16.data_ptr(), B, cin, H, W, S, t, int(normalize), st)
+                pack(f.data_ptr(), x16.data_ptr(), B, cin, H, W, S, t, int(normalize), st)
             bn = trunk.bn1
             stats = torch.empty(2, 64, dtype=F32, device=self.device)
             if train:
@@ -723,7 +741,7 @@ class TransFuser(nn.Module):
             else:
                 ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), 64, stats[0], stats[1], bn.eps)
             st1 = (stats[0], stats[1])
-            pool = ops.bn_relu_maxpool_bf16out if self._use16 else ops.bn_relu_maxpool
+            pool = partial(ops.bn_relu_maxpool_bf16out, dtype=self._dt16) if self._use16 else ops.bn_relu_maxpool
             p1, idx = pool(c1, st1[0], st1[1], self._w(bn.weight), self._w(bn.bias))
             return p1, _StemRec(x, c1, None, st1, idx, cin)
         N, H1, W1, _ = a1.shape
@@ -739,7 +757,7 @@ class TransFuser(nn.Module):
         exact-fp32 mode: 2.25x fewer MFMA FLOPs - the direct kernel already runs at the chip's power-limited fp32 rate),
         else the implicit GEMM.  ud = the transformed dgrad filter when the backward pass will want it (recording), else
         None."""
-        if x.dtype == BF16:
+        if x.dtype in _H16:
             return ops.bf16_conv2d_fwd(x, self._w16(conv.weight), K, R, R, stride, R // 2), None
         if R == 3 and stride == 1 and self.use_winograd and ops.winograd_ok(x.shape, K):
             C = x.shape[-1]
@@ -752,7 +770,7 @@ class TransFuser(nn.Module):
 
     def _conv_dgrad(self, dy, conv, x_shape, R, stride, out=None, accumulate=False, ud=None):
         """data gradient of _conv_fwd; ud: the Winograd dgrad filter recorded by the forward (fp32 storage) or None"""
-        if dy.dtype == BF16:
+        if dy.dtype in _H16:
             return ops.bf16_conv2d_dgrad(dy, self._w16(conv.weight), tuple(x_shape), R, R, stride, R // 2, out=out,
                                          accumulate=accumulate)
         K = dy.shape[-1]
@@ -788,7 +806,7 @@ class TransFuser(nn.Module):
                 idn = ops.conv2d_bias_act_fwd(x, wd.data_ptr(), bd.data_ptr(), K, 1, 1, blk.stride, 0, relu=0)
             out = conv3(a1, blk.conv2, blk.bn2, 1, 2, residual=idn)
             return out, None
-        if train and self.fuse_bn_stats16 and x.dtype == BF16:
+        if train and self.fuse_bn_stats16 and x.dtype in _H16:
             # bf16 train mode: the conv's epilogue emits the BatchNorm statistics of its (stored) output - no statistics
             # pass (the downsample conv runs before conv2 here)
             def conv_bn(inp, conv, bn, R, stride, pad, relu, residual):
@@ -822,7 +840,7 @@ class TransFuser(nn.Module):
         the bf16 shadow, while the residual stream x, x1, x2 and every statistic stay fp32.  Same dropout counters / masks
         in both storages.  -> (x2, _GptRec)"""
         f16 = self._use16
-        op, w = (_BF16_OPS, self._w16) if f16 else (_F32_OPS, self._w)
+        op, w = (_OPS16[self._dt16], self._w16) if f16 else (_F32_OPS, self._w)
         cfg = self.config
         C = x.shape[1]
         nh = cfg.n_head
@@ -869,11 +887,11 @@ class TransFuser(nn.Module):
         x0 = torch.empty((B, T, C), dtype=F32, device=self.device)
         off_e = self._next_drop(x0.numel()) if pe > 0 else 0
         pos = self._w(gpt.pos_emb)
-        f16 = feats[0].dtype == torch.bfloat16   # bf16-storage path: feature maps bf16, tokens fp32
+        f16 = feats[0].dtype in _H16   # 16-bit storage path: feature maps bf16 / f16, tokens fp32
         for m in range(3):
             N, H = feats[m].shape[0], feats[m].shape[1]
-            assert feats[m].shape == (B * fps[m], H, H, C) and (feats[m].dtype == torch.bfloat16) == f16
-            (L.bf16_avgpool_tokens_fwd if f16 else L.avgpool_tokens_fwd)(
+            assert feats[m].shape == (B * fps[m], H, H, C) and feats[m].dtype == feats[0].dtype
+            (ops._fn("bf16_avgpool_tokens_fwd", feats[m].dtype) if f16 else L.avgpool_tokens_fwd)(
                 feats[m].data_ptr(), pos, x0.data_ptr(), N, H, C, fps[m], offs[m], T, pe, self._seed, off_e, st)
         _, gptr, rpg, gstride, K = gps_src
         gemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
@@ -890,7 +908,7 @@ class TransFuser(nn.Module):
         for m in range(3):
             N, H = feats[m].shape[0], feats[m].shape[1]
             o = torch.empty_like(feats[m])
-            (L.bf16_upsample_add_fwd if f16 else L.upsample_add_fwd)(
+            (ops._fn("bf16_upsample_add_fwd", feats[m].dtype) if f16 else L.upsample_add_fwd)(
                 feats[m].data_ptr(), xo.data_ptr(), o.data_ptr(), N, H, C, fps[m], offs[m], T, st)
             outs.append(o)
         return outs, xo, _StageRec(s, C, T, fps, offs, pe, off_e, gps_src, blk_ctx, x, mf, rf, [f.shape for f in feats])
@@ -989,7 +1007,7 @@ class TransFuser(nn.Module):
             N = feats[m].shape[0]
             assert feats[m].shape[1:] == (8, 8, 512)
             pl = torch.empty((N, 512), dtype=F32, device=self.device)
-            (L.bf16_global_pool if feats[m].dtype == torch.bfloat16 else L.global_pool)(feats[m].data_ptr(), pl.data_ptr(), N, 512, st)
+            (ops._fn("bf16_global_pool", feats[m].dtype) if feats[m].dtype in _H16 else L.global_pool)(feats[m].data_ptr(), pl.data_ptr(), N, 512, st)
             pooled.append(pl)
         fused = torch.empty((B, 512), dtype=F32, device=self.device)
         L.head_sum(pooled[0].data_ptr(), pooled[1].data_ptr(), pooled[2].data_ptr(), xo.data_ptr(), fused.data_ptr(), B,
@@ -1024,7 +1042,7 @@ class TransFuser(nn.Module):
     def _conv_wgrad(self, conv, x, dy, R, stride):
         """weight gradient of _conv_fwd (bf16 storage: bf16 operands, fp32 gradient)"""
         gp, acc = self._g(conv.weight)
-        if x.dtype == BF16:
+        if x.dtype in _H16:
             self._wg_launch(lambda: ops.bf16_conv2d_wgrad(x, dy, gp, R, R, stride, R // 2, self._ws, accumulate=bool(acc)),
                             (x, dy))
             return
@@ -1075,7 +1093,7 @@ class TransFuser(nn.Module):
         tensor twice"""
         gw, aw = self._g(bn.weight)
         gb, _ = self._g(bn.bias)
-        return (ops.bf16_bn_bwd if dy.dtype == BF16 else ops.bn_bwd)(
+        return (ops.bf16_bn_bwd if dy.dtype in _H16 else ops.bn_bwd)(
             dy, None if relu_no_residual else y_mask, x, stats[0], stats[1], self._w(bn.weight), gw, gb, self._ws,
             want_dres=want_dres, accumulate=bool(aw), relu_beta_ptr=self._w(bn.bias) if relu_no_residual else 0)
 
@@ -1104,8 +1122,8 @@ class TransFuser(nn.Module):
         itself); next_drop = (p, seed, off) of the block below: the final LayerNorm backward then also emits dropout(dx).
         Returns (dx fp32, dropout(dx) or None)."""
         r = rec
-        f16 = r.h.dtype == BF16
-        op, w = (_BF16_OPS, self._w16) if f16 else (_F32_OPS, self._w)
+        f16 = r.h.dtype in _H16
+        op, w = (_OPS16[r.h.dtype], self._w16) if f16 else (_F32_OPS, self._w)
         C = r.x.shape[1]
         nh = self.config.n_head
         at = blk.attn
@@ -1171,10 +1189,10 @@ class TransFuser(nn.Module):
         gpt = getattr(self.encoder, f"transformer{s}")
         vel = getattr(self.encoder, f"vel_emb{s}")
         dxo = torch.empty((B * T, C), dtype=F32, device=self.device)
-        f16 = dfeats_out[0].dtype == torch.bfloat16
+        f16 = dfeats_out[0].dtype in _H16
         for m in range(3):
             N, H = fshapes[m][0], fshapes[m][1]
-            (L.bf16_upsample_add_bwd if f16 else L.upsample_add_bwd)(dfeats_out[m].data_ptr(), dxo.data_ptr(), N, H, C, fps[m],
+            (ops._fn("bf16_upsample_add_bwd", dfeats_out[m].dtype) if f16 else L.upsample_add_bwd)(dfeats_out[m].data_ptr(), dxo.data_ptr(), N, H, C, fps[m],
                                                                      offs[m], T, st)
         gsrc, bcast = dgps_tok
         L.gps_rows(gsrc.data_ptr(), dxo.data_ptr(), B, C, T, 1, 0, int(bcast), st)
@@ -1183,7 +1201,7 @@ class TransFuser(nn.Module):
         rev = list(zip(reversed(list(gpt.blocks)), reversed(rec.blocks)))
         # (resid_pdrop, seed, fc2-branch mask offset) of each block, in backward order; None below the last
         drops = [(bc.pr, self._seed, bc.off_m) for _, bc in rev] + [None]
-        ln_bwd = ops.layernorm_bwd_bf16 if rec.blocks and rec.blocks[0].h.dtype == BF16 else ops.layernorm_bwd
+        ln_bwd = _OPS16[rec.blocks[0].h.dtype].ln_bwd if rec.blocks and rec.blocks[0].h.dtype in _H16 else ops.layernorm_bwd
         dx, dz = ln_bwd(dxo, rec.x_last, rec.mf, rec.rf, self._w(gpt.ln_f.weight), gfw, gfb, self._ws, accumulate=bool(af),
                         drop=drops[0])
         for i, (blk, bc) in enumerate(rev):
@@ -1196,7 +1214,7 @@ class TransFuser(nn.Module):
         for m in range(3):
             N, H = fshapes[m][0], fshapes[m][1]
             d = torch.empty(tuple(fshapes[m]), dtype=dfeats_out[m].dtype, device=self.device)
-            (L.bf16_avgpool_tokens_bwd if f16 else L.avgpool_tokens_bwd)(dpre.data_ptr(), dfeats_out[m].data_ptr(), d.data_ptr(),
+            (ops._fn("bf16_avgpool_tokens_bwd", dfeats_out[m].dtype) if f16 else L.avgpool_tokens_bwd)(dpre.data_ptr(), dfeats_out[m].data_ptr(), d.data_ptr(),
                                                                        N, H, C, fps[m], offs[m], T, st)
             dfeats.append(d)
         dgemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
@@ -1219,13 +1237,13 @@ class TransFuser(nn.Module):
         bn = trunk.bn1
         gw_bn, a_bn = self._g(bn.weight)
         gb_bn, _ = self._g(bn.bias)
-        if c1.dtype == torch.bfloat16:   # the bf16 stem (csrc/stem.hip)
+        if c1.dtype in _H16:   # the 16-bit stem (csrc/stem.hip)
             dc1 = ops.bf16_stem_bn_bwd_maxpool(dpool, idx, c1, st1[0], st1[1], self._w(bn.weight), self._w(bn.bias), gw_bn,
                                                gb_bn, self._ws, accumulate=bool(a_bn))
             gw, aw = self._g(trunk.conv1.weight)
             self._wg_launch(lambda: ops.bf16_stem_wgrad(x, dc1, gw, cin, self._ws, accumulate=bool(aw)), (x, dc1))
             return
-        bwd_pool = ops.bn_bwd_maxpool_bf16in if dpool.dtype == torch.bfloat16 else ops.bn_bwd_maxpool
+        bwd_pool = ops.bn_bwd_maxpool_bf16in if dpool.dtype in _H16 else ops.bn_bwd_maxpool
         dc1 = bwd_pool(dpool, idx, c1, st1[0], st1[1], self._w(bn.weight), self._w(bn.bias), gw_bn, gb_bn,
                        self._ws, accumulate=bool(a_bn))
         dwpad = torch.empty((64, 7, 7, 4), dtype=F32, device=self.device)
@@ -1290,7 +1308,7 @@ class TransFuser(nn.Module):
         for m in range(3):
             d = torch.empty(tuple(fshapes[m]), dtype=fdtype, device=self.device)
             fps = cfg.n_views * S if m == 0 else S
-            (L.bf16_head_bwd if fdtype == torch.bfloat16 else L.head_bwd)(dfused.data_ptr(), d.data_ptr(), fshapes[m][0], 512,
+            (ops._fn("bf16_head_bwd", fdtype) if fdtype in _H16 else L.head_bwd)(dfused.data_ptr(), d.data_ptr(), fshapes[m][0], 512,
                                                                         fps, st)
             dfeats.append(d)
         dgps = (dfused, True)

@@ -118,9 +118,9 @@ def bn_fold(w_ohwi_ptr, bn, K, taps, cin, cpad=None):
 def winograd_ok(x_shape, K):
     """3x3 / stride 1 / pad 1 conv of an NHWC tensor of this shape to K channels can run as Winograd F(2x2, 3x3)"""
     N, H, W, C = x_shape
-    # exact-fp32 products only: the default mode, and f32x6 (fp32-grade: its direct kernels use the six-product split, its
+    # exact-fp32 products only: the default mode, f16 (whose fp32-storage kernels are those of "f32"), and f32x6 (fp32-grade: its direct kernels use the six-product split, its
     # 3x3 / stride-1 convs stay on the fp32 Winograd kernel, which is faster than the split direct form)
-    return bool(lib().winograd_supported(N, H, W, C, K)) and lib().get_compute_mode() in (0, 3)
+    return bool(lib().winograd_supported(N, H, W, C, K)) and lib().get_compute_mode() in (0, 3, 5)
 
 
 def winograd_weights(w_ohwi_ptr, K, C, device, dgrad=False, both=False):
@@ -155,7 +155,7 @@ def conv3x3_winograd_bias_act(x, u, bias_ptr, K, relu=0, residual=None):
 
 def winograd_wgrad_ok(x_shape, K):
     N, H, W, C = x_shape
-    return bool(lib().winograd_wgrad_supported(N, H, W, C, K)) and lib().get_compute_mode() in (0, 3)
+    return bool(lib().winograd_wgrad_supported(N, H, W, C, K)) and lib().get_compute_mode() in (0, 3, 5)
 
 
 def conv3x3_winograd_wgrad(x, dy, dw_ohwi_ptr, ws: Workspace, accumulate=False):
@@ -367,7 +367,7 @@ def axpby(a, b, alpha=1.0, beta=1.0, out=None):
     return o
 
 
-_MODES = {"f32": 0, "bf16": 1, "f32x3": 2, "f32x6": 3}
+_MODES = {"f32": 0, "bf16": 1, "f32x3": 2, "f32x6": 3, "f16": 5}
 
 
 def set_compute_mode(mode: str):
@@ -376,7 +376,10 @@ def set_compute_mode(mode: str):
     "bf16"  - operands rounded to bf16 on the way into the MFMA, fp32 accumulate and storage (throughput mode; the
               reference has no mixed precision, tolerances for it are declared in tests/test_bf16_gpu.py);
     "f32x3" - split bf16: a*b = hi*hi + hi*lo + lo*hi on the bf16 matrix cores, fp32 accumulate and storage; relative
-              product error <= ~2^-16 (tests/test_bf16_gpu.py holds it to the 1e-3 bar of the exact path)."""
+              product error <= ~2^-16 (tests/test_bf16_gpu.py holds it to the 1e-3 bar of the exact path);
+    "f16"   - the bf16 configuration's 16-bit STORAGE with IEEE half instead of bf16 (3 more significand bits, same matrix-core
+              cycles); everything that is not 16-bit storage runs exactly as in "f32" (eval, the small linears, the fp32
+              stems).  A training-storage mode: train it with train.DynamicLossScaler."""
     if mode not in _MODES:
         raise ValueError(f"compute mode must be one of {sorted(_MODES)}, got {mode!r}")
     lib().set_compute_mode(_MODES[mode])
@@ -387,14 +390,25 @@ def get_compute_mode() -> str:
 
 
 # ------------------------------------------------------------------------------------------------
-# bf16-stored operands (csrc/bgemm.hip): activations / weight shadow bf16, accumulation fp32
+# 16-bit stored operands (csrc/bgemm.hip): activations / weight shadow bf16 or f16, accumulation fp32.  The bf16_* wrappers
+# below dispatch by the dtype of their 16-bit operand: torch.float16 tensors go to the f16-storage twins (ds6g_f16_*,
+# *_f16*) of the same kernels; outputs take the operand's dtype.
 BF16 = torch.bfloat16
+F16 = torch.float16
 
 
-def _chk16(t, *shape):
-    assert t.dtype == BF16 and t.is_cuda and t.is_contiguous(), (t.dtype, t.device, t.stride())
+def _chk16(t, *shape, dtype=None):
+    """a contiguous bf16 / f16 device tensor (of `dtype` when given: every 16-bit operand of one call shares one dtype)"""
+    assert t.dtype in (BF16, F16) and t.is_cuda and t.is_contiguous(), (t.dtype, t.device, t.stride())
+    assert dtype is None or t.dtype == dtype, (t.dtype, dtype)
     if shape:
         assert tuple(t.shape) == tuple(shape), (tuple(t.shape), shape)
+
+
+def _fn(name, dtype):
+    """the C entry point `name` (a bf16 one) for 16-bit storage of `dtype`"""
+    assert dtype in (BF16, F16), dtype
+    return getattr(lib(), name if dtype == BF16 else name.replace("bf16", "f16"))
 
 
 def bf16_linear_fwd(x, w16_ptr, b_ptr, N, relu=False, residual=None, drop_p=0.0, seed=0, seed_off=0, out16=True):
@@ -402,10 +416,10 @@ def bf16_linear_fwd(x, w16_ptr, b_ptr, N, relu=False, residual=None, drop_p=0.0,
     M, K = x.shape
     _chk16(x)
     out16 = bool(out16) and residual is None
-    y = torch.empty((M, N), dtype=BF16 if out16 else F32, device=x.device)
+    y = torch.empty((M, N), dtype=x.dtype if out16 else F32, device=x.device)
     if residual is not None:
         _chk(residual, M, N)
-    lib().bf16_linear_fwd(_p(x), w16_ptr, b_ptr, _p(y), int(out16), M, N, K, int(relu), _p(residual), float(drop_p), seed,
+    _fn("bf16_linear_fwd", x.dtype)(_p(x), w16_ptr, b_ptr, _p(y), int(out16), M, N, K, int(relu), _p(residual), float(drop_p), seed,
                           seed_off, _stream())
     return y
 
@@ -414,13 +428,14 @@ def bf16_linear_dgrad(dy, w16_ptr, K, relu_mask_src=None, out16=True, out=None, 
     """dx (+)= (dy w) * (mask > 0): dy [M, N] bf16, w [N, K] bf16; mask bf16 or fp32 [M, K]"""
     M, N = dy.shape
     _chk16(dy)
-    dx = out if out is not None else torch.empty((M, K), dtype=BF16 if out16 else F32, device=dy.device)
-    assert dx.dtype == (BF16 if out16 else F32) and tuple(dx.shape) == (M, K) and dx.is_contiguous()
+    dx = out if out is not None else torch.empty((M, K), dtype=dy.dtype if out16 else F32, device=dy.device)
+    assert dx.dtype == (dy.dtype if out16 else F32) and tuple(dx.shape) == (M, K) and dx.is_contiguous()
     mask16 = 0
     if relu_mask_src is not None:
         assert tuple(relu_mask_src.shape) == (M, K) and relu_mask_src.is_contiguous() and out16
-        mask16 = int(relu_mask_src.dtype == BF16)
-    lib().bf16_linear_dgrad(_p(dy), w16_ptr, _p(dx), int(out16), M, N, K, _p(relu_mask_src), mask16, int(accumulate), _stream())
+        mask16 = int(relu_mask_src.dtype != F32)
+        assert relu_mask_src.dtype in (F32, dy.dtype)
+    _fn("bf16_linear_dgrad", dy.dtype)(_p(dy), w16_ptr, _p(dx), int(out16), M, N, K, _p(relu_mask_src), mask16, int(accumulate), _stream())
     return dx
 
 
@@ -430,16 +445,16 @@ def bf16_linear_wgrad(x, dy, dw_ptr, ws: Workspace, accumulate=False, dbias_ptr=
     M2, N = dy.shape
     assert M == M2
     _chk16(x)
-    _chk16(dy)
-    lib().bf16_linear_wgrad(_p(x), _p(dy), dw_ptr, dbias_ptr, M, N, K, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    _chk16(dy, dtype=x.dtype)
+    _fn("bf16_linear_wgrad", x.dtype)(_p(x), _p(dy), dw_ptr, dbias_ptr, M, N, K, int(accumulate), ws.ptr, ws.nbytes, _stream())
 
 
 def bf16_conv2d_fwd(x, w16_ptr, K, R, S, stride, pad, out16=True):
     N, H, W, C = x.shape
     _chk16(x)
     Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
-    y = torch.empty((N, Ho, Wo, K), dtype=BF16 if out16 else F32, device=x.device)
-    lib().bf16_conv2d_fwd(_p(x), w16_ptr, _p(y), int(out16), N, H, W, C, K, R, S, stride, pad, _stream())
+    y = torch.empty((N, Ho, Wo, K), dtype=x.dtype if out16 else F32, device=x.device)
+    _fn("bf16_conv2d_fwd", x.dtype)(_p(x), w16_ptr, _p(y), int(out16), N, H, W, C, K, R, S, stride, pad, _stream())
     return y
 
 
@@ -451,8 +466,8 @@ def bf16_conv2d_fwd_bnstats(x, w16_ptr, K, R, S, stride, pad, mean, invstd, rm_p
     _chk(mean, K)
     _chk(invstd, K)
     Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
-    y = torch.empty((N, Ho, Wo, K), dtype=BF16, device=x.device)
-    lib().bf16_conv2d_fwd_bnstats(_p(x), w16_ptr, _p(y), N, H, W, C, K, R, S, stride, pad, eps, momentum, _p(mean),
+    y = torch.empty((N, Ho, Wo, K), dtype=x.dtype, device=x.device)
+    _fn("bf16_conv2d_fwd_bnstats", x.dtype)(_p(x), w16_ptr, _p(y), N, H, W, C, K, R, S, stride, pad, eps, momentum, _p(mean),
                                   _p(invstd), rm_ptr, rv_ptr, ws.ptr, ws.nbytes, _stream())
     return y
 
@@ -462,9 +477,9 @@ def bf16_conv2d_dgrad(dy, w16_ptr, x_shape, R, S, stride, pad, out16=True, out=N
     Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
     K = dy.shape[3]
     _chk16(dy, N, Ho, Wo, K)
-    dx = out if out is not None else torch.empty(x_shape, dtype=BF16 if out16 else F32, device=dy.device)
-    assert dx.dtype == (BF16 if out16 else F32) and tuple(dx.shape) == tuple(x_shape) and dx.is_contiguous()
-    lib().bf16_conv2d_dgrad(_p(dy), w16_ptr, _p(dx), int(out16), N, H, W, C, K, R, S, stride, pad, int(accumulate), _stream())
+    dx = out if out is not None else torch.empty(x_shape, dtype=dy.dtype if out16 else F32, device=dy.device)
+    assert dx.dtype == (dy.dtype if out16 else F32) and tuple(dx.shape) == tuple(x_shape) and dx.is_contiguous()
+    _fn("bf16_conv2d_dgrad", dy.dtype)(_p(dy), w16_ptr, _p(dx), int(out16), N, H, W, C, K, R, S, stride, pad, int(accumulate), _stream())
     return dx
 
 
@@ -473,43 +488,43 @@ def bf16_conv2d_wgrad(x, dy, dw_ptr, R, S, stride, pad, ws: Workspace, accumulat
     _chk16(x)
     Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
     K = dy.shape[3]
-    _chk16(dy, N, Ho, Wo, K)
-    lib().bf16_conv2d_wgrad(_p(x), _p(dy), dw_ptr, N, H, W, C, K, R, S, stride, pad, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    _chk16(dy, N, Ho, Wo, K, dtype=x.dtype)
+    _fn("bf16_conv2d_wgrad", x.dtype)(_p(x), _p(dy), dw_ptr, N, H, W, C, K, R, S, stride, pad, int(accumulate), ws.ptr, ws.nbytes, _stream())
 
 
-def cast_bf16(src, out=None):
-    """bf16 copy (RNE) of a contiguous fp32 tensor whose numel is a multiple of 4"""
+def cast_bf16(src, out=None, dtype=BF16):
+    """bf16 (or f16: dtype / out.dtype) copy (RNE) of a contiguous fp32 tensor whose numel is a multiple of 4"""
     _chk(src)
-    dst = out if out is not None else torch.empty(src.shape, dtype=BF16, device=src.device)
-    assert dst.dtype == BF16 and dst.numel() == src.numel() and dst.is_contiguous()
-    lib().cast_f32_bf16(_p(src), _p(dst), src.numel(), _stream())
+    dst = out if out is not None else torch.empty(src.shape, dtype=dtype, device=src.device)
+    assert dst.dtype in (BF16, F16) and dst.numel() == src.numel() and dst.is_contiguous()
+    _fn("cast_f32_bf16", dst.dtype)(_p(src), _p(dst), src.numel(), _stream())
     return dst
 
 
-def layernorm_fwd_bf16(x, gamma_ptr, beta_ptr, eps=1e-5):
-    """LayerNorm of fp32 rows, output written as bf16 (a GEMM operand) -> (y16, mean, rstd)"""
+def layernorm_fwd_bf16(x, gamma_ptr, beta_ptr, eps=1e-5, dtype=BF16):
+    """LayerNorm of fp32 rows, output written as bf16 / f16 (dtype; a GEMM operand) -> (y16, mean, rstd)"""
     M, C = x.shape
     _chk(x)
-    y = torch.empty((M, C), dtype=BF16, device=x.device)
+    y = torch.empty((M, C), dtype=dtype, device=x.device)
     mean = torch.empty(M, dtype=F32, device=x.device)
     rstd = torch.empty(M, dtype=F32, device=x.device)
-    lib().layernorm_fwd_bf16out(_p(x), gamma_ptr, beta_ptr, _p(y), _p(mean), _p(rstd), M, C, eps, _stream())
+    _fn("layernorm_fwd_bf16out", dtype)(_p(x), gamma_ptr, beta_ptr, _p(y), _p(mean), _p(rstd), M, C, eps, _stream())
     return y, mean, rstd
 
 
 def layernorm_bwd_bf16(dy, x, mean, rstd, gamma_ptr, dgamma_ptr, dbeta_ptr, ws: Workspace, add=None, accumulate=False,
-                       drop=None, want_drop=True):
-    """dy bf16 or fp32 -> (dx fp32, dropout(dx) as bf16); drop = (p, seed, seed_off) or None (= plain bf16 copy of dx);
-    want_drop False: no second output (-> (dx, None))"""
+                       drop=None, want_drop=True, dtype=BF16):
+    """dy 16-bit (dtype: bf16 / f16) or fp32 -> (dx fp32, dropout(dx) as dtype); drop = (p, seed, seed_off) or None (= plain
+    16-bit copy of dx); want_drop False: no second output (-> (dx, None))"""
     M, C = x.shape
-    assert tuple(dy.shape) == (M, C) and dy.is_contiguous() and dy.dtype in (BF16, F32)
+    assert tuple(dy.shape) == (M, C) and dy.is_contiguous() and dy.dtype in (dtype, F32)
     _chk(x)
     if add is not None:
         _chk(add, M, C)
     dx = torch.empty_like(x)
-    dxd = torch.empty((M, C), dtype=BF16, device=x.device) if want_drop else None
+    dxd = torch.empty((M, C), dtype=dtype, device=x.device) if want_drop else None
     p, seed, off = drop if drop is not None else (0.0, 0, 0)
-    lib().layernorm_bwd_bf16(_p(dy), int(dy.dtype == BF16), _p(x), _p(mean), _p(rstd), gamma_ptr, _p(add), _p(dx), dgamma_ptr,
+    _fn("layernorm_bwd_bf16", dtype)(_p(dy), int(dy.dtype != F32), _p(x), _p(mean), _p(rstd), gamma_ptr, _p(add), _p(dx), dgamma_ptr,
                              dbeta_ptr, M, C, int(accumulate), _p(dxd), float(p), seed, off, ws.ptr, ws.nbytes, _stream())
     return dx, dxd
 
@@ -552,7 +567,7 @@ def attention_bwd_bf16(q, k, v, o16, d_o, lse, B, T, nh, ws: Workspace, drop_p=0
 # ---- bf16-storage path: BatchNorm / pooling / resampling on bf16 feature maps (statistics and arithmetic fp32) ----
 def bf16_bn_stats(x2d_rows, C, x, mean, invstd, rm_ptr, rv_ptr, ws: Workspace, eps=1e-5, momentum=0.1):
     _chk16(x)
-    lib().bf16_bn_stats(_p(x), x2d_rows, C, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr, ws.nbytes, _stream())
+    _fn("bf16_bn_stats", x.dtype)(_p(x), x2d_rows, C, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr, ws.nbytes, _stream())
 
 
 def bf16_bn_apply(x, mean, invstd, gamma_ptr, beta_ptr, relu, residual=None):
@@ -560,34 +575,34 @@ def bf16_bn_apply(x, mean, invstd, gamma_ptr, beta_ptr, relu, residual=None):
     C = x.shape[-1]
     y = torch.empty_like(x)
     if residual is not None:
-        _chk16(residual, *x.shape)
-    lib().bf16_bn_apply(_p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(residual), _p(y), x.numel() // C, C, int(relu),
+        _chk16(residual, *x.shape, dtype=x.dtype)
+    _fn("bf16_bn_apply", x.dtype)(_p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(residual), _p(y), x.numel() // C, C, int(relu),
                         _stream())
     return y
 
 
 def bf16_bn_bwd(dy, y_mask, x, mean, invstd, gamma_ptr, dgamma_ptr, dbeta_ptr, ws: Workspace, want_dres=False,
                 accumulate=False, relu_beta_ptr=0):
-    _chk16(dy, *x.shape)
+    _chk16(dy, *x.shape, dtype=x.dtype)
     _chk16(x)
     if y_mask is not None:
-        _chk16(y_mask, *x.shape)
+        _chk16(y_mask, *x.shape, dtype=x.dtype)
     C = x.shape[-1]
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
-    lib().bf16_bn_bwd(_p(dy), _p(y_mask), _p(x), _p(mean), _p(invstd), gamma_ptr, relu_beta_ptr, _p(dx), dgamma_ptr, dbeta_ptr,
+    _fn("bf16_bn_bwd", x.dtype)(_p(dy), _p(y_mask), _p(x), _p(mean), _p(invstd), gamma_ptr, relu_beta_ptr, _p(dx), dgamma_ptr, dbeta_ptr,
                       _p(dres), x.numel() // C, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
     return dx, dres
 
 
-def bn_relu_maxpool_bf16out(x, mean, invstd, gamma_ptr, beta_ptr):
-    """the stem's BN -> ReLU -> MaxPool of the fp32 conv output, pooled tensor written as bf16"""
+def bn_relu_maxpool_bf16out(x, mean, invstd, gamma_ptr, beta_ptr, dtype=BF16):
+    """the stem's BN -> ReLU -> MaxPool of the fp32 conv output, pooled tensor written as bf16 / f16 (dtype)"""
     N, H, W, C = x.shape
     _chk(x)
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
-    y = torch.empty((N, Ho, Wo, C), dtype=BF16, device=x.device)
+    y = torch.empty((N, Ho, Wo, C), dtype=dtype, device=x.device)
     idx = torch.empty((N, Ho, Wo, C), dtype=torch.uint8, device=x.device)
-    lib().bn_relu_maxpool3x3s2_fwd_bf16out(_p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
+    _fn("bn_relu_maxpool3x3s2_fwd_bf16out", dtype)(_p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
     return y, idx
 
 
@@ -596,7 +611,7 @@ def bn_bwd_maxpool_bf16in(dpool, idx, x, mean, invstd, gamma_ptr, beta_ptr, dgam
     _chk(x)
     _chk16(dpool, N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C)
     dx = torch.empty_like(x)
-    lib().bn_bwd_maxpool_bf16in(_p(dpool), _p(idx), _p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
+    _fn("bn_bwd_maxpool_bf16in", dpool.dtype)(_p(dpool), _p(idx), _p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
                                 dbeta_ptr, N, H, W, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
     return dx
 
@@ -611,10 +626,10 @@ def bf16_stem_fwd(x16, w_ohwi_ptr, cin, ws: Workspace, stats=None, rm_ptr=0, rv_
     tensors: also the train-mode BatchNorm statistics of y (running statistics updated in place)"""
     N, H, W, C4 = x16.shape
     _chk16(x16)
-    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(lib().bf16_stem_workspace_bytes())
-    y = torch.empty((N, H // 2, W // 2, 64), dtype=BF16, device=x16.device)
+    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(_fn("bf16_stem_workspace_bytes", x16.dtype)())
+    y = torch.empty((N, H // 2, W // 2, 64), dtype=x16.dtype, device=x16.device)
     mean, invstd = stats if stats is not None else (None, None)
-    lib().bf16_stem_fwd(_p(x16), w_ohwi_ptr, cin, _p(y), N, H, W, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr,
+    _fn("bf16_stem_fwd", x16.dtype)(_p(x16), w_ohwi_ptr, cin, _p(y), N, H, W, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr,
                         ws.nbytes, _stream())
     return y
 
@@ -622,33 +637,33 @@ def bf16_stem_fwd(x16, w_ohwi_ptr, cin, ws: Workspace, stats=None, rm_ptr=0, rv_
 def bf16_stem_wgrad(x16, dy16, dw_ptr, cin, ws: Workspace, accumulate=False):
     N, H, W, C4 = x16.shape
     _chk16(x16)
-    _chk16(dy16, N, H // 2, W // 2, 64)
-    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(lib().bf16_stem_workspace_bytes())
-    lib().bf16_stem_wgrad(_p(x16), _p(dy16), dw_ptr, cin, N, H, W, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    _chk16(dy16, N, H // 2, W // 2, 64, dtype=x16.dtype)
+    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(_fn("bf16_stem_workspace_bytes", x16.dtype)())
+    _fn("bf16_stem_wgrad", x16.dtype)(_p(x16), _p(dy16), dw_ptr, cin, N, H, W, int(accumulate), ws.ptr, ws.nbytes, _stream())
 
 
 def bf16_stem_bn_relu_maxpool(x16, mean, invstd, gamma_ptr, beta_ptr):
     N, H, W, C = x16.shape
     _chk16(x16)
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
-    y = torch.empty((N, Ho, Wo, C), dtype=BF16, device=x16.device)
+    y = torch.empty((N, Ho, Wo, C), dtype=x16.dtype, device=x16.device)
     idx = torch.empty((N, Ho, Wo, C), dtype=torch.uint8, device=x16.device)
-    lib().bf16_stem_bn_relu_maxpool_fwd(_p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
+    _fn("bf16_stem_bn_relu_maxpool_fwd", x16.dtype)(_p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
     return y, idx
 
 
 def bf16_stem_bn_bwd_maxpool(dpool, idx, x16, mean, invstd, gamma_ptr, beta_ptr, dgamma_ptr, dbeta_ptr, ws: Workspace, accumulate=False):
     N, H, W, C = x16.shape
     _chk16(x16)
-    _chk16(dpool, N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C)
+    _chk16(dpool, N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C, dtype=x16.dtype)
     dx = torch.empty_like(x16)
-    lib().bf16_stem_bn_bwd_maxpool(_p(dpool), _p(idx), _p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
+    _fn("bf16_stem_bn_bwd_maxpool", x16.dtype)(_p(dpool), _p(idx), _p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
                                    dbeta_ptr, N, H, W, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
     return dx
 
 
 def _rows16(t, M, C):
-    assert t.dtype == BF16 and t.is_cuda and tuple(t.shape) == (M, C) and t.stride(1) == 1 and t.stride(0) % 8 == 0, \
+    assert t.dtype in (BF16, F16) and t.is_cuda and tuple(t.shape) == (M, C) and t.stride(1) == 1 and t.stride(0) % 8 == 0, \
         (t.dtype, tuple(t.shape), t.stride())
     return t.stride(0)
 
@@ -658,10 +673,10 @@ def attention_fwd_bf16(q, k, v, B, T, nh, ws: Workspace, drop_p=0.0, seed=0, see
     M, C = q.shape
     assert M == B * T
     ldq = _rows16(q, M, C)
-    assert _rows16(k, M, C) == ldq and _rows16(v, M, C) == ldq
-    o = torch.empty((M, C), dtype=BF16, device=q.device)
+    assert _rows16(k, M, C) == ldq and _rows16(v, M, C) == ldq and q.dtype == k.dtype == v.dtype
+    o = torch.empty((M, C), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, nh, T), dtype=F32, device=q.device)
-    lib().attention_fwd_bf16(_p(q), _p(k), _p(v), _p(o), _p(lse), B, T, nh, C // nh, ldq, C, float(drop_p), seed, seed_off,
+    _fn("attention_fwd_bf16", q.dtype)(_p(q), _p(k), _p(v), _p(o), _p(lse), B, T, nh, C // nh, ldq, C, float(drop_p), seed, seed_off,
                              ws.ptr, ws.nbytes, _stream())
     return o, lse
 
@@ -670,19 +685,19 @@ def attention_bwd_bf16io(q, k, v, o, d_o, lse, B, T, nh, ws: Workspace, drop_p=0
     """all-bf16 backward: q, k, v, o, d_o bf16 -> dq, dk, dv bf16 (`out`: three [B*T, C] bf16 views of one row stride)"""
     M, C = q.shape
     ldq = _rows16(q, M, C)
-    assert _rows16(k, M, C) == ldq and _rows16(v, M, C) == ldq
-    _chk16(o, M, C)
-    _chk16(d_o, M, C)
+    assert _rows16(k, M, C) == ldq and _rows16(v, M, C) == ldq and q.dtype == k.dtype == v.dtype
+    _chk16(o, M, C, dtype=q.dtype)
+    _chk16(d_o, M, C, dtype=q.dtype)
     _chk(lse, B, nh, T)
     assert ws.nbytes >= int(lib().attention_workspace_bytes(B, T, nh, C // nh, C)), "attention_bwd_bf16io needs the hand-over workspace"
     delta = torch.empty_like(lse)
     if out is None:
-        out = tuple(torch.empty((M, C), dtype=BF16, device=q.device) for _ in range(3))
+        out = tuple(torch.empty((M, C), dtype=q.dtype, device=q.device) for _ in range(3))
     dq, dk, dv = out
     for t in out:
-        assert t.dtype == BF16 and tuple(t.shape) == (M, C) and t.stride(1) == 1 and t.stride(0) % 4 == 0
+        assert t.dtype == q.dtype and tuple(t.shape) == (M, C) and t.stride(1) == 1 and t.stride(0) % 4 == 0
     ldd = dq.stride(0)
     assert dk.stride(0) == ldd and dv.stride(0) == ldd
-    lib().attention_bwd_bf16io(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, T, nh,
+    _fn("attention_bwd_bf16io", q.dtype)(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, T, nh,
                                C // nh, ldq, C, ldd, float(drop_p), seed, seed_off, ws.ptr, ws.nbytes, _stream())
     return dq, dk, dv

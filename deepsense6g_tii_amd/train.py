@@ -62,19 +62,84 @@ class FocalLoss(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
+class DynamicLossScaler:
+    """torch.amp.GradScaler's dynamic loss scaling for the fused step, entirely on the device (no host sync per step, the
+    step stays replayable from a captured graph): the focal loss's gradient is multiplied by the scale S, the gradient
+    arena is checked for non-finite values after backward (after the all-reduce under data parallelism), AdamW uses
+    g / S (and the clip coefficient of the UNSCALED norm) or skips the step, and S backs off / grows.  Needed for "f16"
+    storage, whose activation gradients leave fp16's range without it; usable in every mode.  Pass it to
+    FusedAdamW(..., loss_scaler=...)."""
+
+    def __init__(self, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        if not (init_scale > 0 and growth_factor >= 1.0 and 0.0 < backoff_factor <= 1.0 and growth_interval >= 1):
+            raise ValueError("DynamicLossScaler: init_scale > 0, growth_factor >= 1, 0 < backoff_factor <= 1, "
+                             "growth_interval >= 1")
+        self.init_scale = float(init_scale)
+        self.growth_factor = float(growth_factor)
+        self.backoff_factor = float(backoff_factor)
+        self.growth_interval = int(growth_interval)
+        self.state = None   # device block {scale, clean steps, found_inf, AdamW coefficient, unscaled norm, pad}
+        self._ws = None
+
+    def bind(self, device, n):
+        """allocate the device state for a gradient arena of n floats (FusedAdamW does this)"""
+        if self.state is None:
+            nb = int(lib().loss_scaler_state_bytes())
+            self.state = torch.zeros(nb // 4, dtype=F32, device=device)
+            self.state[0:1].fill_(self.init_scale)
+        self._ws = torch.zeros(int(lib().loss_scale_check_workspace_bytes(n)), dtype=torch.uint8, device=device)
+        return self
+
+    def scale(self, loss):
+        """loss * S for the autograd-boundary path (loss.backward() through _FusionFn)"""
+        return loss * self.state[0]
+
+    def get_scale(self):
+        return float(self.state[0].item())
+
+    def found_inf(self):
+        """the last check saw a non-finite gradient (its step was skipped); host read: synchronises"""
+        return bool(self.state.view(torch.int32)[2].item())
+
+    def state_dict(self):
+        return dict(scale=self.get_scale(), growth_tracker=int(self.state.view(torch.int32)[1].item()),
+                    growth_factor=self.growth_factor, backoff_factor=self.backoff_factor,
+                    growth_interval=self.growth_interval)
+
+    def load_state_dict(self, sd):
+        self.growth_factor = float(sd.get("growth_factor", self.growth_factor))
+        self.backoff_factor = float(sd.get("backoff_factor", self.backoff_factor))
+        self.growth_interval = int(sd.get("growth_interval", self.growth_interval))
+        self.state[0:1].fill_(float(sd["scale"]))
+        self.state.view(torch.int32)[1:3].fill_(0)
+        self.state.view(torch.int32)[1:2].fill_(int(sd.get("growth_tracker", 0)))
+
+    # the per-step device work (FusedAdamW.step)
+    def _check_and_update(self, g, max_norm, pre_scale, adam_state, betas):
+        st = ops._stream()
+        lib().loss_scale_check(g.data_ptr(), g.numel(), float(max_norm or 0.0), float(pre_scale), self.state.data_ptr(),
+                               self._ws.data_ptr(), self._ws.numel(), st)
+        lib().loss_scale_update(self.state.data_ptr(), adam_state.data_ptr(), betas[0], betas[1], self.backoff_factor,
+                                self.growth_factor, self.growth_interval, st)
+
+
+# ------------------------------------------------------------------------------------------------
 class FusedAdamW:
     """torch.optim.AdamW(model.parameters(), lr) semantics (train2_seq.py:539: betas (.9,.999), eps 1e-8,
     weight_decay .01 on every parameter) as ONE streaming kernel over the parameter arena, optionally
     fused with the EMA shadow update (train2_seq.py:315-320)."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, ema_decay=None,
-                 max_grad_norm=None):
+                 max_grad_norm=None, loss_scaler: DynamicLossScaler | None = None):
         """max_grad_norm: torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) of the 30->5 training step
         (train2_seq_30to5.py:120, max_norm 3.0) folded into the step: one reduction over the gradient arena, the clip
         coefficient stays on the device and is multiplied into the AdamW kernel's gradient scale (no host sync, the
-        arena is not rewritten)."""
+        arena is not rewritten).  loss_scaler: a DynamicLossScaler - train_iteration / CapturedTrainStep scale the loss
+        gradient by it, step() unscales, skips non-finite steps and updates the scale (all on the device); the clip then
+        acts on the unscaled norm.  state_dict()["step"] counts APPLIED steps."""
         self.model = model
         self.max_grad_norm = max_grad_norm
+        self.loss_scaler = loss_scaler
         self._clip_out = torch.zeros(2, dtype=F32, device=model.device)           # [total norm, clip coefficient]
         self._clip_ws = torch.zeros(8 + 8 * 1024, dtype=torch.uint8, device=model.device)
         # per-step scalars in device memory {lr, bc1, bc2_sqrt, step}: the step is hipGraph-replayable (CapturedTrainStep)
@@ -83,6 +148,8 @@ class FusedAdamW:
         p, g = model.flat_parameters()
         self.m = torch.zeros_like(p)
         self.v = torch.zeros_like(p)
+        if loss_scaler is not None:
+            loss_scaler.bind(model.device, p.numel())
         self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
         self.step_count = 0
         self.ema_decay = ema_decay
@@ -107,6 +174,8 @@ class FusedAdamW:
         model = model or self.model
         if self.max_grad_norm is not None:
             raise RuntimeError("enable_overlap(): a global-norm clip needs the whole gradient before the first update")
+        if self.loss_scaler is not None:
+            raise RuntimeError("enable_overlap(): the loss scaler's skip decision needs the whole gradient before the first update")
         red = getattr(model.grad_ready_hook, "__self__", None) if model.grad_ready_hook is not None else None
         if red is None:   # single process: the reducer is only the bucketing engine (no collective at world size 1)
             red = ddist.GradReducer(model.flat_parameters()[1], None, min_bucket_elems, flush_at=7)
@@ -175,6 +244,20 @@ class FusedAdamW:
                 self._update_range(self._applied, p.numel())
             self._applied, self._began = 0, False
             return
+        if self.loss_scaler is not None:
+            # check (found_inf, unscaled norm, coefficient) -> scale update + AdamW state advance unless found_inf -> AdamW
+            # with the device skip flag; step_count mirrors iterations, the device step counts applied steps
+            self.step_count += 1
+            self.sync_lr()
+            grp = self.param_groups[0]
+            self.loss_scaler._check_and_update(g, self.max_grad_norm, self.grad_scale, self._dev, grp["betas"])
+            sc = self.loss_scaler.state
+            lib().adamw_step_scaled(p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                    0 if self.shadow is None else self.shadow.data_ptr(), p.numel(), self._dev.data_ptr(),
+                                    sc.data_ptr(), grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"],
+                                    0.0 if self.ema_decay is None else float(self.ema_decay), float(self.grad_scale),
+                                    ops._stream())
+            return
         self._advance_state()
         coef = 0
         if self.max_grad_norm is not None:
@@ -191,16 +274,29 @@ class FusedAdamW:
             self._dev_lr = lr
 
     def last_grad_norm(self):
-        """total gradient norm of the last clipped step (host read: synchronises)"""
+        """total gradient norm of the last clipped step (under a loss scaler: the unscaled norm of the last step, inf when
+        it was skipped; host read: synchronises)"""
+        if self.loss_scaler is not None:
+            return float(self.loss_scaler.state[4].item())
         return float(self._clip_out[0].item())
 
+    def applied_steps(self):
+        """AdamW steps applied (the device count: a loss scaler's skipped steps are not counted; host read)"""
+        return int(self._dev.view(torch.int32)[3].item())
+
     def state_dict(self):
-        return dict(m=self.m, v=self.v, step=self.step_count, shadow=self.shadow, param_groups=self.param_groups,
-                    dropout_rng=self.model.rng_state())
+        sd = dict(m=self.m, v=self.v, step=self.step_count, shadow=self.shadow, param_groups=self.param_groups,
+                  dropout_rng=self.model.rng_state())
+        if self.loss_scaler is not None:
+            sd["step"] = self.applied_steps()
+            sd["loss_scaler"] = self.loss_scaler.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
+        if self.loss_scaler is not None and sd.get("loss_scaler") is not None:
+            self.loss_scaler.load_state_dict(sd["loss_scaler"])
         self.step_count = int(sd["step"])
         self._dev.view(torch.int32)[3:4].fill_(self.step_count)
         if self.shadow is not None and sd.get("shadow") is not None:
@@ -428,6 +524,8 @@ class CapturedTrainStep:
         # running statistics + num_batches_tracked, the optimizer's device scalars / step count and the dropout salt
         with torch.cuda.stream(side):
             snap_t = [model.flat_parameters()[0], optimizer.m, optimizer.v, optimizer._dev, model._nbt]
+            if getattr(optimizer, "loss_scaler", None) is not None:
+                snap_t.append(optimizer.loss_scaler.state)
             if optimizer.shadow is not None:
                 snap_t.append(optimizer.shadow)
             if ema is not None and ema.shadow is not None and ema.shadow is not optimizer.shadow:
@@ -482,7 +580,8 @@ def train_iteration(model, optimizer, batch, ema=None, reducer=None):
     fronts, lidars, radars, gps, target = batch
     if reducer is not None:
         reducer.begin()
-    loss, logits = model.train_step_loss(fronts, lidars, radars, gps, target)
+    loss, logits = model.train_step_loss(fronts, lidars, radars, gps, target,
+                                         loss_scaler=getattr(optimizer, "loss_scaler", None))
     if reducer is not None:
         reducer.finish()
     optimizer.step()

@@ -54,7 +54,11 @@ int ds6g_debug_occupy_cus(int workgroups, int lds_bytes, int microseconds, void*
  *                       product error <= ~2^-16 (between fp32 and TF32), fp32 storage.
  *   3           "f32x6" three-way truncating split (a == hi + mid + lo exactly), the six products above 2^-24 summed
  *                       smallest first: fp32-grade products on the bf16 matrix cores, fp32 storage; the 3x3 / stride-1
- *                       convs keep the fp32 Winograd kernels. */
+ *                       convs keep the fp32 Winograd kernels.
+ *   4                   unused (refused).
+ *   5           "f16"   f16 storage: the host routes the same convs / linears / attention / BN / LN / pooling as in "bf16" to
+ *                       the f16-storage twins (ds6g_f16_*, *_f16*); every fp32-storage kernel runs exactly as in mode 0
+ *                       (their operand mode stays 0), so eval, the small linears and the fp32 stems are exact fp32. */
 int ds6g_set_compute_mode(int mode);
 int ds6g_get_compute_mode(void);
 
@@ -385,8 +389,108 @@ int ds6g_adamw_step_dev(float* p, const float* g, float* m, float* v, float* sha
  * order: deterministic).  ws: >= 8 KiB + 8 bytes, its first 4 bytes zero on first use. */
 int ds6g_grad_norm_clip(const float* g, long n, float max_norm, float pre_scale, float* out, void* ws, size_t ws_bytes,
                         void* stream);
+/* Dynamic loss scaling (train.DynamicLossScaler; torch.amp.GradScaler semantics, all of it on the device: no host sync, graph-
+ * replayable).  scaler_state: ds6g_loss_scaler_state_bytes() of device memory {float scale, int clean_steps, int found_inf,
+ * float adamw_coef, float unscaled_norm, 3 x pad} - the host writes the initial scale and zeros.  Per step:
+ *   ds6g_focal_loss_scaled    the focal loss with dlogits multiplied by the scale (the reported loss stays unscaled);
+ *   ds6g_loss_scale_check     one deterministic reduction over the (scaled, rank-summed) gradient arena: found_inf when any
+ *                             element is non-finite, the unscaled norm (* pre_scale) and the AdamW coefficient
+ *                             1/scale * min(1, max_norm / (norm + 1e-6)) (no clip when max_norm <= 0);
+ *   ds6g_loss_scale_update    one thread: found_inf -> scale *= backoff, clean_steps = 0, the AdamW state is NOT advanced;
+ *                             else the AdamW state advances (ds6g_adamw_state_advance) and every growth_interval clean steps
+ *                             scale *= growth;
+ *   ds6g_adamw_step_scaled    ds6g_adamw_step_dev with the coefficient / skip flag of scaler_state: a skipped step leaves
+ *                             p, m, v untouched and still updates the EMA shadow from the unchanged p.
+ * ws of the check: >= ds6g_loss_scale_check_workspace_bytes(n), first 4 bytes zero on first use (left zero). */
+size_t ds6g_loss_scaler_state_bytes(void);
+size_t ds6g_loss_scale_check_workspace_bytes(long n);
+int ds6g_focal_loss_scaled(const float* logits, const float* target, float* loss, float* dlogits, int n, float alpha,
+                           float gamma, const void* scaler_state, void* stream);
+int ds6g_loss_scale_check(const float* g, long n, float max_norm, float pre_scale, void* scaler_state, void* ws,
+                          size_t ws_bytes, void* stream);
+int ds6g_loss_scale_update(void* scaler_state, void* adam_state, float beta1, float beta2, float backoff, float growth,
+                           int growth_interval, void* stream);
+int ds6g_adamw_step_scaled(float* p, const float* g, float* m, float* v, float* shadow, long n, const void* state,
+                           const void* scaler_state, float beta1, float beta2, float eps, float wd, float ema_decay,
+                           float grad_scale, void* stream);
 /* dst (bf16, RNE) = src (fp32): refreshes the bf16 shadow of the parameter arena for the bf16-storage path */
 int ds6g_cast_f32_bf16(const float* src, void* dst, long n, void* stream);
+/* ---- f16-STORAGE twins (compute mode 5, "f16"): the same kernels as the bf16-storage entry points above - same signatures,
+ * arguments and layouts - with every 16-bit tensor (activations, their gradients, the weight shadow, the attention P / dS
+ * hand-over tiles) stored as IEEE half and fed to v_mfma_f32_32x32x16_f16; accumulation, statistics, master weights and
+ * gradients stay fp32.  Values are rounded to nearest even; a value beyond 65504 becomes +-inf (never clamped: the
+ * dynamic loss scaler below finds it in the fp32 gradient arena and skips the step).  ds6g_bn_bwd_maxpool_f16in / ds6g_bn_relu_maxpool3x3s2_fwd_f16out are
+ * the twins of the *_bf16in / *_bf16out stem kernels, ds6g_cast_f32_f16 of ds6g_cast_f32_bf16. */
+int ds6g_f16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R,
+                        int S, int stride, int pad, void* stream);
+int ds6g_f16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
+                                int stride, int pad, float eps, float momentum, float* mean, float* invstd,
+                                float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
+size_t ds6g_f16_conv_bnstats_workspace_bytes(long M, int K);
+int ds6g_f16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R,
+                          int S, int stride, int pad, int accumulate, void* stream);
+int ds6g_f16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
+                          int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream);
+int ds6g_f16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K,
+                        int relu, const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
+int ds6g_f16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
+                          int mask16, int accumulate, void* stream);
+int ds6g_f16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
+                          float* ws, size_t ws_bytes, void* stream);
+size_t ds6g_f16_stem_workspace_bytes(void);
+int ds6g_f16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
+                      float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
+                      void* stream);
+int ds6g_f16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate,
+                        void* ws, size_t ws_bytes, void* stream);
+int ds6g_f16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd,
+                      float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
+int ds6g_f16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                      const void* residual, void* y, long M, int C, int relu, void* stream);
+int ds6g_f16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
+                    const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres,
+                    long M, int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream);
+int ds6g_bn_bwd_maxpool_f16in(const void* dpool, const uint8_t* idx, const float* x, const float* mean,
+                              const float* invstd, const float* gamma, const float* relu_beta, float* dx, float* dgamma,
+                              float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
+                              size_t ws_bytes, void* stream);
+int ds6g_f16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean,
+                                 const float* invstd, const float* gamma, const float* relu_beta, void* dx,
+                                 float* dgamma, float* dbeta, int N, int H, int W, int C, int accumulate_param_grads,
+                                 void* ws, size_t ws_bytes, void* stream);
+int ds6g_layernorm_fwd_f16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                              int M, int C, float eps, void* stream);
+int ds6g_layernorm_bwd_f16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
+                           const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
+                           int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off,
+                           void* ws, size_t ws_bytes, void* stream);
+int ds6g_pack_input_f16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
+                        int normalize_imagenet, void* stream);
+int ds6g_bn_relu_maxpool3x3s2_fwd_f16out(const float* x, const float* mean, const float* invstd, const float* gamma,
+                                         const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C,
+                                         void* stream);
+int ds6g_f16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
+                                      const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C,
+                                      void* stream);
+int ds6g_f16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
+                                int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed,
+                                uint64_t seed_off, void* stream);
+int ds6g_f16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
+                                int frames_per_sample, int mod_off, int T, void* stream);
+int ds6g_f16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C,
+                              int frames_per_sample, int mod_off, int T, void* stream);
+int ds6g_f16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
+                              int T, void* stream);
+int ds6g_f16_global_pool(const void* feat, float* pooled, int N, int C, void* stream);
+int ds6g_f16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream);
+int ds6g_attention_fwd_f16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh,
+                           int hd, int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                           size_t ws_bytes, void* stream);
+int ds6g_attention_bwd_f16io(const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                             const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd,
+                             int ld_qkv, int ld, int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                             size_t ws_bytes, void* stream);
+int ds6g_cast_f32_f16(const float* src, void* dst, long n, void* stream);
 /* vel_emb1..4 and the join MLP: model2_seq.py:422-425,518,536,555,574,863-869 */
 int ds6g_small_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K,
                           int rows_per_group, long group_stride, int relu, void* stream);
