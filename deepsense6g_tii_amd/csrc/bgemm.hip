@@ -77,12 +77,16 @@ struct BgemmParams {
     // train-mode BatchNorm that follows the conv - partial[tile_m][0][col], partial[tile_m][1][col] (fp64, the layout
     // bn_stats_finalize_kernel reads), so the separate statistics pass over the conv output is not needed
     double* bn_partial;
+    // FWD, EPI == 2 (inference conv, BN folded into b_src / bias): 16-bit residual [Mg][Ng] of the output's own type (nullable),
+    // added in fp32 before the one rounding; relu 1 = before that add, 2 = after it
+    const void* residual16;
 };
 
 __device__ __forceinline__ unsigned lds_off(const void* p) { return (unsigned)(unsigned long)(lds_void*)p; }
 
-// MODE / BM x BN tile / OUT16: bf16 output through LDS (else fp32, direct) / EPI: fused epilogue (bias, ReLU, mask,
-// dropout, residual, accumulate) instead of a plain store.
+// MODE / BM x BN tile / OUT16: bf16 output through LDS (else fp32, direct) / EPI: 1 = fused epilogue (bias, ReLU, mask,
+// dropout, residual, accumulate) instead of a plain store; 2 = the inference conv's epilogue (FWD, OUT16 only: bias, ReLU before
+// or after a 16-bit residual), a code of its own so that the training instantiations carry none of it.
 // What bounds the loop (round 4, -DDS6G_GEMM_CLOCKS + tools/gemm_clocks.py): a k-tile step of the 128 x 128 tile takes 2 800 -
 // 3 000 cycles for 2 x 512 cycles of MFMA per SIMD (two workgroups per CU): DMA issue 800 - 1 000 (8 pieces per wave), fragment
 // reads + MFMAs 1 100 - 1 200, DMA wait 550, barrier 330.  A 256 x 128 tile with 8 waves and THREE stages (two k-tiles in flight,
@@ -486,6 +490,54 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
         GCLK_END(g_bgemm_clk, g_bgemm_wg);
         return;
     }
+    if constexpr (EPI == 2) {
+        // inference conv: act(acc + bias [+ residual16]).  The tile leaves through wave-private LDS patches as the 16-bit output
+        // below does, but as FP32 (4 x PR x PC x 4 bytes = exactly the two staging buffers): the residual is read where a lane
+        // holds 8 consecutive columns of one row (one 16-byte load), added in fp32, and the sum is rounded ONCE
+        T16* outp = reinterpret_cast<T16*>(p.out);
+        const T16* res = reinterpret_cast<const T16*>(p.residual16);
+        constexpr int PR = WR, PC = BN / 2;
+        static_assert(4 * PR * PC * 4 <= 2 * STAGE, "fp32 output patches must fit the staging buffers");
+        float* patch = reinterpret_cast<float*>(lds) + wave * PR * PC;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int dr = (r & 3) + 8 * (r >> 2);
+                    float v = acc[i][j][r] + bias_pre[j];
+                    if (p.relu == 1) v = fmaxf(v, 0.f);
+                    patch[(i * 32 + 4 * khalf + dr) * PC + j * 32 + l31] = v;
+                }
+            }
+        }
+        constexpr int PPR = PC / 8;  // 8-column pieces per patch row
+#pragma unroll
+        for (int t = 0; t < PR * PPR / 64; ++t) {
+            const int idx = t * 64 + lane;
+            const int rl = idx / PPR, pc = idx - rl * PPR;
+            const int grow = m0 + wm * PR + rl, gcol = n0 + wn * PC + pc * 8;
+            if (grow < p.Mg && gcol < p.Ng) {   // Ng % 8 == 0: the piece lies inside the row
+                const float* src = patch + rl * PC + pc * 8;
+                const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
+                float f[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const size_t e = (size_t)grow * p.Ng + gcol;
+                if (res) {
+                    const h8 rv = *reinterpret_cast<const h8*>(res + e);
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) f[q] += (float)rv[q];
+                }
+                h8 v;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) v[q] = (T16)(p.relu == 2 ? fmaxf(f[q], 0.f) : f[q]);
+                *reinterpret_cast<h8*>(outp + e) = v;
+            }
+        }
+        GCLK(g_bgemm_clk, 6);
+        GCLK_END(g_bgemm_clk, g_bgemm_wg);
+        return;
+    }
     // bf16 output: epilogue arithmetic in fp32 on the accumulators, one rounding, then through a wave-private LDS patch
     // [BM/2 rows][BN/2 cols] so that global stores are 16-byte row pieces (the loop's last barrier has been passed by
     // every wave: the staging buffers are free)
@@ -771,6 +823,38 @@ int ds6g_f16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, in
                                 float* running_var, void* ws, size_t ws_bytes, void* stream) {
     return h16_conv2d_fwd_bnstats<_Float16>(x, w, y, N, H, W, C, K, R, S, stride, pad, eps, momentum, mean, invstd,
                                             running_mean, running_var, ws, ws_bytes, stream);
+}
+
+// inference form of Conv2d + eval-mode BatchNorm2d (+ identity) (+ ReLU) on 16-bit storage: the BN is folded into w (16-bit,
+// ds6g_bn_fold_bf16 / _f16) and bias (fp32); y = act(conv(x, w) + bias [+ residual]), relu 0 none / 1 before / 2 after the
+// residual add - the contract of ds6g_conv2d_bias_act_fwd.  x, w, residual, y 16-bit; accumulation, bias and the residual add
+// fp32, one rounding.  C % 64 == 0, K % 8 == 0.
+extern "C++" template <typename T16>
+static int h16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H,
+                                   int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(x && w && bias && y && C % BK == 0 && K % 8 == 0 && N > 0 && relu >= 0 && relu <= 2);
+    BgemmParams p;
+    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
+    DS6G_CHECK_ARG(p.Ho > 0 && p.Wo > 0 && sizes_ok(p));
+    p.a_src = (const __bf16*)x; p.b_src = (const __bf16*)w; p.out = y;
+    p.bias = bias; p.residual16 = residual; p.relu = relu;
+    p.a_bytes = (unsigned)((size_t)N * H * W * C * 2); p.b_bytes = (unsigned)((size_t)K * R * S * C * 2);
+    p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
+    DS6G_CHECK_ARG((size_t)p.Mg * p.Ng * 4 < OOB_OFF);
+    const int tile = pick_tile(p.Mg, p.Ng, 1);
+    void* rec = ds6g_prof_open(30200 + tile, 2.0 * p.Mg * p.Ng * p.Kg, (hipStream_t)stream);
+    const int rc = launch_tiles<B_FWD, 1, 2, T16>(p, 1, tile, (hipStream_t)stream);
+    ds6g_prof_close(rec, (hipStream_t)stream);
+    return rc;
+}
+int ds6g_bf16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H,
+                                  int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
+    return h16_conv2d_bias_act_fwd<__bf16>(x, w, bias, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream);
+}
+int ds6g_f16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H,
+                                 int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
+    return h16_conv2d_bias_act_fwd<_Float16>(x, w, bias, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream);
 }
 
 size_t ds6g_bf16_conv_bnstats_workspace_bytes(long M, int K) { return (size_t)cdiv(M, 64) * 2 * K * sizeof(double); }

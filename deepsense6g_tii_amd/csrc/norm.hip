@@ -441,9 +441,12 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
 
 // eval-mode BatchNorm folded into the preceding convolution: w_out[o][j] = w[o][j] * g[o] / sqrt(var[o] + eps),
 // bias_out[o] = b[o] - mean[o] * g[o] / sqrt(var[o] + eps).  cin < cout_pad zero-pads each tap (stem: 3/1/2 -> 4 ch).
+// TW: storage type of w_out - float, or __bf16 / _Float16 (the frozen inference engine's filters): the same fp32 product,
+// rounded once (nearest even) on the store; the bias stays fp32.
+template <typename TW>
 __global__ __launch_bounds__(256) void bn_fold_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, const float* __restrict__ mean,
-                                                      const float* __restrict__ var, float eps, float* __restrict__ w_out,
+                                                      const float* __restrict__ var, float eps, TW* __restrict__ w_out,
                                                       float* __restrict__ bias_out, int K, int taps, int cin, int cpad) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long per_o = (long)taps * cpad;
@@ -452,7 +455,12 @@ __global__ __launch_bounds__(256) void bn_fold_kernel(const float* __restrict__ 
     const int rem = (int)(i - (long)o * per_o);
     const int tap = rem / cpad, c = rem - tap * cpad;
     const float scale = gamma[o] / sqrtf(var[o] + eps);
-    w_out[i] = c < cin ? w[((long)o * taps + tap) * cin + c] * scale : 0.f;
+    float v = c < cin ? w[((long)o * taps + tap) * cin + c] * scale : 0.f;
+    // 16-bit store: the product is first rounded to fp32 (what ds6g_bn_fold stores), then once more to TW.  Without the
+    // barrier the compiler contracts multiply + conversion into one mixed-precision instruction (v_fma_mixlo_f16) that rounds
+    // the exact product straight to f16, which differs from the rounded fp32 fold in the double-rounding cases
+    if constexpr (sizeof(TW) == 2) asm volatile("" : "+v"(v));
+    w_out[i] = (TW)v;
     if (rem == 0) bias_out[o] = beta[o] - mean[o] * scale;
 }
 
@@ -828,17 +836,36 @@ int ds6g_colsum(const float* x, long M, int C, float* out, int accumulate, void*
     return DS6G_OK;
 }
 
-int ds6g_bn_fold(const float* w, const float* gamma, const float* beta, const float* running_mean,
-                 const float* running_var, float eps, float* w_out, float* bias_out, int K, int taps, int cin, int cpad,
-                 void* stream) {
+extern "C++" template <typename TW>
+static int bn_fold_run(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, float eps, TW* w_out, float* bias_out, int K, int taps, int cin, int cpad,
+                       void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(w && gamma && beta && running_mean && running_var && w_out && bias_out && K > 0 && taps > 0 &&
                    cin > 0 && cpad >= cin);
     const long n = (long)K * taps * cpad;
-    hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, gamma, beta,
+    hipLaunchKernelGGL(bn_fold_kernel<TW>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, gamma, beta,
                        running_mean, running_var, eps, w_out, bias_out, K, taps, cin, cpad);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
+}
+int ds6g_bn_fold(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                 const float* running_var, float eps, float* w_out, float* bias_out, int K, int taps, int cin, int cpad,
+                 void* stream) {
+    return bn_fold_run<float>(w, gamma, beta, running_mean, running_var, eps, w_out, bias_out, K, taps, cin, cpad, stream);
+}
+// the same fold with a 16-bit w_out (one rounding of the fp32 product) and an fp32 bias_out
+int ds6g_bn_fold_bf16(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                      const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin, int cpad,
+                      void* stream) {
+    return bn_fold_run<__bf16>(w, gamma, beta, running_mean, running_var, eps, (__bf16*)w_out, bias_out, K, taps, cin, cpad,
+                               stream);
+}
+int ds6g_bn_fold_f16(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                     const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin, int cpad,
+                     void* stream) {
+    return bn_fold_run<_Float16>(w, gamma, beta, running_mean, running_var, eps, (_Float16*)w_out, bias_out, K, taps, cin, cpad,
+                                 stream);
 }
 
 }  // extern "C"

@@ -108,6 +108,44 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const TX* __restrict__
     *reinterpret_cast<uint32_t*>(idx + o) = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24);
 }
 
+// inference: 3x3 / 2 max-pool of a 16-bit map (the stem's relu(conv + bias)), 8 channels = one 16-byte piece per thread, no
+// arg-max index (nothing differentiates through it).  max commutes with the monotonic rounding: pooling the rounded values
+// equals rounding the pooled ones.  NaN propagates as in maxpool_fwd_kernel.
+template <typename T16>
+__global__ __launch_bounds__(256) void maxpool16_fwd_kernel(const T16* __restrict__ x, T16* __restrict__ y, int N, int H, int W,
+                                                            int C, int Ho, int Wo) {
+    typedef typename H16<T16>::x8 h8;
+    const int cg = C >> 3;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)N * Ho * Wo * cg) return;
+    const int c8 = (int)(i % cg) * 8;
+    long t = i / cg;
+    const int ow = (int)(t % Wo); t /= Wo;
+    const int oh = (int)(t % Ho);
+    const int n = (int)(t / Ho);
+    float best[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) best[j] = -INFINITY;
+    for (int r = 0; r < 3; ++r) {
+        const int ih = oh * 2 - 1 + r;
+        if (ih < 0 || ih >= H) continue;
+        for (int s = 0; s < 3; ++s) {
+            const int iw = ow * 2 - 1 + s;
+            if (iw < 0 || iw >= W) continue;
+            const h8 v = *reinterpret_cast<const h8*>(x + (((long)n * H + ih) * W + iw) * C + c8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float f = (float)v[j];
+                if (f > best[j] || f != f) best[j] = f;
+            }
+        }
+    }
+    h8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (T16)best[j];
+    *reinterpret_cast<h8*>(y + (((long)n * Ho + oh) * Wo + ow) * C + c8) = o;
+}
+
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ dy,
                                                           const uint8_t* __restrict__ idx, float* __restrict__ dx,
                                                           int N, int H, int W, int C, int Ho, int Wo) {
@@ -676,6 +714,24 @@ int ds6g_bf16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const f
 int ds6g_f16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
                                       const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
     return h16_stem_bn_relu_maxpool_fwd<_Float16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
+}
+
+// index-free 3x3 / 2 / pad 1 max-pool of a 16-bit NHWC map (the inference stem: after ds6g_*_stem_bias_relu_fwd); C % 8 == 0
+extern "C++" template <typename T16>
+static int h16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(x && y && C % 8 == 0 && C > 0 && N > 0 && H > 0 && W > 0);
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    hipLaunchKernelGGL((maxpool16_fwd_kernel<T16>), dim3(grid1((long)N * Ho * Wo * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+                       (const T16*)x, (T16*)y, N, H, W, C, Ho, Wo);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+int ds6g_bf16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
+    return h16_maxpool3x3s2_fwd<__bf16>(x, y, N, H, W, C, stream);
+}
+int ds6g_f16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
+    return h16_maxpool3x3s2_fwd<_Float16>(x, y, N, H, W, C, stream);
 }
 
 extern "C++" template <typename T16>

@@ -47,6 +47,16 @@ __global__ __launch_bounds__(256) void stem_pack_weights_kernel(const float* __r
     w16[i] = (T16)v;
 }
 
+// the inference engine's filter: BN-folded and already rounded to 16 bits, [64][7][7][4] (ds6g_bn_fold_bf16 / _f16 with 4 padded
+// channels) -> the forward's [64][7][8][4] layout (tap s' = s + 1, tap 0 zero).  Pure data movement, done once per snapshot.
+template <typename T16>
+__global__ __launch_bounds__(256) void stem_pack_filter16_kernel(const T16* __restrict__ w, T16* __restrict__ w16) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= KO * WROW) return;
+    const int c = i & 3, sp = (i >> 2) & 7, r = (i >> 5) % 7, o = i / WROW;
+    w16[i] = sp >= 1 ? w[((o * 7 + r) * 7 + (sp - 1)) * 4 + c] : (T16)0.f;
+}
+
 struct StemParams {   // 16-bit tensors: __bf16 or _Float16 storage (the kernels' template argument)
     const __bf16* x;      // [N][H][W][4]
     const __bf16* w16;    // [64][7][8][4]
@@ -54,6 +64,7 @@ struct StemParams {   // 16-bit tensors: __bf16 or _Float16 storage (the kernels
     const __bf16* dy;     // [N][Ho][Wo][64]      (weight gradient)
     float* slabs;         // [grid][64][7][32]    (weight gradient)
     double* bn_partial;   // [grid][2][64]        (forward)
+    const float* bias;    // [64]                 (inference forward, EPI: y = relu(conv + bias))
     int N, H, W, Ho, Wo, tiles_x, tiles_y, ntiles;
     unsigned x_bytes, dy_bytes;
 };
@@ -91,7 +102,9 @@ __device__ __forceinline__ void tile_coords(const StemParams& p, int t, int& n, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T16>
+// EPI = 1: the inference form - y = relu(conv + bias) (BN folded into filter and bias), the bias added to the fp32 accumulator
+// before the one rounding, no BatchNorm statistics
+template <typename T16, int EPI = 0>
 __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
     typedef typename H16<T16>::x8 h8;
     __shared__ __attribute__((aligned(1024))) unsigned char patch[2][PATCH_BYTES];
@@ -116,7 +129,12 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
     const int oy_rel = 2 * wave + (l31 >> 4), ox = l31 & 15;
     const unsigned a_base = (unsigned)((2 * oy_rel * PP + ox + khalf) * 16);   // + (r * PP + 2 jj) * 16 per k-step
 
-    float cs[2] = {0.f, 0.f}, cq[2] = {0.f, 0.f};
+    [[maybe_unused]] float cs[2] = {0.f, 0.f}, cq[2] = {0.f, 0.f};
+    [[maybe_unused]] float bias[2] = {0.f, 0.f};
+    if constexpr (EPI != 0) {
+        bias[0] = p.bias[l31];
+        bias[1] = p.bias[32 + l31];
+    }
     int buf = 0;
     int t = blockIdx.x;
     if (t < p.ntiles) {
@@ -155,11 +173,15 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int px = (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                const T16 vb = (T16)acc[nt][r];
-                op[px * KO + nt * 32 + l31] = vb;
-                const float vr = (float)vb;
-                cs[nt] += vr;
-                cq[nt] += vr * vr;
+                if constexpr (EPI != 0) {
+                    op[px * KO + nt * 32 + l31] = (T16)fmaxf(acc[nt][r] + bias[nt], 0.f);
+                } else {
+                    const T16 vb = (T16)acc[nt][r];
+                    op[px * KO + nt * 32 + l31] = vb;
+                    const float vr = (float)vb;
+                    cs[nt] += vr;
+                    cq[nt] += vr * vr;
+                }
             }
         // rows of the output: pixel px of the wave = (row oy0 + 2 wave + (px >> 4), column ox0 + (px & 15)), 128 B each
         const int oy0 = ty * TH + 2 * wave, ox0 = tx * TW;
@@ -172,6 +194,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(const StemParams p) {
         }
         buf ^= 1;
     }
+    if constexpr (EPI != 0) return;
     // BatchNorm partial sums of this workgroup (all its tiles): lane halves, then the four waves
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
@@ -370,6 +393,43 @@ int ds6g_f16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, in
                       void* stream) {
     return h16_stem_fwd<_Float16>(x, w, cin, y, N, H, W, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
                                   stream);
+}
+
+// inference stem: the filter is prepared once per snapshot (ds6g_bn_fold_bf16 / _f16 with cpad = 4 -> w [64][7][7][4], then
+// ds6g_*_stem_pack_filter -> w_packed [64][7][8][4]); the forward is y = relu(conv7x7/2(x, w_packed) + bias), one launch, no
+// workspace.  x [N][H][W][4], y [N][H/2][W/2][64] 16-bit, bias fp32 [64]; H % 16 == 0, W % 32 == 0.
+extern "C++" template <typename T16>
+static int h16_stem_pack_filter(const void* w, void* w_packed, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(w && w_packed);
+    hipLaunchKernelGGL(stem_pack_filter16_kernel<T16>, dim3(cdiv(KO * WROW, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const T16*)w, (T16*)w_packed);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+int ds6g_bf16_stem_pack_filter(const void* w, void* w_packed, void* stream) { return h16_stem_pack_filter<__bf16>(w, w_packed, stream); }
+int ds6g_f16_stem_pack_filter(const void* w, void* w_packed, void* stream) { return h16_stem_pack_filter<_Float16>(w, w_packed, stream); }
+
+extern "C++" template <typename T16>
+static int h16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
+                                  void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(x && w_packed && bias && y);
+    StemParams p{};
+    DS6G_CHECK_ARG(stem_geometry(p, N, H, W) == DS6G_OK);
+    p.x = (const __bf16*)x; p.w16 = (const __bf16*)w_packed; p.y = (__bf16*)y; p.bias = bias;
+    const int grid = p.ntiles < STEM_GRID_FWD ? p.ntiles : STEM_GRID_FWD;
+    hipLaunchKernelGGL((stem_fwd_kernel<T16, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+int ds6g_bf16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
+                                 void* stream) {
+    return h16_stem_bias_relu_fwd<__bf16>(x, w_packed, bias, y, N, H, W, stream);
+}
+int ds6g_f16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
+                                void* stream) {
+    return h16_stem_bias_relu_fwd<_Float16>(x, w_packed, bias, y, N, H, W, stream);
 }
 
 // dw[64][7][7][cin] (+)= weight gradient of the same convolution from x [N][H][W][4] bf16 and dy [N][H/2][W/2][64] bf16

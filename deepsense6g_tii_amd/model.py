@@ -234,6 +234,33 @@ class _FusionFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
+def capture_forward(fwd, device, image_list, lidar_list, radar_list, gps):
+    """Captures ``fwd(image_list, lidar_list, radar_list, gps)`` (an inference forward: TransFuser.forward under eval(), or an
+    infer.InferenceEngine) for inputs of these shapes into ONE HIP graph over static input buffers ->
+    ``run(image_list, lidar_list, radar_list, gps)``: copy-in, one replay; the returned tensor is overwritten by the next."""
+    to_dev = lambda seq: [t.to(device, F32).contiguous().clone() for t in seq]  # noqa: E731
+    st_img, st_lid, st_rad = to_dev(image_list), to_dev(lidar_list), to_dev(radar_list)
+    st_gps = gps.to(device, F32).contiguous().clone()
+    cur = torch.cuda.current_stream()
+    warm = torch.cuda.Stream(device)
+    warm.wait_stream(cur)
+    with torch.cuda.stream(warm), torch.no_grad():  # lazy one-time work (side streams, scratch) outside the capture
+        for _ in range(2):
+            fwd(st_img, st_lid, st_rad, st_gps)
+    cur.wait_stream(warm)
+    graph = torch.cuda.CUDAGraph()
+    with torch.no_grad(), torch.cuda.graph(graph):
+        out = fwd(st_img, st_lid, st_rad, st_gps)
+
+    def run(image_list, lidar_list, radar_list, gps):
+        for dst, src in zip(st_img + st_lid + st_rad + [st_gps], list(image_list) + list(lidar_list) + list(radar_list) + [gps]):
+            dst.copy_(src, non_blocking=True)
+        graph.replay()
+        return out
+    run.graph = graph
+    return run
+
+
 class TransFuser(nn.Module):
     """Drop-in for model2_seq.TransFuser (GPT variant).  See module docstring."""
     _GRU_HEAD = False
@@ -288,6 +315,7 @@ class TransFuser(nn.Module):
         self._arena = None
         self._wfast = None     # parameter-pointer table of the walk in flight (see _run_forward)
         self._wtable = None
+        self._infer = None     # the infer.InferenceEngine whose snapshot the walk in flight reads (freeze_inference), else None
         if self.device.type == "cuda":
             lib()  # fail loudly now if the HIP library is missing
             self._build_arena()
@@ -487,6 +515,8 @@ class TransFuser(nn.Module):
 
     def _w16(self, p):
         """device pointer of parameter p inside the bf16 shadow of the parameter arena (same layout, 2-byte elements)"""
+        if self._infer is not None:   # a frozen 16-bit engine runs the walk: its own 16-bit copies
+            return self._infer.wtable16[id(p)]
         return self._arena16.data_ptr() + 2 * self._pslice[self._pname[id(p)]][0]
 
     def _refresh_shadow16(self):
@@ -619,30 +649,23 @@ class TransFuser(nn.Module):
         buffers and replays it.  A single-sample forward is launch-bound from Python (~600 kernel launches for ~3 ms of
         GPU work); replayed from the graph the host cost is one call.  The graph reads parameter memory at replay time
         (weights may keep training / be swapped by EMA between calls as long as they stay in the same storage); the
-        returned tensor is overwritten by the next replay."""
+        returned tensor is overwritten by the next replay.  This FOLLOWS the live weights; freeze_inference() is the
+        opposite: an engine that owns a snapshot of the weights (BN folded once, optionally stored as bf16 / f16) and
+        changes its output only at engine.refresh()."""
         if self.training:
             raise RuntimeError("capture_inference() needs model.eval()")
-        to_dev = lambda seq: [t.to(self.device, F32).contiguous().clone() for t in seq]  # noqa: E731
-        st_img, st_lid, st_rad = to_dev(image_list), to_dev(lidar_list), to_dev(radar_list)
-        st_gps = gps.to(self.device, F32).contiguous().clone()
-        cur = torch.cuda.current_stream()
-        warm = torch.cuda.Stream(self.device)
-        warm.wait_stream(cur)
-        with torch.cuda.stream(warm), torch.no_grad():  # lazy one-time work (side streams, scratch) outside the capture
-            for _ in range(2):
-                self.forward(st_img, st_lid, st_rad, st_gps)
-        cur.wait_stream(warm)
-        graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph):
-            out = self.forward(st_img, st_lid, st_rad, st_gps)
+        return capture_forward(self.forward, self.device, image_list, lidar_list, radar_list, gps)
 
-        def run(image_list, lidar_list, radar_list, gps):
-            for dst, src in zip(st_img + st_lid + st_rad + [st_gps], list(image_list) + list(lidar_list) + list(radar_list) + [gps]):
-                dst.copy_(src, non_blocking=True)
-            graph.replay()
-            return out
-        run.graph = graph
-        return run
+    def freeze_inference(self, storage="f32"):
+        """Deployable forward: -> infer.InferenceEngine, a SNAPSHOT of this model prepared once for inference - eval-mode
+        BatchNorm folded into every conv (and the Winograd filters transformed) at freeze time instead of on every call,
+        stored as fp32 ("f32": bit-identical to model.eval()) or as bf16 / f16 with 16-bit feature maps and GPT operands
+        ("bf16" / "f16", whatever ops.set_compute_mode says).  The engine copies what it needs (from wherever param.data
+        points now: an applied EMA shadow is honoured) into memory it owns and never reads this model's parameters or
+        buffers again until engine.refresh(); the model may go on training meanwhile.  capture_inference() is the
+        opposite contract (a graph that follows the live weights)."""
+        from .infer import InferenceEngine
+        return InferenceEngine(self, storage)
 
     def train_step_loss(self, image_list, lidar_list, radar_list, gps, target, alpha=0.25, gamma=2.0, loss_scaler=None):
         """Fused forward -> sigmoid focal loss -> backward without autograd (the harness path).  loss_scaler (a
@@ -689,9 +712,42 @@ class TransFuser(nn.Module):
                                                          residual)
         return y, (mean, invstd)
 
+    def _folded(self, conv, bn, K, taps, cin, cpad=None):
+        """(filter [K, taps, cpad], bias [K]) of `conv` with the eval-mode `bn` folded in: the frozen engine's prepared
+        pair when one runs this walk, else folded now from the live parameters"""
+        if self._infer is not None:
+            f = self._infer.folded[id(conv.weight)]
+            return f.w, f.b
+        return ops.bn_fold(self._w(conv.weight), bn, K, taps, cin, cpad)
+
+    def _stem_fwd_frozen16(self, trunk, cin, normalize, frames):
+        """the stem of a frozen 16-bit engine: packed 16-bit input -> relu(conv + bias), BN folded into the 16-bit filter
+        and the fp32 bias, the bias added before the one rounding -> index-free 16-bit max-pool"""
+        L = lib()
+        st = ops._stream()
+        dt = self._infer.dtype
+        if torch.is_tensor(frames):  # data.PackedInputs: fp32 NHWC x4, normalised
+            assert frames.dim() == 4 and frames.shape[3] == 4 and frames.dtype == F32 and frames.is_contiguous()
+            x16 = ops.cast_bf16(frames, dtype=dt)
+        else:
+            B, S = frames[0].shape[0], len(frames)
+            H, W = frames[0].shape[2:]
+            x16 = torch.empty((B * S, H, W, 4), dtype=dt, device=self.device)
+            pack = L.pack_input_bf16 if dt == BF16 else L.pack_input_f16
+            for t, f in enumerate(frames):
+                assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
+                pack(f.data_ptr(), x16.data_ptr(), B, cin, H, W, S, t, int(normalize), st)
+        if not ops.bf16_stem_ok(*x16.shape[1:3]):
+            raise RuntimeError(f"the 16-bit inference stem needs H % 16 == 0 and W % 32 == 0, got {tuple(x16.shape[1:3])}")
+        f = self._infer.folded[id(trunk.conv1.weight)]
+        a1 = ops.bf16_stem_bias_relu_fwd(x16, f.wp, f.b)
+        return ops.bf16_maxpool3x3s2_fwd(a1), None
+
     def _stem_fwd(self, trunk, cin, normalize, frames, train):
         L = lib()
         st = ops._stream()
+        if self._infer is not None and self._infer.dtype in _H16:
+            return self._stem_fwd_frozen16(trunk, cin, normalize, frames)
         if (self._use16 and self.bf16_stems and not self._fold_now and not torch.is_tensor(frames)
                 and ops.bf16_stem_ok(*frames[0].shape[2:])):
             # bf16 configuration: the stem too on bf16 storage (csrc/stem.hip) - packed input, conv output and its gradient
@@ -725,7 +781,7 @@ class TransFuser(nn.Module):
                 assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
                 L.pack_input(f.data_ptr(), x.data_ptr(), B, cin, H, W, 4, S, t, int(normalize), st)
         if self._fold_now:
-            wf, bf = ops.bn_fold(self._w(trunk.conv1.weight), trunk.bn1, 64, 49, cin, 4)  # folds and pads to 4 channels
+            wf, bf = self._folded(trunk.conv1, trunk.bn1, 64, 49, cin, 4)  # folds and pads to 4 channels
             c1, st1 = None, None
             a1 = ops.conv2d_bias_act_fwd(x, wf.data_ptr(), bf.data_ptr(), 64, 7, 7, 2, 3, relu=1)
         else:
@@ -789,12 +845,24 @@ class TransFuser(nn.Module):
             # inference: eval-mode BN is an affine map per channel - folded into the conv weights, the block is three
             # (two) convolutions with bias / ReLU / identity epilogues and no BN pass at all
             Cin = x.shape[-1]
+            eng = self._infer
+            if x.dtype in _H16:
+                # frozen 16-bit engine: the same three (two) convolutions on 16-bit maps, filters and fp32 biases from the
+                # snapshot, bias / residual / ReLU in the conv's own epilogue (csrc/bgemm.hip, EPI 2)
+                def conv16(inp, conv, R, stride, relu, residual=None):
+                    f = eng.folded[id(conv.weight)]
+                    return ops.bf16_conv2d_bias_act_fwd(inp, f.w.data_ptr(), f.b.data_ptr(), K, R, R, stride, R // 2,
+                                                        relu=relu, residual=residual)
+                a1 = conv16(x, blk.conv1, 3, blk.stride, 1)
+                idn = x if blk.downsample is None else conv16(x, blk.downsample[0], 1, blk.stride, 0)
+                return conv16(a1, blk.conv2, 3, 1, 2, residual=idn), None
 
             def conv3(inp, conv, bn, stride, relu, residual=None):
                 C = inp.shape[-1]
-                wf, bf = ops.bn_fold(self._w(conv.weight), bn, K, 9, C)
+                wf, bf = self._folded(conv, bn, K, 9, C)
                 if stride == 1 and self.use_winograd and ops.winograd_ok(inp.shape, K):
-                    u = ops.winograd_weights(wf.data_ptr(), K, C, self.device)
+                    u = (eng.folded[id(conv.weight)].u if eng is not None
+                         else ops.winograd_weights(wf.data_ptr(), K, C, self.device))
                     return ops.conv3x3_winograd_bias_act(inp, u, bf.data_ptr(), K, relu=relu, residual=residual)
                 return ops.conv2d_bias_act_fwd(inp, wf.data_ptr(), bf.data_ptr(), K, 3, 3, stride, 1, relu=relu,
                                                residual=residual)
@@ -802,7 +870,7 @@ class TransFuser(nn.Module):
             a1 = conv3(x, blk.conv1, blk.bn1, blk.stride, 1)
             idn = x
             if blk.downsample is not None:
-                wd, bd = ops.bn_fold(self._w(blk.downsample[0].weight), blk.downsample[1], K, 1, Cin)
+                wd, bd = self._folded(blk.downsample[0], blk.downsample[1], K, 1, Cin)
                 idn = ops.conv2d_bias_act_fwd(x, wd.data_ptr(), bd.data_ptr(), K, 1, 1, blk.stride, 0, relu=0)
             out = conv3(a1, blk.conv2, blk.bn2, 1, 2, residual=idn)
             return out, None
@@ -941,12 +1009,18 @@ class TransFuser(nn.Module):
         L = lib()
         st = ops._stream()
         cfg = self.config
-        train = self.training
-        self._fold_now = self.fold_bn_eval and not train and not record  # inference only: backward needs the BN tape
+        eng = self._infer
+        train = self.training and eng is None   # a frozen engine is always the eval-mode forward
+        self._fold_now = (self.fold_bn_eval and not train and not record) or eng is not None  # inference only: backward needs the BN tape
         self._recording = bool(record)
-        self._refresh_shadow16()
-        if self._fold_now:
-            self._use16 = False   # folded inference convs read the fp32 weights (BN folded per call)
+        if eng is not None:   # storage is the engine's, whatever the process-wide compute mode says
+            self._use16 = eng.dtype in _H16
+            if self._use16:
+                self._dt16 = eng.dtype
+        else:
+            self._refresh_shadow16()
+            if self._fold_now:
+                self._use16 = False   # folded inference convs read the fp32 weights (BN folded per call)
         S = cfg.seq_len
         if torch.is_tensor(lidars):
             B = lidars.shape[0] // S

@@ -104,14 +104,24 @@ def conv2d_bias_act_fwd(x, w_ohwi_ptr, bias_ptr, K, R, S, stride, pad, relu=0, r
     return y
 
 
-def bn_fold(w_ohwi_ptr, bn, K, taps, cin, cpad=None):
-    """-> (w_folded [K, taps, cpad], bias [K]) of an eval-mode BatchNorm2d folded into the preceding conv"""
+def bn_fold(w_ohwi_ptr, bn, K, taps, cin, cpad=None, dtype=F32, out=None):
+    """-> (w_folded [K, taps, cpad], bias [K]) of an eval-mode BatchNorm2d folded into the preceding conv.  dtype bf16 / f16:
+    the folded filter is stored in that type (scaled in fp32, rounded once; the bias stays fp32).  out = (w_folded, bias):
+    written in place (the frozen inference engine refreshes its snapshot into the same buffers)"""
     cpad = cin if cpad is None else cpad
     dev = bn.weight.device
-    w_out = torch.empty((K, taps, cpad), dtype=F32, device=dev)
-    b_out = torch.empty((K,), dtype=F32, device=dev)
-    lib().bn_fold(w_ohwi_ptr, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                  bn.running_var.data_ptr(), float(bn.eps), w_out.data_ptr(), b_out.data_ptr(), K, taps, cin, cpad, _stream())
+    if out is not None:
+        w_out, b_out = out
+        dtype = w_out.dtype
+        assert w_out.is_cuda and w_out.is_contiguous() and w_out.numel() == K * taps * cpad, (tuple(w_out.shape), K, taps, cpad)
+        _chk(b_out, K)
+    else:
+        w_out = torch.empty((K, taps, cpad), dtype=dtype, device=dev)
+        b_out = torch.empty((K,), dtype=F32, device=dev)
+    assert dtype in (F32, BF16, F16), dtype
+    fold = lib().bn_fold if dtype == F32 else _fn("bn_fold_bf16", dtype)
+    fold(w_ohwi_ptr, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+         bn.running_var.data_ptr(), float(bn.eps), w_out.data_ptr(), b_out.data_ptr(), K, taps, cin, cpad, _stream())
     return w_out, b_out
 
 
@@ -123,11 +133,13 @@ def winograd_ok(x_shape, K):
     return bool(lib().winograd_supported(N, H, W, C, K)) and lib().get_compute_mode() in (0, 3, 5)
 
 
-def winograd_weights(w_ohwi_ptr, K, C, device, dgrad=False, both=False):
+def winograd_weights(w_ohwi_ptr, K, C, device, dgrad=False, both=False, out=None):
     """U = G g G^T of an OHWI [K, 3, 3, C] filter: [16, K, C] (forward) or, dgrad=True, [16, C, K] of the
-    channel-swapped, 180-degree-rotated filter; both=True: (forward, dgrad) from one launch"""
+    channel-swapped, 180-degree-rotated filter; both=True: (forward, dgrad) from one launch; out: written in place"""
     n = lib().winograd_weight_floats(K, C)
-    u = torch.empty(2 * n if both else n, dtype=F32, device=device)
+    if out is not None:
+        _chk(out, 2 * n if both else n)
+    u = out if out is not None else torch.empty(2 * n if both else n, dtype=F32, device=device)
     lib().winograd_weights(w_ohwi_ptr, _p(u), K, C, 2 if both else int(dgrad), _stream())
     return (u[:n], u[n:]) if both else u
 
@@ -458,6 +470,21 @@ def bf16_conv2d_fwd(x, w16_ptr, K, R, S, stride, pad, out16=True):
     return y
 
 
+def bf16_conv2d_bias_act_fwd(x, w16_ptr, bias_ptr, K, R, S, stride, pad, relu=0, residual=None):
+    """inference conv on 16-bit storage with folded BN: act(conv(x, w) + bias [+ residual]) -> 16-bit; relu 0 none / 1 before /
+    2 after the add; bias fp32, residual of x's dtype, added in fp32 before the one rounding"""
+    N, H, W, C = x.shape
+    _chk16(x)
+    Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
+    assert Ho > 0 and Wo > 0 and C % 64 == 0 and K % 8 == 0, (x.shape, K, R, S, stride, pad)
+    y = torch.empty((N, Ho, Wo, K), dtype=x.dtype, device=x.device)
+    if residual is not None:
+        _chk16(residual, N, Ho, Wo, K, dtype=x.dtype)
+    _fn("bf16_conv2d_bias_act_fwd", x.dtype)(_p(x), w16_ptr, bias_ptr, _p(residual), _p(y), N, H, W, C, K, R, S, stride, pad,
+                                             int(relu), _stream())
+    return y
+
+
 def bf16_conv2d_fwd_bnstats(x, w16_ptr, K, R, S, stride, pad, mean, invstd, rm_ptr, rv_ptr, ws: Workspace, eps=1e-5,
                             momentum=0.1):
     """y = conv(x, w) (bf16) and the train-mode BatchNorm statistics of y from the conv's own epilogue (no pass over y)"""
@@ -631,6 +658,37 @@ def bf16_stem_fwd(x16, w_ohwi_ptr, cin, ws: Workspace, stats=None, rm_ptr=0, rv_
     mean, invstd = stats if stats is not None else (None, None)
     _fn("bf16_stem_fwd", x16.dtype)(_p(x16), w_ohwi_ptr, cin, _p(y), N, H, W, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr,
                         ws.nbytes, _stream())
+    return y
+
+
+def bf16_stem_pack_filter(w16, out=None):
+    """BN-folded 16-bit stem filter [64, 49, 4] (bn_fold with cpad 4) -> the stem kernel's layout [64, 7, 8, 4]"""
+    _chk16(w16, 64, 49, 4)
+    wp = out if out is not None else torch.empty((64, 7, 8, 4), dtype=w16.dtype, device=w16.device)
+    _chk16(wp, 64, 7, 8, 4, dtype=w16.dtype)
+    _fn("bf16_stem_pack_filter", w16.dtype)(_p(w16), _p(wp), _stream())
+    return wp
+
+
+def bf16_stem_bias_relu_fwd(x16, w_packed, bias):
+    """inference stem: relu(conv7x7/2(x, w) + bias) for x [N, H, W, 4] and the packed folded filter of x's dtype, bias fp32"""
+    N, H, W, C4 = x16.shape
+    _chk16(x16)
+    _chk16(w_packed, 64, 7, 8, 4, dtype=x16.dtype)
+    _chk(bias, 64)
+    assert C4 == 4 and bf16_stem_ok(H, W), tuple(x16.shape)
+    y = torch.empty((N, H // 2, W // 2, 64), dtype=x16.dtype, device=x16.device)
+    _fn("bf16_stem_bias_relu_fwd", x16.dtype)(_p(x16), _p(w_packed), _p(bias), _p(y), N, H, W, _stream())
+    return y
+
+
+def bf16_maxpool3x3s2_fwd(x16):
+    """3x3 / stride 2 / pad 1 max-pool of a 16-bit NHWC map, no arg-max index (inference)"""
+    N, H, W, C = x16.shape
+    _chk16(x16)
+    assert C % 8 == 0, C
+    y = torch.empty((N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C), dtype=x16.dtype, device=x16.device)
+    _fn("bf16_maxpool3x3s2_fwd", x16.dtype)(_p(x16), _p(y), N, H, W, C, _stream())
     return y
 
 

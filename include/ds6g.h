@@ -95,6 +95,15 @@ int ds6g_conv2d_bias_act_fwd(const float* x, const float* w, const float* bias, 
 int ds6g_bn_fold(const float* w, const float* gamma, const float* beta, const float* running_mean,
                  const float* running_var, float eps, float* w_out, float* bias_out, int K, int taps, int cin, int cpad,
                  void* stream);
+/* the same fold for the frozen inference engine's 16-bit filters (TransFuser.freeze_inference): the scale is applied in
+ * fp32 and the product rounded ONCE (nearest even) to bf16 / f16 on the store; bias_out stays fp32.  w_out: [K][taps][cpad]
+ * bf16 / f16. */
+int ds6g_bn_fold_bf16(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                      const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin,
+                      int cpad, void* stream);
+int ds6g_bn_fold_f16(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                     const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin,
+                     int cpad, void* stream);
 /* ---- winograd.hip : Winograd F(2x2, 3x3) for the 3x3 / stride 1 / pad 1 convolutions of the BasicBlocks
  * (model2_seq.py:510-512,528-530,546-548,565-567): 16 GEMMs on transformed 4x4 tiles, 2.25x fewer MFMA FLOPs.
  * winograd_weights builds U[16][K][C] = G g G^T from the OHWI filter (transpose_flip = 1: the dgrad filter, i.e.
@@ -134,6 +143,13 @@ int ds6g_linear_wgrad(const float* x, const float* dy, float* dw, float* dbias, 
  * other a multiple of 8; dgrad: stride 1, or 2 with even H, W; wgrad: Wo % 64 == 0, or 64 % Wo == 0 with Ho % (64 / Wo) == 0, or a Linear. */
 int ds6g_bf16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
                          int stride, int pad, void* stream);
+/* inference form of Conv2d + eval-mode BatchNorm2d (+ identity) (+ ReLU) on 16-bit storage (the BasicBlock convs under
+ * model.eval(), model2_seq.py:510-512,528-530,546-548,565-567): the BN is folded into w (bf16, ds6g_bn_fold_bf16) and bias
+ * (fp32); y = act(conv(x, w) + bias [+ residual]); relu: 0 none, 1 before the residual add, 2 after it - the contract of
+ * ds6g_conv2d_bias_act_fwd.  x, w, residual (nullable), y: bf16; bias and the residual are added to the fp32 accumulator
+ * and the result is rounded once.  Shape limits of ds6g_bf16_conv2d_fwd. */
+int ds6g_bf16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N,
+                                  int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream);
 /* conv (bf16 output) + the train-mode BatchNorm statistics of its output in one call (the BasicBlock pairs conv1 / bn1,
  * conv2 / bn2, downsample.0 / .1 of torchvision's ResNet, model2_seq.py:510-512,528-530,546-548,565-567): the conv's epilogue
  * writes per-tile column sums / sums of squares of the STORED bf16 tile, a small finalize kernel turns them into mean /
@@ -172,6 +188,15 @@ int ds6g_bf16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const v
                                   const float* invstd, const float* gamma, const float* relu_beta, void* dx, float* dgamma,
                                   float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
                                   size_t ws_bytes, void* stream);
+/* inference stem (conv1 + bn1 + relu + maxpool under model.eval(), model2_seq.py:495-507): the filter is prepared once per
+ * snapshot - ds6g_bn_fold_bf16 with cpad = 4 gives w [64][7][7][4] bf16 and the fp32 bias, ds6g_bf16_stem_pack_filter lays
+ * it out as the forward reads it, w_packed [64][7][8][4] - then y = relu(conv7x7/2(x, w_packed) + bias) in one launch with
+ * the bias added before the one rounding (no workspace, no statistics), and ds6g_bf16_maxpool3x3s2_fwd is the 3x3 / 2 /
+ * pad 1 max-pool of a bf16 NHWC map without an arg-max index (C % 8 == 0). */
+int ds6g_bf16_stem_pack_filter(const void* w, void* w_packed, void* stream);
+int ds6g_bf16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
+                                 void* stream);
+int ds6g_bf16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream);
 
 /* ---- norm.hip ----------------------------------------------------------------------------------
  * BatchNorm2d in train mode (+ReLU, +residual add of BasicBlock): torchvision BasicBlock via
@@ -437,6 +462,12 @@ int ds6g_f16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, in
                           int mask16, int accumulate, void* stream);
 int ds6g_f16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
                           float* ws, size_t ws_bytes, void* stream);
+int ds6g_f16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N,
+                                 int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream);
+int ds6g_f16_stem_pack_filter(const void* w, void* w_packed, void* stream);
+int ds6g_f16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
+                                void* stream);
+int ds6g_f16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream);
 size_t ds6g_f16_stem_workspace_bytes(void);
 int ds6g_f16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
                       float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
