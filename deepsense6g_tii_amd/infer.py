@@ -16,21 +16,21 @@ on training, be re-pointed by an EMA shadow or be reloaded.  ``refresh()`` write
 buffers, so a HIP graph captured by ``capture()`` sees it.  (``TransFuser.capture_inference`` is the opposite contract: a
 graph that follows the live weights.)
 
-The forward itself is the model's own walk (``TransFuser._run_forward_walk``) with the engine installed as its weight
-source; the engine borrows the model's scratch workspaces and trunk streams, so calls on one model and its engines must
-come from one thread, as for the model itself.  The snapshot tables are keyed by the model's Parameter objects: re-pointing
+The forward itself is the model's own walk (``TransFuser._run_forward_walk``) under a ``_Walk`` the engine builds from
+its own pointer tables, folded convs and storage type; it writes nothing on the model.  It does borrow the model's scratch
+workspaces and trunk streams, so calls on one model and its engines must come from one thread, as for the model itself.  The snapshot tables are keyed by the model's Parameter objects: re-pointing
 ``param.data`` (EMA, load_state_dict, optimizer steps) is what refresh() follows; a model whose Parameter OBJECTS were
 replaced after the freeze is a different model - refresh() refuses it, freeze it again.
 """
 from __future__ import annotations
 
 import re
-from types import SimpleNamespace
 
 import torch
 
 from . import ops
 from ._lib import lib
+from .model import _Folded, _live_ptr, _table, _Walk, capture_forward
 
 F32 = torch.float32
 _STORAGE = {"f32": F32, "bf16": torch.bfloat16, "f16": torch.float16}
@@ -56,7 +56,7 @@ class InferenceEngine:
 
     # ---------------------------------------------------------------- snapshot ------------------
     def _allocate(self):
-        """device buffers of the snapshot (allocated once: refresh() writes into them) and the pointer tables of the walk"""
+        """device buffers of the snapshot (allocated once: refresh() writes into them) and the walk that reads them"""
         m, dev, h16 = self.model, self.model.device, self.dtype != F32
         named = [(n, p) for n, p in m.arena_layout()[0] if not n.startswith(_TRUNKS)]   # arena order: k|q|v stay adjacent
         pad4 = lambda n: (n + 3) // 4 * 4  # noqa: E731
@@ -86,15 +86,14 @@ class InferenceEngine:
                     self._add_fold(blk.conv2, blk.bn2, K, 9, K, K, wino=True)
                     if blk.downsample is not None:
                         self._add_fold(blk.downsample[0], blk.downsample[1], K, 1, C, C)
+        self._walk = _Walk(_table(self.wtable), _table(self.wtable16) if h16 else None,
+                           lambda conv, *_: self.folded[id(conv.weight)], self.dtype)
 
     def _add_fold(self, conv, bn, K, taps, cin, cpad, wino=False, stem=False):
         dev, h16 = self.model.device, self.dtype != F32
-        f = SimpleNamespace(w=torch.empty((K, taps, cpad), dtype=self.dtype, device=dev),
-                            b=torch.empty((K,), dtype=F32, device=dev), u=None, wp=None)
-        if wino and not h16:
-            f.u = torch.empty(lib().winograd_weight_floats(K, cin), dtype=F32, device=dev)
-        if stem and h16:
-            f.wp = torch.empty((64, 7, 8, 4), dtype=self.dtype, device=dev)
+        f = _Folded(torch.empty((K, taps, cpad), dtype=self.dtype, device=dev), torch.empty((K,), dtype=F32, device=dev),
+                    torch.empty(lib().winograd_weight_floats(K, cin), dtype=F32, device=dev) if wino and not h16 else None,
+                    torch.empty((64, 7, 8, 4), dtype=self.dtype, device=dev) if stem and h16 else None)
         self.folded[id(conv.weight)] = f
         self._folds.append((conv, bn, K, taps, cin, cpad, f))
 
@@ -102,7 +101,7 @@ class InferenceEngine:
         yield self._flat32
         yield self._flat16
         for f in self.folded.values():
-            for t in (f.w, f.b, f.u, f.wp):
+            for t in f:
                 if t is not None:
                     yield t
 
@@ -120,21 +119,17 @@ class InferenceEngine:
         if any(id(p) not in self.wtable and id(p) not in self.wtable16 and id(p) not in self._trunk_ids
                for p in m.parameters()):
             raise RuntimeError("the model's Parameter objects were replaced after freeze_inference(); freeze it again")
-        wfast, m._wfast = m._wfast, None   # live pointers, not the table of a recorded forward still awaiting its backward
-        try:
-            for p, seg in self._copies:
-                if seg.dtype == F32:
-                    seg.view(p.shape).copy_(p.data)
-                else:
-                    ops.cast_bf16(p.data.contiguous(), out=seg.view(p.shape))
-            for conv, bn, K, taps, cin, cpad, f in self._folds:
-                ops.bn_fold(m._w(conv.weight), bn, K, taps, cin, cpad, out=(f.w, f.b))
-                if f.u is not None:
-                    ops.winograd_weights(f.w.data_ptr(), K, cin, m.device, out=f.u)
-                if f.wp is not None:
-                    ops.bf16_stem_pack_filter(f.w, out=f.wp)
-        finally:
-            m._wfast = wfast
+        for p, seg in self._copies:
+            if seg.dtype == F32:
+                seg.view(p.shape).copy_(p.data)
+            else:
+                ops.cast_bf16(p.data.contiguous(), out=seg.view(p.shape))
+        for conv, bn, K, taps, cin, cpad, f in self._folds:
+            ops.bn_fold(_live_ptr(conv.weight), bn, K, taps, cin, cpad, out=(f.w, f.b))
+            if f.u is not None:
+                ops.winograd_weights(f.w.data_ptr(), K, cin, m.device, out=f.u)
+            if f.wp is not None:
+                ops.bf16_stem_pack_filter(f.w, out=f.wp)
         return self
 
     # ---------------------------------------------------------------- nn.Module-like surface ----
@@ -152,14 +147,10 @@ class InferenceEngine:
     def __call__(self, image_list, lidar_list=None, radar_list=None, gps=None, rebuild_modality_feat_list=None):
         m = self.model
         images, lidars, radars, gps = m._inputs(image_list, lidar_list, radar_list, gps)
-        saved = (m._infer, m._wfast, m._use16, m._dt16, m._fold_now, m._recording)
-        m._infer, m._wfast = self, self.wtable
         try:
-            logits, _ = m._run_forward_walk(images, lidars, radars, gps, record=False)
+            return m._run_forward_walk(self._walk, images, lidars, radars, gps)[0]
         finally:
             lib().set_dropout_salt(0)
-            m._infer, m._wfast, m._use16, m._dt16, m._fold_now, m._recording = saved
-        return logits
 
     forward = __call__
 
@@ -168,5 +159,4 @@ class InferenceEngine:
         ``run(image_list, lidar_list, radar_list, gps) -> logits`` as ``TransFuser.capture_inference`` does: static input
         buffers, one replay per call, the returned tensor overwritten by the next replay.  The graph reads the engine's
         snapshot buffers, which ``refresh()`` rewrites in place: the same ``run`` serves the refreshed weights."""
-        from .model import capture_forward
         return capture_forward(self, self.model.device, image_list, lidar_list, radar_list, gps)

@@ -21,6 +21,7 @@ train2_seq.py:326-333).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from functools import partial
@@ -197,22 +198,52 @@ _StageRec = _record("_StageRec", "s C T fps offs pe off_e gps_src blocks x_last 
 # the head: fused tokens, join MLP hiddens, final feature-map shapes, (join output, saved state) of the GRU head or None,
 # feature-map dtype
 _HeadRec = _record("_HeadRec", "fused h1 h2 fshapes gru fdtype")
-# a whole training forward: stems / stages per trunk / stage, layers[stage][trunk] = [_BlockRec]
-_Tape = _record("_Tape", "B stems layers stages head gps salt")
+# a whole training forward: stems / stages per trunk / stage, layers[stage][trunk] = [_BlockRec]; walk = the _Walk it ran
+# under (the backward walk takes weights and storage from there, whatever forward ran in between)
+_Tape = _record("_Tape", "B stems layers stages head gps salt walk")
+# a conv with the eval-mode BatchNorm behind it folded in: filter [K, taps, cpad], fp32 bias [K], Winograd-transformed filter
+# (fp32 3x3 / stride 1) or None, filter in the 16-bit stem kernel's packed layout or None
+_Folded = _record("_Folded", "w b u wp")
 
-# GPT-block kernels of the two activation storages (same arguments; bf16: operands stored as bf16, weights from the shadow)
-_F32_OPS = SimpleNamespace(dtype=F32, ln_fwd=ops.layernorm_fwd, ln_bwd=ops.layernorm_bwd, lin_fwd=ops.linear_fwd,
-                           lin_dgrad=ops.linear_dgrad, lin_wgrad=ops.linear_wgrad, attn_fwd=ops.attention_fwd,
-                           attn_bwd=ops.attention_bwd)
-_BF16_OPS = SimpleNamespace(dtype=BF16, ln_fwd=ops.layernorm_fwd_bf16, ln_bwd=ops.layernorm_bwd_bf16,
-                            lin_fwd=ops.bf16_linear_fwd, lin_dgrad=ops.bf16_linear_dgrad, lin_wgrad=ops.bf16_linear_wgrad,
-                            attn_fwd=ops.attention_fwd_bf16, attn_bwd=ops.attention_bwd_bf16io)
-# f16 storage: the same kernels' f16 twins (the ops wrappers dispatch by operand dtype; LayerNorm is told its output dtype)
-_F16_OPS = SimpleNamespace(dtype=F16, ln_fwd=partial(ops.layernorm_fwd_bf16, dtype=F16),
-                           ln_bwd=partial(ops.layernorm_bwd_bf16, dtype=F16), lin_fwd=ops.bf16_linear_fwd,
-                           lin_dgrad=ops.bf16_linear_dgrad, lin_wgrad=ops.bf16_linear_wgrad, attn_fwd=ops.attention_fwd_bf16,
-                           attn_bwd=ops.attention_bwd_bf16io)
-_OPS16 = {BF16: _BF16_OPS, F16: _F16_OPS}
+# GPT-block kernels by activation storage (same arguments; 16-bit: operands stored as bf16 / f16, weights from the 16-bit copy;
+# the ops wrappers dispatch by operand dtype, LayerNorm is told its output dtype)
+_OPS = {F32: SimpleNamespace(ln_fwd=ops.layernorm_fwd, ln_bwd=ops.layernorm_bwd, lin_fwd=ops.linear_fwd,
+                             lin_dgrad=ops.linear_dgrad, lin_wgrad=ops.linear_wgrad, attn_fwd=ops.attention_fwd,
+                             attn_bwd=ops.attention_bwd)}
+for _dt in _H16:
+    _OPS[_dt] = SimpleNamespace(ln_fwd=partial(ops.layernorm_fwd_bf16, dtype=_dt),
+                                ln_bwd=partial(ops.layernorm_bwd_bf16, dtype=_dt), lin_fwd=ops.bf16_linear_fwd,
+                                lin_dgrad=ops.bf16_linear_dgrad, lin_wgrad=ops.bf16_linear_wgrad,
+                                attn_fwd=ops.attention_fwd_bf16, attn_bwd=ops.attention_bwd_bf16io)
+
+
+def _live_ptr(p):
+    """device pointer of a parameter as the kernels expect it (conv: OHWI), read from wherever param.data points now"""
+    if p.dim() == 4 and not p.data.is_contiguous(memory_format=torch.channels_last):
+        p.data = p.data.contiguous(memory_format=torch.channels_last)
+    elif p.dim() != 4 and not p.data.is_contiguous():
+        p.data = p.data.contiguous()
+    return p.data_ptr()
+
+
+def _table(ptrs):
+    """pointer lookup p -> ptrs[id(p)]: one dict index per call (the walk asks ~1250 times per step)"""
+    return lambda p: ptrs[id(p)]
+
+
+class _Walk:
+    """What one forward walk (and the backward walk of its tape) runs under, passed to every helper; the model builds one
+    per forward (_new_walk), a frozen engine keeps the one over its snapshot tables.
+    w(p) / w16(p): fp32 / 16-bit device pointer of parameter p (w16 None on fp32 storage); folded(conv, bn, K, taps, cin,
+    cpad, wino) -> _Folded of a BN-folded inference conv, None when BatchNorm is not folded; dtype: the storage of feature
+    maps and GEMM operands (F32, BF16 or F16); train: train-mode BatchNorm and dropout; record: a tape is kept; g(p): (grad
+    pointer, accumulate flag) of p, set by _begin_backward."""
+    __slots__ = ("w", "w16", "folded", "dtype", "train", "record", "fold", "g")
+
+    def __init__(self, w, w16=None, folded=None, dtype=F32, train=False, record=False):
+        assert not (folded is not None and (train or record)), "the backward needs the BatchNorm tape"
+        self.w, self.w16, self.folded, self.dtype, self.train, self.record = w, w16, folded, dtype, train, record
+        self.fold, self.g = folded is not None, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -297,8 +328,6 @@ class TransFuser(nn.Module):
         self.overlap_wgrad_trunks = False  # measured: no gain on top of the three concurrent trunk streams
         # bf16 configuration: train-mode BatchNorm statistics come out of the conv's epilogue (ds6g_bf16_conv2d_fwd_bnstats)
         self.fuse_bn_stats16 = os.environ.get("DS6G_FUSE_BN_STATS16", "1") != "0"
-        self._fold_now = False
-        self._recording = False
         self.use_winograd = True  # 3x3 / stride-1 convs (forward and data gradient) as Winograd F(2x2, 3x3) in fp32 mode
         self.fold_bn_eval = True  # eval(): BatchNorm folded into the conv weights (no BN kernels at inference)
         self.fuse_qkv = True      # key|query|value projections as one GEMM when their parameters are contiguous (arena)
@@ -308,14 +337,9 @@ class TransFuser(nn.Module):
         # master weights, the residual stream, LayerNorm / softmax statistics, every accumulator, loss, optimizer.
         self.bf16_storage = True
         self.bf16_stems = os.environ.get("DS6G_BF16_STEMS", "1") != "0"   # 7x7 stems on bf16 storage too (csrc/stem.hip)
-        self._arena16 = None
-        self._use16 = False
-        self._dt16 = BF16      # the walk's 16-bit storage dtype (bf16 in mode "bf16", f16 in mode "f16")
+        self._arena16 = None   # 16-bit shadow of the parameter arena (_refresh_shadow16)
         self._anchor = None
         self._arena = None
-        self._wfast = None     # parameter-pointer table of the walk in flight (see _run_forward)
-        self._wtable = None
-        self._infer = None     # the infer.InferenceEngine whose snapshot the walk in flight reads (freeze_inference), else None
         if self.device.type == "cuda":
             lib()  # fail loudly now if the HIP library is missing
             self._build_arena()
@@ -360,19 +384,17 @@ class TransFuser(nn.Module):
                 i += 1
         return out
 
-    def _qkv_fused(self, at, grads=False):
+    def _qkv_fused(self, at, look=_live_ptr, grads=False):
         """(weight ptr, bias ptr) of the fused key|query|value block when the three projections are contiguous in
-        memory right now (arena or EMA-shadow layout; param.data may have been re-pointed), else None."""
+        memory right now (arena or EMA-shadow layout; param.data may have been re-pointed), else None.  look: a walk's
+        pointer lookup w - or, grads=True, its gradient lookup g: the gradients contiguous with ONE accumulate flag."""
         C = at.key.weight.shape[0]
+        wp = [look(m.weight) for m in (at.key, at.query, at.value)]
+        bp = [look(m.bias) for m in (at.key, at.query, at.value)]
         if grads:
-            w = [self._g(m.weight) for m in (at.key, at.query, at.value)]
-            b = [self._g(m.bias) for m in (at.key, at.query, at.value)]
-            if len({f for _, f in w + b}) != 1:
+            if len({f for _, f in wp + bp}) != 1:
                 return None
-            wp, bp = [x for x, _ in w], [x for x, _ in b]
-        else:
-            wp = [self._w(m.weight) for m in (at.key, at.query, at.value)]
-            bp = [self._w(m.bias) for m in (at.key, at.query, at.value)]
+            wp, bp = [x for x, _ in wp], [x for x, _ in bp]
         if wp[1] == wp[0] + 4 * C * C and wp[2] == wp[0] + 8 * C * C and bp[1] == bp[0] + 4 * C and bp[2] == bp[0] + 8 * C:
             return wp[0], bp[0]
         return None
@@ -393,16 +415,13 @@ class TransFuser(nn.Module):
 
     def _build_arena(self):
         dev = self.device
-        named, _, _, total = self.arena_layout()
-        self._arena = torch.zeros(total, dtype=F32, device=dev)
-        self._garena = torch.zeros(total, dtype=F32, device=dev)
+        named, self._pslice, self._milestone_end, self._arena_used = self.arena_layout()
+        self._arena = torch.zeros(self._arena_used, dtype=F32, device=dev)
+        self._garena = torch.zeros(self._arena_used, dtype=F32, device=dev)
         self._gview = {}
-        self._pslice = {}
-        self._milestone_end = {}
         self.grad_ready_hook = None  # callable(milestone, lo, hi): grads garena[lo:hi] are final
-        off = 0
         for name, p in named:
-            n = p.numel()
+            off, n = self._pslice[name]
             seg = self._arena[off:off + n]
             gseg = self._garena[off:off + n]
             if p.dim() == 4:  # conv OIHW parameter stored OHWI (channels_last)
@@ -415,10 +434,6 @@ class TransFuser(nn.Module):
             view.copy_(p.data)
             p.data = view
             self._gview[name] = gview
-            self._pslice[name] = (off, n)
-            off += (n + 3) // 4 * 4
-            self._milestone_end[self._milestone(name)] = off
-        self._arena_used = off
         for _, b in self.named_buffers():
             b.data = b.data.to(dev)
         nb = [b for n_, b in self.named_buffers() if n_.endswith("num_batches_tracked")]
@@ -427,12 +442,13 @@ class TransFuser(nn.Module):
             b.data = self._nbt[i]
         self._ws_main = ops.Workspace(dev, 1 << 30)
         self._anchor = torch.zeros(1, dtype=F32, device=dev, requires_grad=True)
-        self._pname = {id(p): n for n, p in named}
         # the hot path walks the parameter list several times per step (fresh / accumulate modes, arena check, zero_grad):
         # nn.Module.named_parameters() re-traverses the module tree each time (~3 ms of host per walk), the set is fixed
         self._plist = list(self.named_parameters())
+        # parameter pointers of a walk while every parameter lives in the arena: base + offset (one pass over the list instead
+        # of ~1250 Tensor.data round trips per step)
         a0 = self._arena.data_ptr()
-        self._wtable = {id(p): a0 + 4 * self._pslice[n][0] for n, p in self._plist}
+        self._wtable = _table({id(p): a0 + 4 * self._pslice[n][0] for n, p in self._plist})
 
     @property
     def _ws(self):
@@ -475,7 +491,6 @@ class TransFuser(nn.Module):
             cur.wait_stream(st)
 
     def _trunk_ctx(self, streams, m):
-        import contextlib
         return ops.on_stream(streams[m]) if streams is not None else contextlib.nullcontext()
 
     def _apply(self, fn, recurse=True):
@@ -498,45 +513,47 @@ class TransFuser(nn.Module):
         return True
 
     # ---------------------------------------------------------------- pointers ------------------
-    def _w(self, p):
-        """device pointer of a parameter as the kernels expect it (conv: OHWI)."""
-        fast = self._wfast
-        if fast is not None:      # walk in flight with every parameter in the arena (checked once at its start)
-            return fast[id(p)]
-        if p.dim() == 4 and not p.data.is_contiguous(memory_format=torch.channels_last):
-            p.data = p.data.contiguous(memory_format=torch.channels_last)
-        elif p.dim() != 4 and not p.data.is_contiguous():
-            p.data = p.data.contiguous()
-        return p.data_ptr()
-
-    def _g(self, p):
-        """(grad pointer, accumulate flag) of parameter p for the backward walk in flight."""
-        return self._gmode[id(p)]
-
-    def _w16(self, p):
-        """device pointer of parameter p inside the bf16 shadow of the parameter arena (same layout, 2-byte elements)"""
-        if self._infer is not None:   # a frozen 16-bit engine runs the walk: its own 16-bit copies
-            return self._infer.wtable16[id(p)]
-        return self._arena16.data_ptr() + 2 * self._pslice[self._pname[id(p)]][0]
-
-    def _refresh_shadow16(self):
-        """bf16 shadow of the fp32 master weights, refreshed once per forward of the bf16-storage path: one streaming cast
-        over the arena (0.47 GB of traffic, ~0.1 ms: 0.3 % of a step), so it can never be stale whatever touched the
-        parameters (optimizer, load_state_dict, in-place edits).  Off when the parameters were re-pointed away from the
-        arena (EMA shadow applied): the fp32-storage kernels then run, reading the live pointers."""
+    def _refresh_shadow16(self, in_arena):
+        """-> the storage dtype of a walk that starts now.  16-bit (compute modes "bf16" / "f16"): the 16-bit shadow of the
+        fp32 master weights is refreshed, once per forward: one streaming cast over the arena (0.47 GB of traffic, ~0.1 ms:
+        0.3 % of a step), so it can never be stale whatever touched the parameters (optimizer, load_state_dict, in-place
+        edits).  F32 when the parameters were re-pointed away from the arena (EMA shadow applied): the fp32-storage kernels
+        then run, reading the live pointers."""
         mode = lib().get_compute_mode()
-        self._use16 = bool(self.bf16_storage and self._arena is not None and mode in (1, 5)
-                           and self.fuse_qkv and self.params_in_arena())
-        if self._use16:
-            self._dt16 = F16 if mode == 5 else BF16
-            if self._arena16 is None or self._arena16.dtype != self._dt16:   # (re)allocated when the mode changes
-                self._arena16 = torch.empty(self._arena.numel(), dtype=self._dt16, device=self.device)
-            ops.cast_bf16(self._arena, out=self._arena16)
+        if not (self.bf16_storage and self._arena is not None and mode in (1, 5) and self.fuse_qkv and in_arena):
+            return F32
+        dt = F16 if mode == 5 else BF16
+        if self._arena16 is None or self._arena16.dtype != dt:   # (re)allocated when the mode changes: same layout, 2-byte elements
+            self._arena16 = torch.empty(self._arena.numel(), dtype=dt, device=self.device)
+            a16 = self._arena16.data_ptr()
+            self._wtable16 = _table({id(p): a16 + 2 * self._pslice[n][0] for n, p in self._plist})
+        ops.cast_bf16(self._arena, out=self._arena16)
+        return dt
 
-    def _begin_backward(self):
+    def _fold_live(self, w):
+        """the folded-conv source of model.eval(): folded (and Winograd-transformed) now, from the live parameters"""
+        def folded(conv, bn, K, taps, cin, cpad, wino):
+            wf, bf = ops.bn_fold(w(conv.weight), bn, K, taps, cin, cpad)
+            return _Folded(wf, bf, ops.winograd_weights(wf.data_ptr(), K, cin, self.device) if wino else None, None)
+        return folded
+
+    def _new_walk(self, record):
+        """the walk of a forward of this model that starts now"""
+        train = self.training
+        # arena base + offset when every parameter still lives in the arena; re-pointed parameters (EMA shadow applied) ->
+        # live reads
+        in_arena = self._arena is not None and self.params_in_arena()
+        w = self._wtable if in_arena else _live_ptr
+        dtype = self._refresh_shadow16(in_arena)
+        if self.fold_bn_eval and not train and not record:   # inference only (the backward needs the BN tape): BN folded per
+            return _Walk(w, folded=self._fold_live(w))       # call into the fp32 weights, fp32 storage
+        return _Walk(w, self._wtable16 if dtype != F32 else None, None, dtype, train, record)
+
+    def _begin_backward(self, wk):
         # .grad is None -> write fresh and attach the arena view; .grad is our view -> accumulate in
         # place (torch semantics when zero_grad was not called); foreign tensor -> write, then add.
-        self._gmode, self._fresh, self._foreign = {}, [], []
+        gmode, self._fresh, self._foreign = {}, [], []
+        wk.g = _table(gmode)
         plist = self._plist if self._arena is not None else list(self.named_parameters())
         if self.grad_ready_hook is not None:
             self._dp_check_fresh_grads()
@@ -547,12 +564,12 @@ class TransFuser(nn.Module):
             gv = self._gview[name]
             if p.grad is None:
                 self._fresh.append((p, gv))
-                self._gmode[id(p)] = (gv.data_ptr(), 0)
+                gmode[id(p)] = (gv.data_ptr(), 0)
             elif p.grad.data_ptr() == gv.data_ptr():
-                self._gmode[id(p)] = (gv.data_ptr(), 1)
+                gmode[id(p)] = (gv.data_ptr(), 1)
             else:
                 self._foreign.append((p, gv))
-                self._gmode[id(p)] = (gv.data_ptr(), 0)
+                gmode[id(p)] = (gv.data_ptr(), 0)
 
     def _milestone_done(self, k):
         if self.grad_ready_hook is not None:
@@ -560,7 +577,6 @@ class TransFuser(nn.Module):
             self.grad_ready_hook(k, lo, self._milestone_end[k])
 
     def _end_backward(self):
-        self._wfast = None
         owner = getattr(self.grad_ready_hook, "__self__", None)
         if owner is not None and hasattr(owner, "finish"):
             owner.finish()  # flush the tail bucket; the calling stream waits for every outstanding all-reduce
@@ -568,7 +584,7 @@ class TransFuser(nn.Module):
             p.grad = gv
         for p, gv in self._foreign:
             p.grad.add_(gv)
-        self._gmode, self._fresh, self._foreign = {}, [], []
+        self._fresh, self._foreign = [], []
 
     def set_dropout_seed(self, seed, rank=0):
         """Seed of the counter-based dropout masks.  Data-parallel ranks must draw independent masks (the reference's
@@ -696,193 +712,170 @@ class TransFuser(nn.Module):
                 (e.lidar_encoder._model, "resnet18", 1, False),
                 (e.radar_encoder._model, "resnet18", 2 if self.config.add_velocity else 1, False))
 
-    def _bn_fwd(self, bn, x, relu, residual, train):
+    def _bn_fwd(self, wk, bn, x, relu, residual):
         """BatchNorm (+ residual, + ReLU) of an fp32 or bf16 feature map; statistics fp32 -> (y, (mean, invstd))"""
         f16 = x.dtype in _H16
         C = x.shape[-1]
         M = x.numel() // C
         stats = torch.empty(2, C, dtype=F32, device=x.device)
         mean, invstd = stats[0], stats[1]
-        if train:
+        if wk.train:
             (ops.bf16_bn_stats if f16 else ops.bn_stats)(M, C, x, mean, invstd, bn.running_mean.data_ptr(),
                                                          bn.running_var.data_ptr(), self._ws, bn.eps, bn.momentum)
         else:
             ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), C, mean, invstd, bn.eps)
-        y = (ops.bf16_bn_apply if f16 else ops.bn_apply)(x, mean, invstd, self._w(bn.weight), self._w(bn.bias), relu,
-                                                         residual)
+        y = (ops.bf16_bn_apply if f16 else ops.bn_apply)(x, mean, invstd, wk.w(bn.weight), wk.w(bn.bias), relu, residual)
         return y, (mean, invstd)
 
-    def _folded(self, conv, bn, K, taps, cin, cpad=None):
-        """(filter [K, taps, cpad], bias [K]) of `conv` with the eval-mode `bn` folded in: the frozen engine's prepared
-        pair when one runs this walk, else folded now from the live parameters"""
-        if self._infer is not None:
-            f = self._infer.folded[id(conv.weight)]
-            return f.w, f.b
-        return ops.bn_fold(self._w(conv.weight), bn, K, taps, cin, cpad)
+    def _pack_frames(self, frames, cin, normalize, dtype):
+        """the stem's input, NHWC x4 of `dtype`: S NCHW fp32 frames packed (and normalised), or the tensor of a
+        data.PackedInputs, which is packed and normalised fp32 already"""
+        if torch.is_tensor(frames):
+            assert frames.dim() == 4 and frames.shape[3] == 4 and frames.dtype == F32 and frames.is_contiguous() \
+                and frames.device == self.device
+            return frames if dtype == F32 else ops.cast_bf16(frames, dtype=dtype)
+        L, st = lib(), ops._stream()
+        B, S = frames[0].shape[0], len(frames)
+        H, W = frames[0].shape[2:]
+        x = torch.empty((B * S, H, W, 4), dtype=dtype, device=self.device)
+        for t, f in enumerate(frames):
+            assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
+            if dtype == F32:
+                L.pack_input(f.data_ptr(), x.data_ptr(), B, cin, H, W, 4, S, t, int(normalize), st)
+            else:
+                ops._fn("pack_input_bf16", dtype)(f.data_ptr(), x.data_ptr(), B, cin, H, W, S, t, int(normalize), st)
+        return x
 
-    def _stem_fwd_frozen16(self, trunk, cin, normalize, frames):
-        """the stem of a frozen 16-bit engine: packed 16-bit input -> relu(conv + bias), BN folded into the 16-bit filter
-        and the fp32 bias, the bias added before the one rounding -> index-free 16-bit max-pool"""
-        L = lib()
-        st = ops._stream()
-        dt = self._infer.dtype
-        if torch.is_tensor(frames):  # data.PackedInputs: fp32 NHWC x4, normalised
-            assert frames.dim() == 4 and frames.shape[3] == 4 and frames.dtype == F32 and frames.is_contiguous()
-            x16 = ops.cast_bf16(frames, dtype=dt)
+    def _stem_fwd(self, wk, trunk, cin, normalize, frames):
+        """7x7 / 2 conv -> BatchNorm -> ReLU -> 3x3 / 2 max-pool of one trunk -> (pooled map, _StemRec or None)"""
+        if wk.fold:
+            stem = self._stem_fwd_folded if wk.dtype == F32 else self._stem_fwd_folded16
+        elif (wk.dtype != F32 and self.bf16_stems and not torch.is_tensor(frames)
+                and ops.bf16_stem_ok(*frames[0].shape[2:])):
+            stem = self._stem_fwd16
         else:
-            B, S = frames[0].shape[0], len(frames)
-            H, W = frames[0].shape[2:]
-            x16 = torch.empty((B * S, H, W, 4), dtype=dt, device=self.device)
-            pack = L.pack_input_bf16 if dt == BF16 else L.pack_input_f16
-            for t, f in enumerate(frames):
-                assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
-                pack(f.data_ptr(), x16.data_ptr(), B, cin, H, W, S, t, int(normalize), st)
+            stem = self._stem_fwd32
+        return stem(wk, trunk, cin, normalize, frames)
+
+    def _stem_fwd_folded16(self, wk, trunk, cin, normalize, frames):
+        """inference on 16-bit storage: packed 16-bit input -> relu(conv + bias), BN folded into the 16-bit filter and the
+        fp32 bias, the bias added before the one rounding -> index-free 16-bit max-pool"""
+        x16 = self._pack_frames(frames, cin, normalize, wk.dtype)
         if not ops.bf16_stem_ok(*x16.shape[1:3]):
             raise RuntimeError(f"the 16-bit inference stem needs H % 16 == 0 and W % 32 == 0, got {tuple(x16.shape[1:3])}")
-        f = self._infer.folded[id(trunk.conv1.weight)]
-        a1 = ops.bf16_stem_bias_relu_fwd(x16, f.wp, f.b)
-        return ops.bf16_maxpool3x3s2_fwd(a1), None
+        f = wk.folded(trunk.conv1, trunk.bn1, 64, 49, cin, 4, False)
+        return ops.bf16_maxpool3x3s2_fwd(ops.bf16_stem_bias_relu_fwd(x16, f.wp, f.b)), None
 
-    def _stem_fwd(self, trunk, cin, normalize, frames, train):
-        L = lib()
-        st = ops._stream()
-        if self._infer is not None and self._infer.dtype in _H16:
-            return self._stem_fwd_frozen16(trunk, cin, normalize, frames)
-        if (self._use16 and self.bf16_stems and not self._fold_now and not torch.is_tensor(frames)
-                and ops.bf16_stem_ok(*frames[0].shape[2:])):
-            # bf16 configuration: the stem too on bf16 storage (csrc/stem.hip) - packed input, conv output and its gradient
-            # are bf16; the conv's epilogue delivers the BatchNorm statistics
-            B, S = frames[0].shape[0], len(frames)
-            H, W = frames[0].shape[2:]
-            x16 = torch.empty((B * S, H, W, 4), dtype=self._dt16, device=self.device)
-            pack = L.pack_input_bf16 if self._dt16 == BF16 else L.pack_input_f16
-            for t, f in enumerate(frames):
-                assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
-                pack(f.data_ptr(), x16.data_ptr(), B, cin, H, W, S, t, int(normalize), st)
-            bn = trunk.bn1
-            stats = torch.empty(2, 64, dtype=F32, device=self.device)
-            if train:
-                c1 = ops.bf16_stem_fwd(x16, self._w(trunk.conv1.weight), cin, self._ws, (stats[0], stats[1]),
-                                       bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps, bn.momentum)
-            else:
-                c1 = ops.bf16_stem_fwd(x16, self._w(trunk.conv1.weight), cin, self._ws)
-                ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), 64, stats[0], stats[1], bn.eps)
-            p1, idx = ops.bf16_stem_bn_relu_maxpool(c1, stats[0], stats[1], self._w(bn.weight), self._w(bn.bias))
-            return p1, _StemRec(x16, c1, None, (stats[0], stats[1]), idx, cin)
-        if torch.is_tensor(frames):  # data.PackedInputs: already NHWC x4, normalised
-            x = frames
-            assert x.dim() == 4 and x.shape[3] == 4 and x.dtype == F32 and x.is_contiguous() and x.device == self.device
-        else:
-            B = frames[0].shape[0]
-            S = len(frames)
-            H, W = frames[0].shape[2:]
-            x = torch.empty((B * S, H, W, 4), dtype=F32, device=self.device)
-            for t, f in enumerate(frames):
-                assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
-                L.pack_input(f.data_ptr(), x.data_ptr(), B, cin, H, W, 4, S, t, int(normalize), st)
-        if self._fold_now:
-            wf, bf = self._folded(trunk.conv1, trunk.bn1, 64, 49, cin, 4)  # folds and pads to 4 channels
-            c1, st1 = None, None
-            a1 = ops.conv2d_bias_act_fwd(x, wf.data_ptr(), bf.data_ptr(), 64, 7, 7, 2, 3, relu=1)
-        else:
-            wpad = torch.empty((64, 7, 7, 4), dtype=F32, device=self.device)
-            L.pad_channels(self._w(trunk.conv1.weight), wpad.data_ptr(), 64 * 49, cin, 4, 0, 0, st)
-            c1 = ops.conv2d_fwd(x, wpad.data_ptr(), 64, 7, 7, 2, 3)
-            # BN -> ReLU -> max-pool in one pass: the [N, 128, 128, 64] activation is never materialised
-            bn = trunk.bn1
-            stats = torch.empty(2, 64, dtype=F32, device=self.device)
-            if train:
-                ops.bn_stats(c1.numel() // 64, 64, c1, stats[0], stats[1], bn.running_mean.data_ptr(),
-                             bn.running_var.data_ptr(), self._ws, bn.eps, bn.momentum)
-            else:
-                ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), 64, stats[0], stats[1], bn.eps)
-            st1 = (stats[0], stats[1])
-            pool = partial(ops.bn_relu_maxpool_bf16out, dtype=self._dt16) if self._use16 else ops.bn_relu_maxpool
-            p1, idx = pool(c1, st1[0], st1[1], self._w(bn.weight), self._w(bn.bias))
-            return p1, _StemRec(x, c1, None, st1, idx, cin)
+    def _stem_fwd_folded(self, wk, trunk, cin, normalize, frames):
+        """inference on fp32 storage: BN folded into the filter (padded to 4 channels) and a bias"""
+        x = self._pack_frames(frames, cin, normalize, F32)
+        f = wk.folded(trunk.conv1, trunk.bn1, 64, 49, cin, 4, False)
+        a1 = ops.conv2d_bias_act_fwd(x, f.w.data_ptr(), f.b.data_ptr(), 64, 7, 7, 2, 3, relu=1)
         N, H1, W1, _ = a1.shape
         Ho, Wo = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
         p1 = torch.empty((N, Ho, Wo, 64), dtype=F32, device=self.device)
         idx = torch.empty((N, Ho, Wo, 64), dtype=torch.uint8, device=self.device)
-        L.maxpool3x3s2_fwd(a1.data_ptr(), p1.data_ptr(), idx.data_ptr(), N, H1, W1, 64, st)
-        return p1, _StemRec(x, c1, a1, st1, idx, cin)
+        lib().maxpool3x3s2_fwd(a1.data_ptr(), p1.data_ptr(), idx.data_ptr(), N, H1, W1, 64, ops._stream())
+        return p1, _StemRec(x, None, a1, None, idx, cin)
 
-    def _conv_fwd(self, x, conv, K, R, stride):
+    def _stem_fwd16(self, wk, trunk, cin, normalize, frames):
+        """bf16 configuration: the stem too on 16-bit storage (csrc/stem.hip) - packed input, conv output and its gradient
+        are 16-bit; the conv's epilogue delivers the BatchNorm statistics"""
+        x16 = self._pack_frames(frames, cin, normalize, wk.dtype)
+        bn = trunk.bn1
+        stats = torch.empty(2, 64, dtype=F32, device=self.device)
+        if wk.train:
+            c1 = ops.bf16_stem_fwd(x16, wk.w(trunk.conv1.weight), cin, self._ws, (stats[0], stats[1]),
+                                   bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps, bn.momentum)
+        else:
+            c1 = ops.bf16_stem_fwd(x16, wk.w(trunk.conv1.weight), cin, self._ws)
+            ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), 64, stats[0], stats[1], bn.eps)
+        p1, idx = ops.bf16_stem_bn_relu_maxpool(c1, stats[0], stats[1], wk.w(bn.weight), wk.w(bn.bias))
+        return p1, _StemRec(x16, c1, None, (stats[0], stats[1]), idx, cin)
+
+    def _stem_fwd32(self, wk, trunk, cin, normalize, frames):
+        """fp32 conv; BN -> ReLU -> max-pool in one pass (the [N, 128, 128, 64] activation is never materialised), the
+        pooled map written in the walk's storage"""
+        x = self._pack_frames(frames, cin, normalize, F32)
+        wpad = torch.empty((64, 7, 7, 4), dtype=F32, device=self.device)
+        lib().pad_channels(wk.w(trunk.conv1.weight), wpad.data_ptr(), 64 * 49, cin, 4, 0, 0, ops._stream())
+        c1 = ops.conv2d_fwd(x, wpad.data_ptr(), 64, 7, 7, 2, 3)
+        bn = trunk.bn1
+        stats = torch.empty(2, 64, dtype=F32, device=self.device)
+        if wk.train:
+            ops.bn_stats(c1.numel() // 64, 64, c1, stats[0], stats[1], bn.running_mean.data_ptr(),
+                         bn.running_var.data_ptr(), self._ws, bn.eps, bn.momentum)
+        else:
+            ops.bn_eval_prepare(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), 64, stats[0], stats[1], bn.eps)
+        pool = ops.bn_relu_maxpool if wk.dtype == F32 else partial(ops.bn_relu_maxpool_bf16out, dtype=wk.dtype)
+        p1, idx = pool(c1, stats[0], stats[1], wk.w(bn.weight), wk.w(bn.bias))
+        return p1, _StemRec(x, c1, None, (stats[0], stats[1]), idx, cin)
+
+    def _conv_fwd(self, wk, x, conv, K, R, stride):
         """R x R conv (padding R // 2) of a BasicBlock -> (y, ud).  bf16 storage: the direct implicit GEMM on bf16 tiles
         and the bf16 weight shadow.  fp32: a 3x3 runs as Winograd F(2x2, 3x3) where the shape allows it (stride 1,
         exact-fp32 mode: 2.25x fewer MFMA FLOPs - the direct kernel already runs at the chip's power-limited fp32 rate),
         else the implicit GEMM.  ud = the transformed dgrad filter when the backward pass will want it (recording), else
         None."""
         if x.dtype in _H16:
-            return ops.bf16_conv2d_fwd(x, self._w16(conv.weight), K, R, R, stride, R // 2), None
+            return ops.bf16_conv2d_fwd(x, wk.w16(conv.weight), K, R, R, stride, R // 2), None
         if R == 3 and stride == 1 and self.use_winograd and ops.winograd_ok(x.shape, K):
             C = x.shape[-1]
-            if self._recording and ops.winograd_ok((x.shape[0], x.shape[1], x.shape[2], K), C):
-                u, ud = ops.winograd_weights(self._w(conv.weight), K, C, self.device, both=True)  # one launch for both
+            if wk.record and ops.winograd_ok((x.shape[0], x.shape[1], x.shape[2], K), C):
+                u, ud = ops.winograd_weights(wk.w(conv.weight), K, C, self.device, both=True)  # one launch for both
                 return ops.conv3x3_winograd(x, u, K), ud
-            u = ops.winograd_weights(self._w(conv.weight), K, C, self.device)
+            u = ops.winograd_weights(wk.w(conv.weight), K, C, self.device)
             return ops.conv3x3_winograd(x, u, K), None
-        return ops.conv2d_fwd(x, self._w(conv.weight), K, R, R, stride, R // 2), None
+        return ops.conv2d_fwd(x, wk.w(conv.weight), K, R, R, stride, R // 2), None
 
-    def _conv_dgrad(self, dy, conv, x_shape, R, stride, out=None, accumulate=False, ud=None):
+    def _conv_dgrad(self, wk, dy, conv, x_shape, R, stride, out=None, accumulate=False, ud=None):
         """data gradient of _conv_fwd; ud: the Winograd dgrad filter recorded by the forward (fp32 storage) or None"""
         if dy.dtype in _H16:
-            return ops.bf16_conv2d_dgrad(dy, self._w16(conv.weight), tuple(x_shape), R, R, stride, R // 2, out=out,
+            return ops.bf16_conv2d_dgrad(dy, wk.w16(conv.weight), tuple(x_shape), R, R, stride, R // 2, out=out,
                                          accumulate=accumulate)
         K = dy.shape[-1]
         if R == 3 and stride == 1 and self.use_winograd and ops.winograd_ok(dy.shape, x_shape[-1]):
             if ud is None:  # (weights are unchanged between forward and backward: normally handed over by the tape)
-                ud = ops.winograd_weights(self._w(conv.weight), K, x_shape[-1], self.device, dgrad=True)
+                ud = ops.winograd_weights(wk.w(conv.weight), K, x_shape[-1], self.device, dgrad=True)
             return ops.conv3x3_winograd(dy, ud, x_shape[-1], out=out, accumulate=accumulate)
-        return ops.conv2d_dgrad(dy, self._w(conv.weight), tuple(x_shape), R, R, stride, R // 2, out=out,
+        return ops.conv2d_dgrad(dy, wk.w(conv.weight), tuple(x_shape), R, R, stride, R // 2, out=out,
                                 accumulate=accumulate)
 
-    def _block_fwd(self, blk, x, train):
+    def _folded_conv(self, wk, x, conv, bn, K, R, stride, relu, residual=None):
+        """R x R inference conv (padding R // 2) with `bn` folded in: act(conv(x) + bias [+ residual]), bias / residual / ReLU
+        in the conv's own epilogue.  16-bit maps: csrc/bgemm.hip (EPI 2); fp32: Winograd where _conv_fwd takes it"""
+        C = x.shape[-1]
+        if x.dtype in _H16:
+            f = wk.folded(conv, bn, K, R * R, C, C, False)
+            return ops.bf16_conv2d_bias_act_fwd(x, f.w.data_ptr(), f.b.data_ptr(), K, R, R, stride, R // 2, relu=relu,
+                                                residual=residual)
+        wino = R == 3 and stride == 1 and self.use_winograd and ops.winograd_ok(x.shape, K)
+        f = wk.folded(conv, bn, K, R * R, C, C, wino)
+        if wino:
+            return ops.conv3x3_winograd_bias_act(x, f.u, f.b.data_ptr(), K, relu=relu, residual=residual)
+        return ops.conv2d_bias_act_fwd(x, f.w.data_ptr(), f.b.data_ptr(), K, R, R, stride, R // 2, relu=relu, residual=residual)
+
+    def _block_fwd(self, wk, blk, x):
         """BasicBlock on fp32 or bf16-stored feature maps (bf16: convs on csrc/bgemm.hip with the bf16 weight shadow,
         BatchNorm reading / writing bf16 with fp32 statistics) -> (out, _BlockRec or None when BN is folded)"""
         K = blk.conv1.out_channels
-        if self._fold_now:
+        if wk.fold:
             # inference: eval-mode BN is an affine map per channel - folded into the conv weights, the block is three
             # (two) convolutions with bias / ReLU / identity epilogues and no BN pass at all
-            Cin = x.shape[-1]
-            eng = self._infer
-            if x.dtype in _H16:
-                # frozen 16-bit engine: the same three (two) convolutions on 16-bit maps, filters and fp32 biases from the
-                # snapshot, bias / residual / ReLU in the conv's own epilogue (csrc/bgemm.hip, EPI 2)
-                def conv16(inp, conv, R, stride, relu, residual=None):
-                    f = eng.folded[id(conv.weight)]
-                    return ops.bf16_conv2d_bias_act_fwd(inp, f.w.data_ptr(), f.b.data_ptr(), K, R, R, stride, R // 2,
-                                                        relu=relu, residual=residual)
-                a1 = conv16(x, blk.conv1, 3, blk.stride, 1)
-                idn = x if blk.downsample is None else conv16(x, blk.downsample[0], 1, blk.stride, 0)
-                return conv16(a1, blk.conv2, 3, 1, 2, residual=idn), None
-
-            def conv3(inp, conv, bn, stride, relu, residual=None):
-                C = inp.shape[-1]
-                wf, bf = self._folded(conv, bn, K, 9, C)
-                if stride == 1 and self.use_winograd and ops.winograd_ok(inp.shape, K):
-                    u = (eng.folded[id(conv.weight)].u if eng is not None
-                         else ops.winograd_weights(wf.data_ptr(), K, C, self.device))
-                    return ops.conv3x3_winograd_bias_act(inp, u, bf.data_ptr(), K, relu=relu, residual=residual)
-                return ops.conv2d_bias_act_fwd(inp, wf.data_ptr(), bf.data_ptr(), K, 3, 3, stride, 1, relu=relu,
-                                               residual=residual)
-
-            a1 = conv3(x, blk.conv1, blk.bn1, blk.stride, 1)
+            a1 = self._folded_conv(wk, x, blk.conv1, blk.bn1, K, 3, blk.stride, 1)
             idn = x
             if blk.downsample is not None:
-                wd, bd = self._folded(blk.downsample[0], blk.downsample[1], K, 1, Cin)
-                idn = ops.conv2d_bias_act_fwd(x, wd.data_ptr(), bd.data_ptr(), K, 1, 1, blk.stride, 0, relu=0)
-            out = conv3(a1, blk.conv2, blk.bn2, 1, 2, residual=idn)
-            return out, None
-        if train and self.fuse_bn_stats16 and x.dtype in _H16:
+                idn = self._folded_conv(wk, x, blk.downsample[0], blk.downsample[1], K, 1, blk.stride, 0)
+            return self._folded_conv(wk, a1, blk.conv2, blk.bn2, K, 3, 1, 2, residual=idn), None
+        if wk.train and self.fuse_bn_stats16 and x.dtype in _H16:
             # bf16 train mode: the conv's epilogue emits the BatchNorm statistics of its (stored) output - no statistics
             # pass (the downsample conv runs before conv2 here)
             def conv_bn(inp, conv, bn, R, stride, pad, relu, residual):
                 stats = torch.empty(2, K, dtype=F32, device=inp.device)
-                c = ops.bf16_conv2d_fwd_bnstats(inp, self._w16(conv.weight), K, R, R, stride, pad, stats[0], stats[1],
+                c = ops.bf16_conv2d_fwd_bnstats(inp, wk.w16(conv.weight), K, R, R, stride, pad, stats[0], stats[1],
                                                 bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self._ws, bn.eps,
                                                 bn.momentum)
-                y = ops.bf16_bn_apply(c, stats[0], stats[1], self._w(bn.weight), self._w(bn.bias), relu, residual)
+                y = ops.bf16_bn_apply(c, stats[0], stats[1], wk.w(bn.weight), wk.w(bn.bias), relu, residual)
                 return c, y, (stats[0], stats[1])
             c1, a1, s1 = conv_bn(x, blk.conv1, blk.bn1, 3, blk.stride, 1, True, None)
             if blk.downsample is not None:
@@ -891,53 +884,54 @@ class TransFuser(nn.Module):
                 cd, sd, idn = None, None, x
             c2, out, s2 = conv_bn(a1, blk.conv2, blk.bn2, 3, 1, 1, True, idn)
             return out, _BlockRec(x, c1, a1, s1, c2, s2, cd, sd, out, None, None)
-        c1, ud1 = self._conv_fwd(x, blk.conv1, K, 3, blk.stride)
-        a1, s1 = self._bn_fwd(blk.bn1, c1, True, None, train)
-        c2, ud2 = self._conv_fwd(a1, blk.conv2, K, 3, 1)
+        c1, ud1 = self._conv_fwd(wk, x, blk.conv1, K, 3, blk.stride)
+        a1, s1 = self._bn_fwd(wk, blk.bn1, c1, True, None)
+        c2, ud2 = self._conv_fwd(wk, a1, blk.conv2, K, 3, 1)
         if blk.downsample is not None:
-            cd, _ = self._conv_fwd(x, blk.downsample[0], K, 1, blk.stride)
-            idn, sd = self._bn_fwd(blk.downsample[1], cd, False, None, train)
+            cd, _ = self._conv_fwd(wk, x, blk.downsample[0], K, 1, blk.stride)
+            idn, sd = self._bn_fwd(wk, blk.downsample[1], cd, False, None)
         else:
             cd, sd, idn = None, None, x
-        out, s2 = self._bn_fwd(blk.bn2, c2, True, idn, train)
+        out, s2 = self._bn_fwd(wk, blk.bn2, c2, True, idn)
         return out, _BlockRec(x, c1, a1, s1, c2, s2, cd, sd, out, ud1, ud2)
 
-    def _gpt_block_fwd(self, blk, x, B, T, train):
+    def _gpt_block_fwd(self, wk, blk, x, B, T):
         """LN -> h -> k|q|v GEMM -> attention -> proj GEMM + dropout + residual -> LN -> h2 -> fc1 + ReLU -> fc2 + dropout +
-        residual, on fp32 or (self._use16) bf16-stored GEMM operands: h, q / k / v, y, h2, f1 bf16 and the weights from
+        residual, on fp32 or (wk.dtype) bf16 / f16-stored GEMM operands: h, q / k / v, y, h2, f1 bf16 and the weights from
         the bf16 shadow, while the residual stream x, x1, x2 and every statistic stay fp32.  Same dropout counters / masks
         in both storages.  -> (x2, _GptRec)"""
-        f16 = self._use16
-        op, w = (_OPS16[self._dt16], self._w16) if f16 else (_F32_OPS, self._w)
+        f16 = wk.dtype != F32
+        op, w32 = _OPS[wk.dtype], wk.w
+        w = wk.w16 if f16 else w32
         cfg = self.config
         C = x.shape[1]
         nh = cfg.n_head
-        pa = cfg.attn_pdrop if train else 0.0
-        pr = cfg.resid_pdrop if train else 0.0
+        pa = cfg.attn_pdrop if wk.train else 0.0
+        pr = cfg.resid_pdrop if wk.train else 0.0
         at = blk.attn
-        h, m1, r1 = op.ln_fwd(x, self._w(blk.ln1.weight), self._w(blk.ln1.bias), blk.ln1.eps)
+        h, m1, r1 = op.ln_fwd(x, w32(blk.ln1.weight), w32(blk.ln1.bias), blk.ln1.eps)
         # one GEMM, columns key | query | value, when the three projections are contiguous (always on the bf16 storage,
         # which runs on the arena only)
-        if f16 or (self.fuse_qkv and self._qkv_fused(at) is not None):
-            kqv = op.lin_fwd(h, w(at.key.weight), self._w(at.key.bias), 3 * C)
+        if f16 or (self.fuse_qkv and self._qkv_fused(at, w32) is not None):
+            kqv = op.lin_fwd(h, w(at.key.weight), w32(at.key.bias), 3 * C)
             k, q, v = kqv[:, :C], kqv[:, C:2 * C], kqv[:, 2 * C:]
         else:
-            q = op.lin_fwd(h, w(at.query.weight), self._w(at.query.bias), C)
-            k = op.lin_fwd(h, w(at.key.weight), self._w(at.key.bias), C)
-            v = op.lin_fwd(h, w(at.value.weight), self._w(at.value.bias), C)
+            q = op.lin_fwd(h, w(at.query.weight), w32(at.query.bias), C)
+            k = op.lin_fwd(h, w(at.key.weight), w32(at.key.bias), C)
+            v = op.lin_fwd(h, w(at.value.weight), w32(at.value.bias), C)
         off_a = self._next_drop(B * nh * T * T) if pa > 0 else 0
         y, lse = op.attn_fwd(q, k, v, B, T, nh, self._ws, pa, self._seed, off_a)
         off_p = self._next_drop(x.numel()) if pr > 0 else 0
-        x1 = op.lin_fwd(y, w(at.proj.weight), self._w(at.proj.bias), C, residual=x, drop_p=pr, seed=self._seed,
+        x1 = op.lin_fwd(y, w(at.proj.weight), w32(at.proj.bias), C, residual=x, drop_p=pr, seed=self._seed,
                         seed_off=off_p)
-        h2, m2, r2 = op.ln_fwd(x1, self._w(blk.ln2.weight), self._w(blk.ln2.bias), blk.ln2.eps)
+        h2, m2, r2 = op.ln_fwd(x1, w32(blk.ln2.weight), w32(blk.ln2.bias), blk.ln2.eps)
         fc1, fc2 = blk.mlp[0], blk.mlp[2]
-        f1 = op.lin_fwd(h2, w(fc1.weight), self._w(fc1.bias), fc1.out_features, relu=True)
+        f1 = op.lin_fwd(h2, w(fc1.weight), w32(fc1.bias), fc1.out_features, relu=True)
         off_m = self._next_drop(x.numel()) if pr > 0 else 0
-        x2 = op.lin_fwd(f1, w(fc2.weight), self._w(fc2.bias), C, residual=x1, drop_p=pr, seed=self._seed, seed_off=off_m)
+        x2 = op.lin_fwd(f1, w(fc2.weight), w32(fc2.bias), C, residual=x1, drop_p=pr, seed=self._seed, seed_off=off_m)
         return x2, _GptRec(x, h, m1, r1, q, k, v, y, lse, off_a, pa, off_p, pr, x1, h2, m2, r2, f1, off_m)
 
-    def _stage_fwd(self, s, feats, gps_src, B, train):
+    def _stage_fwd(self, wk, s, feats, gps_src, B):
         """GPT fusion at scale s (1-based).  feats: 3 NHWC maps.  gps_src: (tensor, ptr, rows_per_group,
         group_stride, K) addressing the (B,2,K) input of vel_emb{s}."""
         L = lib()
@@ -951,32 +945,31 @@ class TransFuser(nn.Module):
         offs = (0, fps[0] * 64, (fps[0] + S) * 64)
         T = (cfg.n_views + 2) * S * 64 + 2
         assert gpt.pos_emb.shape == (1, T, C)
-        pe = cfg.embd_pdrop if train else 0.0
+        pe = cfg.embd_pdrop if wk.train else 0.0
         x0 = torch.empty((B, T, C), dtype=F32, device=self.device)
         off_e = self._next_drop(x0.numel()) if pe > 0 else 0
-        pos = self._w(gpt.pos_emb)
-        f16 = feats[0].dtype in _H16   # 16-bit storage path: feature maps bf16 / f16, tokens fp32
+        pos = wk.w(gpt.pos_emb)
+        fdt = feats[0].dtype   # 16-bit storage: feature maps bf16 / f16, tokens fp32
         for m in range(3):
             N, H = feats[m].shape[0], feats[m].shape[1]
-            assert feats[m].shape == (B * fps[m], H, H, C) and feats[m].dtype == feats[0].dtype
-            (ops._fn("bf16_avgpool_tokens_fwd", feats[m].dtype) if f16 else L.avgpool_tokens_fwd)(
+            assert feats[m].shape == (B * fps[m], H, H, C) and feats[m].dtype == fdt
+            ops._fn("bf16_avgpool_tokens_fwd", fdt)(
                 feats[m].data_ptr(), pos, x0.data_ptr(), N, H, C, fps[m], offs[m], T, pe, self._seed, off_e, st)
         _, gptr, rpg, gstride, K = gps_src
         gemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
-        L.small_linear_fwd(gptr, self._w(vel.weight), self._w(vel.bias), gemb.data_ptr(), 2 * B, C, K, rpg, gstride,
-                           0, st)
+        L.small_linear_fwd(gptr, wk.w(vel.weight), wk.w(vel.bias), gemb.data_ptr(), 2 * B, C, K, rpg, gstride, 0, st)
         L.gps_tokens_fwd(gemb.data_ptr(), pos, x0.data_ptr(), B, C, T, pe, self._seed, off_e, st)
         x = x0.view(B * T, C)
         blk_ctx = []
         for blk in gpt.blocks:
-            x, c = self._gpt_block_fwd(blk, x, B, T, train)
+            x, c = self._gpt_block_fwd(wk, blk, x, B, T)
             blk_ctx.append(c)
-        xo, mf, rf = ops.layernorm_fwd(x, self._w(gpt.ln_f.weight), self._w(gpt.ln_f.bias), gpt.ln_f.eps)
+        xo, mf, rf = ops.layernorm_fwd(x, wk.w(gpt.ln_f.weight), wk.w(gpt.ln_f.bias), gpt.ln_f.eps)
         outs = []
         for m in range(3):
             N, H = feats[m].shape[0], feats[m].shape[1]
             o = torch.empty_like(feats[m])
-            (ops._fn("bf16_upsample_add_fwd", feats[m].dtype) if f16 else L.upsample_add_fwd)(
+            ops._fn("bf16_upsample_add_fwd", fdt)(
                 feats[m].data_ptr(), xo.data_ptr(), o.data_ptr(), N, H, C, fps[m], offs[m], T, st)
             outs.append(o)
         return outs, xo, _StageRec(s, C, T, fps, offs, pe, off_e, gps_src, blk_ctx, x, mf, rf, [f.shape for f in feats])
@@ -995,32 +988,17 @@ class TransFuser(nn.Module):
         clear, also when a launch raises): no later launch of this thread can pick up a stale salt"""
         if record and self.grad_ready_hook is not None:
             self._dp_check_fresh_grads()   # before the forward advances the salt, the BN running stats and _nbt
-        # parameter pointers of this walk: arena base + offset when every parameter still lives in the arena (one pass over
-        # the list instead of ~1250 Tensor.data round trips per step); re-pointed parameters (EMA shadow applied) -> live reads
-        self._wfast = self._wtable if (self._arena is not None and self.params_in_arena()) else None
         try:
-            return self._run_forward_walk(images, lidars, radars, gps, record)
+            return self._run_forward_walk(self._new_walk(record), images, lidars, radars, gps)
         finally:
             lib().set_dropout_salt(0)
-            if not record:
-                self._wfast = None   # a recorded forward keeps the table for its backward walk (cleared in _end_backward)
 
-    def _run_forward_walk(self, images, lidars, radars, gps, record):
+    def _run_forward_walk(self, wk, images, lidars, radars, gps):
+        """-> (logits, _Tape or None) of a forward under walk `wk` (this model's own, or a frozen engine's)"""
         L = lib()
         st = ops._stream()
         cfg = self.config
-        eng = self._infer
-        train = self.training and eng is None   # a frozen engine is always the eval-mode forward
-        self._fold_now = (self.fold_bn_eval and not train and not record) or eng is not None  # inference only: backward needs the BN tape
-        self._recording = bool(record)
-        if eng is not None:   # storage is the engine's, whatever the process-wide compute mode says
-            self._use16 = eng.dtype in _H16
-            if self._use16:
-                self._dt16 = eng.dtype
-        else:
-            self._refresh_shadow16()
-            if self._fold_now:
-                self._use16 = False   # folded inference convs read the fp32 weights (BN folded per call)
+        train, record, w = wk.train, wk.record, wk.w
         S = cfg.seq_len
         if torch.is_tensor(lidars):
             B = lidars.shape[0] // S
@@ -1038,7 +1016,7 @@ class TransFuser(nn.Module):
         streams = self._fork() if self.multi_stream else None
         for m, ((trunk, arch, cin, norm), frames) in enumerate(zip(trunks, (images, lidars, radars))):
             with self._trunk_ctx(streams, m):
-                f, c = self._stem_fwd(trunk, cin, norm, frames, train)
+                f, c = self._stem_fwd(wk, trunk, cin, norm, frames)
             feats.append(f)
             stem_ctx.append(c)
         cap = getattr(self, "_capture", None)  # test hook: name -> list of NHWC / token tensors
@@ -1058,7 +1036,7 @@ class TransFuser(nn.Module):
                 x = feats[m]
                 with self._trunk_ctx(streams, m):
                     for blk in getattr(trunk, f"layer{s}"):
-                        x, c = self._block_fwd(blk, x, train)
+                        x, c = self._block_fwd(wk, blk, x)
                         bc.append(c)
                 feats[m] = x
                 lc.append(bc)
@@ -1067,7 +1045,7 @@ class TransFuser(nn.Module):
             layer_ctx.append(lc)
             if cap is not None:
                 cap[f"layer{s}"] = [f.clone() for f in feats]
-            feats, xo, sc = self._stage_fwd(s, feats, gps_src, B, train)
+            feats, xo, sc = self._stage_fwd(wk, s, feats, gps_src, B)
             if cap is not None:
                 cap[f"gpt{s}"] = xo.clone()
                 cap[f"fused{s}"] = [f.clone() for f in feats]
@@ -1081,7 +1059,7 @@ class TransFuser(nn.Module):
             N = feats[m].shape[0]
             assert feats[m].shape[1:] == (8, 8, 512)
             pl = torch.empty((N, 512), dtype=F32, device=self.device)
-            (ops._fn("bf16_global_pool", feats[m].dtype) if feats[m].dtype in _H16 else L.global_pool)(feats[m].data_ptr(), pl.data_ptr(), N, 512, st)
+            ops._fn("bf16_global_pool", feats[m].dtype)(feats[m].data_ptr(), pl.data_ptr(), N, 512, st)
             pooled.append(pl)
         fused = torch.empty((B, 512), dtype=F32, device=self.device)
         L.head_sum(pooled[0].data_ptr(), pooled[1].data_ptr(), pooled[2].data_ptr(), xo.data_ptr(), fused.data_ptr(), B,
@@ -1092,30 +1070,30 @@ class TransFuser(nn.Module):
         h1 = torch.empty((B, 256), dtype=F32, device=self.device)
         h2 = torch.empty((B, 128), dtype=F32, device=self.device)
         logits = torch.empty((B, 64), dtype=F32, device=self.device)
-        L.small_linear_fwd(fused.data_ptr(), self._w(j0.weight), self._w(j0.bias), h1.data_ptr(), B, 256, 512, B, 0, 1, st)
-        L.small_linear_fwd(h1.data_ptr(), self._w(j2.weight), self._w(j2.bias), h2.data_ptr(), B, 128, 256, B, 0, 1, st)
-        L.small_linear_fwd(h2.data_ptr(), self._w(j4.weight), self._w(j4.bias), logits.data_ptr(), B, 64, 128, B, 0, 0, st)
+        L.small_linear_fwd(fused.data_ptr(), w(j0.weight), w(j0.bias), h1.data_ptr(), B, 256, 512, B, 0, 1, st)
+        L.small_linear_fwd(h1.data_ptr(), w(j2.weight), w(j2.bias), h2.data_ptr(), B, 128, 256, B, 0, 1, st)
+        L.small_linear_fwd(h2.data_ptr(), w(j4.weight), w(j4.bias), logits.data_ptr(), B, 64, 128, B, 0, 0, st)
         gru = None
         if self.gru_head:  # model2_seq_30to5.py:846-862: logits is the GRU's initial hidden state
             T = self.pred_len
             pred = torch.empty((B, T, 64), dtype=F32, device=self.device)
             saved = torch.empty(L.gru_head_saved_floats(B, T), dtype=F32, device=self.device) if record else None
             d = self.decoder
-            L.gru_head_fwd(logits.data_ptr(), self._w(d.weight_ih), self._w(d.weight_hh), self._w(d.bias_ih),
-                           self._w(d.bias_hh), self._w(self.output.weight), self._w(self.output.bias), pred.data_ptr(),
+            L.gru_head_fwd(logits.data_ptr(), w(d.weight_ih), w(d.weight_hh), w(d.bias_ih), w(d.bias_hh),
+                           w(self.output.weight), w(self.output.bias), pred.data_ptr(),
                            0 if saved is None else saved.data_ptr(), B, T, 64, st)
             gru = (logits, saved)
             logits = pred
         tape = None
         if record:
             head = _HeadRec(fused, h1, h2, [f.shape for f in feats], gru, feats[0].dtype)
-            tape = _Tape(B, stem_ctx, layer_ctx, stage_ctx, head, gps, self._salt_cur if train else None)
+            tape = _Tape(B, stem_ctx, layer_ctx, stage_ctx, head, gps, self._salt_cur if train else None, wk)
         return logits, tape
 
     # ================================================================ backward walk =============
-    def _conv_wgrad(self, conv, x, dy, R, stride):
+    def _conv_wgrad(self, wk, conv, x, dy, R, stride):
         """weight gradient of _conv_fwd (bf16 storage: bf16 operands, fp32 gradient)"""
-        gp, acc = self._g(conv.weight)
+        gp, acc = wk.g(conv.weight)
         if x.dtype in _H16:
             self._wg_launch(lambda: ops.bf16_conv2d_wgrad(x, dy, gp, R, R, stride, R // 2, self._ws, accumulate=bool(acc)),
                             (x, dy))
@@ -1161,51 +1139,52 @@ class TransFuser(nn.Module):
             self._wg_used = {}
         self._wg_keep = []
 
-    def _bn_bwd(self, bn, dy, y_mask, x, stats, want_dres=False, relu_no_residual=False):
+    def _bn_bwd(self, wk, bn, dy, y_mask, x, stats, want_dres=False, relu_no_residual=False):
         """backward of _bn_fwd (fp32 or bf16 maps) -> (dx, dresidual or None).  relu_no_residual: y_mask is relu(bn(x))
         itself (bn1 of a block) - its sign is recomputed from x inside the kernels instead of reading the activation
         tensor twice"""
-        gw, aw = self._g(bn.weight)
-        gb, _ = self._g(bn.bias)
+        gw, aw = wk.g(bn.weight)
+        gb, _ = wk.g(bn.bias)
         return (ops.bf16_bn_bwd if dy.dtype in _H16 else ops.bn_bwd)(
-            dy, None if relu_no_residual else y_mask, x, stats[0], stats[1], self._w(bn.weight), gw, gb, self._ws,
-            want_dres=want_dres, accumulate=bool(aw), relu_beta_ptr=self._w(bn.bias) if relu_no_residual else 0)
+            dy, None if relu_no_residual else y_mask, x, stats[0], stats[1], wk.w(bn.weight), gw, gb, self._ws,
+            want_dres=want_dres, accumulate=bool(aw), relu_beta_ptr=wk.w(bn.bias) if relu_no_residual else 0)
 
-    def _block_bwd(self, blk, rec, dout):
+    def _block_bwd(self, wk, blk, rec, dout):
         r = rec
-        dc2, dres = self._bn_bwd(blk.bn2, dout, r.out, r.c2, r.s2, want_dres=True)
-        self._conv_wgrad(blk.conv2, r.a1, dc2, 3, 1)
-        da1 = self._conv_dgrad(dc2, blk.conv2, r.a1.shape, 3, 1, ud=r.ud2)
-        dc1, _ = self._bn_bwd(blk.bn1, da1, r.a1, r.c1, r.s1, relu_no_residual=True)
-        self._conv_wgrad(blk.conv1, r.x, dc1, 3, blk.stride)
+        dc2, dres = self._bn_bwd(wk, blk.bn2, dout, r.out, r.c2, r.s2, want_dres=True)
+        self._conv_wgrad(wk, blk.conv2, r.a1, dc2, 3, 1)
+        da1 = self._conv_dgrad(wk, dc2, blk.conv2, r.a1.shape, 3, 1, ud=r.ud2)
+        dc1, _ = self._bn_bwd(wk, blk.bn1, da1, r.a1, r.c1, r.s1, relu_no_residual=True)
+        self._conv_wgrad(wk, blk.conv1, r.x, dc1, 3, blk.stride)
         if blk.downsample is not None:
-            dcd, _ = self._bn_bwd(blk.downsample[1], dres, None, r.cd, r.sd)
-            self._conv_wgrad(blk.downsample[0], r.x, dcd, 1, blk.stride)
+            dcd, _ = self._bn_bwd(wk, blk.downsample[1], dres, None, r.cd, r.sd)
+            self._conv_wgrad(wk, blk.downsample[0], r.x, dcd, 1, blk.stride)
             # the 3x3 dgrad writes every input pixel; the strided 1x1 only touches the even/even parity class
-            dx = self._conv_dgrad(dc1, blk.conv1, r.x.shape, 3, blk.stride, ud=r.ud1)
-            self._conv_dgrad(dcd, blk.downsample[0], r.x.shape, 1, blk.stride, out=dx, accumulate=True)
+            dx = self._conv_dgrad(wk, dc1, blk.conv1, r.x.shape, 3, blk.stride, ud=r.ud1)
+            self._conv_dgrad(wk, dcd, blk.downsample[0], r.x.shape, 1, blk.stride, out=dx, accumulate=True)
         else:
             dx = dres
-            self._conv_dgrad(dc1, blk.conv1, r.x.shape, 3, blk.stride, out=dx, accumulate=True, ud=r.ud1)
+            self._conv_dgrad(wk, dc1, blk.conv1, r.x.shape, 3, blk.stride, out=dx, accumulate=True, ud=r.ud1)
         return dx
 
-    def _gpt_block_bwd(self, blk, rec, dx2, B, T, dz2=None, next_drop=None):
-        """backward of _gpt_block_fwd on the storage the block was recorded in.  dx2: fp32 gradient of the block output
+    def _gpt_block_bwd(self, wk, blk, rec, dx2, B, T, dz2=None, next_drop=None):
+        """backward of _gpt_block_fwd on the storage the block was recorded in (wk.dtype).  dx2: fp32 gradient of the block output
         (residual stream); dz2: dropout(dx2) on this block's fc2-branch mask in the storage's dtype if the producer of dx2
         already emitted it (fused into its LayerNorm backward), else None (fp32 storage: the block applies the dropout
         itself); next_drop = (p, seed, off) of the block below: the final LayerNorm backward then also emits dropout(dx).
         Returns (dx fp32, dropout(dx) or None)."""
         r = rec
-        f16 = r.h.dtype in _H16
-        op, w = (_OPS16[r.h.dtype], self._w16) if f16 else (_F32_OPS, self._w)
+        f16 = wk.dtype != F32
+        op, w32, g = _OPS[wk.dtype], wk.w, wk.g
+        w = wk.w16 if f16 else w32
         C = r.x.shape[1]
         nh = self.config.n_head
         at = blk.attn
         fc1, fc2 = blk.mlp[0], blk.mlp[2]
 
         def wgrad(lin, x, dy):
-            gw, aw = self._g(lin.weight)
-            gb, _ = self._g(lin.bias)
+            gw, aw = g(lin.weight)
+            gb, _ = g(lin.bias)
             self._wg_launch(lambda: op.lin_wgrad(x, dy, gw, self._ws, accumulate=bool(aw), dbias_ptr=gb), (x, dy))
 
         # x2 = x1 + drop(fc2(f1))
@@ -1215,23 +1194,23 @@ class TransFuser(nn.Module):
         df1 = op.lin_dgrad(dz2, w(fc2.weight), fc1.out_features, relu_mask_src=r.f1)
         wgrad(fc1, r.h2, df1)
         dh2 = op.lin_dgrad(df1, w(fc1.weight), C)
-        g2w, a2 = self._g(blk.ln2.weight)
-        g2b, _ = self._g(blk.ln2.bias)
+        g2w, a2 = g(blk.ln2.weight)
+        g2b, _ = g(blk.ln2.bias)
         # x1 = x + drop(proj(y)): the LayerNorm backward emits dx1 and dropout(dx1) together
-        dx1, dz1 = op.ln_bwd(dh2, r.x1, r.m2, r.r2, self._w(blk.ln2.weight), g2w, g2b, self._ws, add=dx2,
+        dx1, dz1 = op.ln_bwd(dh2, r.x1, r.m2, r.r2, w32(blk.ln2.weight), g2w, g2b, self._ws, add=dx2,
                              accumulate=bool(a2), drop=(r.pr, self._seed, r.off_p))
         wgrad(at.proj, r.y, dz1)
         dy = op.lin_dgrad(dz1, w(at.proj.weight), C)   # bf16 storage: the attention backward's dO
         # the fused [3C, C] weight-gradient block and its [3C] bias block start at key.*: only valid while the three
         # projections' gradients are contiguous arena views with ONE accumulate flag.  fp32 storage falls back to three
         # GEMMs otherwise; the bf16 storage has no such fallback, so it refuses instead of writing wrong slices
-        fused = ((f16 or (self.fuse_qkv and self._qkv_fused(at) is not None))
-                 and self._qkv_fused(at, grads=True) is not None)
+        fused = ((f16 or (self.fuse_qkv and self._qkv_fused(at, w32) is not None))
+                 and self._qkv_fused(at, g, grads=True) is not None)
         if f16 and not fused:
             raise RuntimeError("bf16-storage backward needs key / query / value gradients in the gradient arena with one "
                                "common state (all None or all arena views): call zero_grad(set_to_none=True) first")
         if fused:  # gradients of the fused projection: one [M, 3C] matrix, one wgrad, one dgrad
-            dkqv = torch.empty((dy.shape[0], 3 * C), dtype=op.dtype, device=dy.device)
+            dkqv = torch.empty((dy.shape[0], 3 * C), dtype=wk.dtype, device=dy.device)
             op.attn_bwd(r.q, r.k, r.v, r.y, dy, r.lse, B, T, nh, self._attn_ws(B, T, nh, C), r.pa, self._seed, r.off_a,
                         out=(dkqv[:, C:2 * C], dkqv[:, :C], dkqv[:, 2 * C:]))
             wgrad(at.key, r.h, dkqv)
@@ -1245,16 +1224,16 @@ class TransFuser(nn.Module):
             dh = op.lin_dgrad(dq, w(at.query.weight), C)
             op.lin_dgrad(dk, w(at.key.weight), C, out=dh, accumulate=True)
             op.lin_dgrad(dv, w(at.value.weight), C, out=dh, accumulate=True)
-        g1w, a1 = self._g(blk.ln1.weight)
-        g1b, _ = self._g(blk.ln1.bias)
-        ln1 = (dh, r.x, r.m1, r.r1, self._w(blk.ln1.weight), g1w, g1b, self._ws)
+        g1w, a1 = g(blk.ln1.weight)
+        g1b, _ = g(blk.ln1.bias)
+        ln1 = (dh, r.x, r.m1, r.r1, w32(blk.ln1.weight), g1w, g1b, self._ws)
         if next_drop is not None:   # also dropout(dx) on the mask of the block below
             return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1), drop=next_drop)
         if f16:
             return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1), want_drop=False)
         return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1)), None
 
-    def _stage_bwd(self, rec, dfeats_out, dgps_tok, B):
+    def _stage_bwd(self, wk, rec, dfeats_out, dgps_tok, B):
         """rec: the stage's _StageRec; dfeats_out: grads of the 3 post-fusion maps; dgps_tok: (tensor, bcast) grad of the
         GPS rows of this stage's output.  Returns the grads of the 3 pre-fusion maps and of the GPS input (None at s = 1)."""
         L = lib()
@@ -1263,65 +1242,63 @@ class TransFuser(nn.Module):
         gpt = getattr(self.encoder, f"transformer{s}")
         vel = getattr(self.encoder, f"vel_emb{s}")
         dxo = torch.empty((B * T, C), dtype=F32, device=self.device)
-        f16 = dfeats_out[0].dtype in _H16
         for m in range(3):
             N, H = fshapes[m][0], fshapes[m][1]
-            (ops._fn("bf16_upsample_add_bwd", dfeats_out[m].dtype) if f16 else L.upsample_add_bwd)(dfeats_out[m].data_ptr(), dxo.data_ptr(), N, H, C, fps[m],
-                                                                     offs[m], T, st)
+            ops._fn("bf16_upsample_add_bwd", dfeats_out[m].dtype)(dfeats_out[m].data_ptr(), dxo.data_ptr(), N, H, C, fps[m],
+                                                                  offs[m], T, st)
         gsrc, bcast = dgps_tok
         L.gps_rows(gsrc.data_ptr(), dxo.data_ptr(), B, C, T, 1, 0, int(bcast), st)
-        gfw, af = self._g(gpt.ln_f.weight)
-        gfb, _ = self._g(gpt.ln_f.bias)
+        gfw, af = wk.g(gpt.ln_f.weight)
+        gfb, _ = wk.g(gpt.ln_f.bias)
         rev = list(zip(reversed(list(gpt.blocks)), reversed(rec.blocks)))
         # (resid_pdrop, seed, fc2-branch mask offset) of each block, in backward order; None below the last
         drops = [(bc.pr, self._seed, bc.off_m) for _, bc in rev] + [None]
-        ln_bwd = _OPS16[rec.blocks[0].h.dtype].ln_bwd if rec.blocks and rec.blocks[0].h.dtype in _H16 else ops.layernorm_bwd
-        dx, dz = ln_bwd(dxo, rec.x_last, rec.mf, rec.rf, self._w(gpt.ln_f.weight), gfw, gfb, self._ws, accumulate=bool(af),
-                        drop=drops[0])
+        dx, dz = _OPS[wk.dtype].ln_bwd(dxo, rec.x_last, rec.mf, rec.rf, wk.w(gpt.ln_f.weight), gfw, gfb, self._ws,
+                                       accumulate=bool(af), drop=drops[0])
         for i, (blk, bc) in enumerate(rev):
-            dx, dz = self._gpt_block_bwd(blk, bc, dx, B, T, dz2=dz, next_drop=drops[i + 1])
+            dx, dz = self._gpt_block_bwd(wk, blk, bc, dx, B, T, dz2=dz, next_drop=drops[i + 1])
         self._wg_join()
         dpre = ops.dropout(dx, rec.pe, self._seed, rec.off_e) if rec.pe > 0 else dx
-        gpos, apos = self._g(gpt.pos_emb)
+        gpos, apos = wk.g(gpt.pos_emb)
         L.batch_sum(dpre.data_ptr(), gpos, T * C, B, T * C, apos, st)
         dfeats = []
         for m in range(3):
             N, H = fshapes[m][0], fshapes[m][1]
             d = torch.empty(tuple(fshapes[m]), dtype=dfeats_out[m].dtype, device=self.device)
-            (ops._fn("bf16_avgpool_tokens_bwd", dfeats_out[m].dtype) if f16 else L.avgpool_tokens_bwd)(dpre.data_ptr(), dfeats_out[m].data_ptr(), d.data_ptr(),
-                                                                       N, H, C, fps[m], offs[m], T, st)
+            ops._fn("bf16_avgpool_tokens_bwd", dfeats_out[m].dtype)(dpre.data_ptr(), dfeats_out[m].data_ptr(), d.data_ptr(),
+                                                                    N, H, C, fps[m], offs[m], T, st)
             dfeats.append(d)
         dgemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
         L.gps_rows(dpre.data_ptr(), dgemb.data_ptr(), B, C, T, 0, 0, 0, st)
         _, gptr, rpg, gstride, K = rec.gps_src
-        gw, aw = self._g(vel.weight)
-        gb, _ = self._g(vel.bias)
+        gw, aw = wk.g(vel.weight)
+        gb, _ = wk.g(vel.bias)
         if s > 1:
             dprev = torch.empty((B, 2, K), dtype=F32, device=self.device)
             dptr = dprev.data_ptr()
         else:
             dprev, dptr = None, 0
-        L.small_linear_bwd(dgemb.data_ptr(), 0, gptr, self._w(vel.weight), dptr, gw, gb, 2 * B, C, K, rpg, gstride,
+        L.small_linear_bwd(dgemb.data_ptr(), 0, gptr, wk.w(vel.weight), dptr, gw, gb, 2 * B, C, K, rpg, gstride,
                            2 * B, 0, 0, aw, st)
         return dfeats, dprev
 
-    def _stem_bwd(self, trunk, rec, dpool, cin):
+    def _stem_bwd(self, wk, trunk, rec, dpool, cin):
         L = lib()
         x, c1, st1, idx = rec.x, rec.c1, rec.stats, rec.idx
         bn = trunk.bn1
-        gw_bn, a_bn = self._g(bn.weight)
-        gb_bn, _ = self._g(bn.bias)
+        gw_bn, a_bn = wk.g(bn.weight)
+        gb_bn, _ = wk.g(bn.bias)
         if c1.dtype in _H16:   # the 16-bit stem (csrc/stem.hip)
-            dc1 = ops.bf16_stem_bn_bwd_maxpool(dpool, idx, c1, st1[0], st1[1], self._w(bn.weight), self._w(bn.bias), gw_bn,
+            dc1 = ops.bf16_stem_bn_bwd_maxpool(dpool, idx, c1, st1[0], st1[1], wk.w(bn.weight), wk.w(bn.bias), gw_bn,
                                                gb_bn, self._ws, accumulate=bool(a_bn))
-            gw, aw = self._g(trunk.conv1.weight)
+            gw, aw = wk.g(trunk.conv1.weight)
             self._wg_launch(lambda: ops.bf16_stem_wgrad(x, dc1, gw, cin, self._ws, accumulate=bool(aw)), (x, dc1))
             return
         bwd_pool = ops.bn_bwd_maxpool_bf16in if dpool.dtype in _H16 else ops.bn_bwd_maxpool
-        dc1 = bwd_pool(dpool, idx, c1, st1[0], st1[1], self._w(bn.weight), self._w(bn.bias), gw_bn, gb_bn,
+        dc1 = bwd_pool(dpool, idx, c1, st1[0], st1[1], wk.w(bn.weight), wk.w(bn.bias), gw_bn, gb_bn,
                        self._ws, accumulate=bool(a_bn))
         dwpad = torch.empty((64, 7, 7, 4), dtype=F32, device=self.device)
-        gw, aw = self._g(trunk.conv1.weight)
+        gw, aw = wk.g(trunk.conv1.weight)
 
         def stem_wgrad():
             ops.conv2d_wgrad(x, dc1, dwpad.data_ptr(), 7, 7, 2, 3, self._ws)
@@ -1333,16 +1310,16 @@ class TransFuser(nn.Module):
             self._run_backward_walk(tape, dlogits)
         finally:
             lib().set_dropout_salt(0)
-            self._wfast = None
 
     def _run_backward_walk(self, tape, dlogits):
         L = lib()
         st = ops._stream()
         cfg = self.config
-        B, head = tape.B, tape.head
+        B, head, wk = tape.B, tape.head, tape.walk
+        w = wk.w
         fshapes, gru, fdtype = head.fshapes, head.gru, head.fdtype
         L.set_dropout_salt(tape.salt.data_ptr() if tape.salt is not None else 0)
-        self._begin_backward()
+        self._begin_backward(wk)
         if gru is not None:  # back through the GRU head: dpred (B, pred_len, 64) -> gradient of the join output
             z0, saved = gru
             T = self.pred_len
@@ -1351,11 +1328,11 @@ class TransFuser(nn.Module):
             slabs = torch.empty((B, npar), dtype=F32, device=self.device)
             dz = torch.empty((B, 64), dtype=F32, device=self.device)
             d = self.decoder
-            L.gru_head_bwd(dlogits.contiguous().data_ptr(), z0.data_ptr(), saved.data_ptr(), self._w(d.weight_ih),
-                           self._w(d.weight_hh), self._w(self.output.weight), dz.data_ptr(), slabs.data_ptr(), B, T, 64, st)
+            L.gru_head_bwd(dlogits.contiguous().data_ptr(), z0.data_ptr(), saved.data_ptr(), w(d.weight_ih),
+                           w(d.weight_hh), w(self.output.weight), dz.data_ptr(), slabs.data_ptr(), B, T, 64, st)
             off = 0
             for prm in (d.weight_ih, d.weight_hh, d.bias_ih, d.bias_hh, self.output.weight, self.output.bias):
-                gp, acc = self._g(prm)
+                gp, acc = wk.g(prm)
                 L.batch_sum(slabs.data_ptr() + 4 * off, gp, prm.numel(), B, npar, acc, st)
                 off += prm.numel()
             dlogits = dz
@@ -1368,10 +1345,10 @@ class TransFuser(nn.Module):
         dfused = torch.empty_like(fused)
 
         def small_bwd(lin, dy, ymask, x, dx, M, N, K):
-            gw, aw = self._g(lin.weight)
-            gb, _ = self._g(lin.bias)
+            gw, aw = wk.g(lin.weight)
+            gb, _ = wk.g(lin.bias)
             L.small_linear_bwd(dy.data_ptr(), 0 if ymask is None else ymask.data_ptr(), x.data_ptr(),
-                               self._w(lin.weight), dx.data_ptr(), gw, gb, M, N, K, M, 0, M, 0, 0, aw, st)
+                               w(lin.weight), dx.data_ptr(), gw, gb, M, N, K, M, 0, M, 0, 0, aw, st)
 
         small_bwd(j4, dlogits, None, h2, dh2, B, 64, 128)
         small_bwd(j2, dh2, h2, h1, dh1, B, 128, 256)
@@ -1382,12 +1359,11 @@ class TransFuser(nn.Module):
         for m in range(3):
             d = torch.empty(tuple(fshapes[m]), dtype=fdtype, device=self.device)
             fps = cfg.n_views * S if m == 0 else S
-            (ops._fn("bf16_head_bwd", fdtype) if fdtype in _H16 else L.head_bwd)(dfused.data_ptr(), d.data_ptr(), fshapes[m][0], 512,
-                                                                        fps, st)
+            ops._fn("bf16_head_bwd", fdtype)(dfused.data_ptr(), d.data_ptr(), fshapes[m][0], 512, fps, st)
             dfeats.append(d)
         dgps = (dfused, True)
         for s in range(4, 0, -1):
-            dfeats, dprev = self._stage_bwd(tape.stages[s - 1], dfeats, dgps, B)
+            dfeats, dprev = self._stage_bwd(wk, tape.stages[s - 1], dfeats, dgps, B)
             self._milestone_done(1 + 2 * (4 - s))
             dgps = (dprev, False)
             streams = self._fork() if self.multi_stream else None
@@ -1396,9 +1372,9 @@ class TransFuser(nn.Module):
                 d = dfeats[m]
                 with self._trunk_ctx(streams, m):
                     for blk, bc in zip(reversed(blocks), reversed(tape.layers[s - 1][m])):
-                        d = self._block_bwd(blk, bc, d)
+                        d = self._block_bwd(wk, blk, bc, d)
                     if s == 1:  # the stem backward continues on the same trunk stream
-                        self._stem_bwd(trunk, tape.stems[m], d, cin)
+                        self._stem_bwd(wk, trunk, tape.stems[m], d, cin)
                 dfeats[m] = d
             if streams is not None:
                 self._join()

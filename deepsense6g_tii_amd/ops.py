@@ -418,9 +418,11 @@ def _chk16(t, *shape, dtype=None):
 
 
 def _fn(name, dtype):
-    """the C entry point `name` (a bf16 one) for 16-bit storage of `dtype`"""
-    assert dtype in (BF16, F16), dtype
-    return getattr(lib(), name if dtype == BF16 else name.replace("bf16", "f16"))
+    """the C entry point `name` (a bf16 one) for storage `dtype`: its f16 twin, or (a "bf16_" name) the fp32 kernel it mirrors"""
+    if dtype != BF16:
+        assert dtype in (F32, F16), dtype
+        name = name.replace("bf16", "f16") if dtype == F16 else name.removeprefix("bf16_")
+    return getattr(lib(), name)
 
 
 def bf16_linear_fwd(x, w16_ptr, b_ptr, N, relu=False, residual=None, drop_p=0.0, seed=0, seed_off=0, out16=True):

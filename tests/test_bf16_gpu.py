@@ -145,9 +145,12 @@ def test_model_bf16_gradients_against_the_bf16_rounding_floor(dev, bf16_mode):
     model.load_state_dict(sd)
     model.train()
     imgs, lids, rads, gps, target, _ = fr.make_inputs(rcfg, 2, seed=100)
+    tapes, run_backward = [], model._run_backward
+    model._run_backward = lambda tape, dlogits: (tapes.append(tape), run_backward(tape, dlogits))   # the step's own tape
     loss, logits = model.train_step_loss(imgs, lids, rads, gps, target)
     torch.cuda.synchronize()
-    assert model._use16, "the bf16-storage path must be the one that ran"
+    assert tapes[0].walk.dtype == tapes[0].stages[0].blocks[0].h.dtype == torch.bfloat16, \
+        "the bf16-storage path must be the one that ran"
     hip = {n: p.grad.detach().cpu() for n, p in model.named_parameters()}
     # fp32 oracle (logit reference), bf16-autocast oracle (the floor), fp64 oracle (the yardstick)
     with torch.no_grad():

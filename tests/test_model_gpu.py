@@ -354,7 +354,7 @@ def test_gpt_stage_alone_matches_reference_fixture_and_oracle_gradients(dev):
     mis-scaled LayerNorm beta, bias or pos_emb gradient cannot hide behind conditioning)."""
     from deepsense6g_tii_amd import ops
     from deepsense6g_tii_amd._lib import lib
-    from deepsense6g_tii_amd.model import GlobalConfig, TransFuser
+    from deepsense6g_tii_amd.model import GlobalConfig, TransFuser, _live_ptr, _Walk
     from oracle import fusion_ref as fr
     gold = np.load(GOLD)
     kw = dict(seq_len=1, n_layer=2, embd_pdrop=0.0, attn_pdrop=0.0, resid_pdrop=0.0)
@@ -376,10 +376,10 @@ def test_gpt_stage_alone_matches_reference_fixture_and_oracle_gradients(dev):
         L.avgpool_tokens_fwd(feats[m].data_ptr(), pos, x0.data_ptr(), B * S, 8, C, S, m * S * 64, T, 0.0, 0, 0, st)
     gemb = gps.to(dev).contiguous()
     L.gps_tokens_fwd(gemb.data_ptr(), pos, x0.data_ptr(), B, C, T, 0.0, 0, 0, st)
-    model._recording, model._use16 = True, False
+    wk = _Walk(_live_ptr, train=True, record=True)   # fp32 storage, BatchNorm not folded
     x, ctxs = x0.view(B * T, C), []
     for blk in gpt.blocks:
-        x, c = model._gpt_block_fwd(blk, x, B, T, True)
+        x, c = model._gpt_block_fwd(wk, blk, x, B, T)
         ctxs.append(c)
     xo, mf, rf = ops.layernorm_fwd(x, gpt.ln_f.weight.data_ptr(), gpt.ln_f.bias.data_ptr(), gpt.ln_f.eps)
     out = xo.view(B, T, C).cpu()
@@ -396,15 +396,15 @@ def test_gpt_stage_alone_matches_reference_fixture_and_oracle_gradients(dev):
     (flat * up).sum().backward()
     for p in model.parameters():
         p.grad = None
-    model._begin_backward()
-    gw, aw = model._g(gpt.ln_f.weight)
-    gb, _ = model._g(gpt.ln_f.bias)
+    model._begin_backward(wk)
+    gw, aw = wk.g(gpt.ln_f.weight)
+    gb, _ = wk.g(gpt.ln_f.bias)
     dx = ops.layernorm_bwd(up.view(B * T, C).to(dev).contiguous(), x, mf, rf, gpt.ln_f.weight.data_ptr(), gw, gb, model._ws,
                            accumulate=bool(aw))
     for blk, c in zip(reversed(list(gpt.blocks)), reversed(ctxs)):
-        dx, _ = model._gpt_block_bwd(blk, c, dx, B, T)
+        dx, _ = model._gpt_block_bwd(wk, blk, c, dx, B, T)
     model._wg_join()
-    gpos, apos = model._g(gpt.pos_emb)
+    gpos, apos = wk.g(gpt.pos_emb)
     L.batch_sum(dx.data_ptr(), gpos, T * C, B, T * C, apos, st)
     model._end_backward()
     torch.cuda.synchronize()
@@ -429,7 +429,7 @@ def test_basic_block_alone_gradients_match_torch_autograd(dev, layer, idx):
     each tensor's largest entry (the whole-model gradient bars are necessarily loose - ill-conditioned
     ReLU / max-pool decisions over 34 layers - so a mis-scaled BN beta or downsample gradient is pinned here instead)."""
     import torch.nn.functional as F
-    from deepsense6g_tii_amd.model import GlobalConfig, TransFuser
+    from deepsense6g_tii_amd.model import GlobalConfig, TransFuser, _live_ptr, _Walk
     kw = dict(n_layer=1, embd_pdrop=0.0, attn_pdrop=0.0, resid_pdrop=0.0)
     torch.manual_seed(5)
     model = TransFuser(GlobalConfig(**kw), dev)
@@ -455,14 +455,14 @@ def test_basic_block_alone_gradients_match_torch_autograd(dev, layer, idx):
     dy = torch.randn(y.shape, generator=g)
     y.backward(dy)
     # ---- HIP kernels through the model's own block walk
-    model._recording, model._use16, model._fold_now = True, False, False
+    wk = _Walk(_live_ptr, train=True, record=True)   # fp32 storage, BatchNorm not folded
     xg = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    yg, ctx = model._block_fwd(blk, xg, True)
+    yg, ctx = model._block_fwd(wk, blk, xg)
     assert rel(yg.cpu().permute(0, 3, 1, 2), y.detach()) < 2e-5
     for p in model.parameters():
         p.grad = None
-    model._begin_backward()
-    dxg = model._block_bwd(blk, ctx, dy.permute(0, 2, 3, 1).contiguous().to(dev))
+    model._begin_backward(wk)
+    dxg = model._block_bwd(wk, blk, ctx, dy.permute(0, 2, 3, 1).contiguous().to(dev))
     model._wg_join()
     model._end_backward()
     torch.cuda.synchronize()

@@ -4,13 +4,13 @@ and each other's launch ramps / tails).  Prints ms per chain for C in 64..512.""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from deepsense6g_tii_amd.model import GlobalConfig, TransFuser
+from deepsense6g_tii_amd.model import GlobalConfig, TransFuser, _live_ptr, _Walk
 
 dev = torch.device("cuda:0")
 cfg = GlobalConfig()
 model = TransFuser(cfg, dev)
 model.train()
-model._recording = True
+wk = _Walk(_live_ptr, train=True, record=True)   # fp32 storage, BatchNorm not folded
 B, T = 12, 962
 streams = [torch.cuda.Stream(dev) for _ in range(2)]
 from deepsense6g_tii_amd import ops
@@ -21,11 +21,11 @@ for st in streams:
 def chain(gpt, x, Bh, wg=True):
     ctxs = []
     for blk in gpt.blocks:
-        x, c = model._gpt_block_fwd(blk, x, Bh, T, True)
+        x, c = model._gpt_block_fwd(wk, blk, x, Bh, T)
         ctxs.append(c)
     dx = torch.ones_like(x)
     for blk, c in zip(reversed(list(gpt.blocks)), reversed(ctxs)):
-        dx, _ = model._gpt_block_bwd(blk, c, dx, Bh, T)
+        dx, _ = model._gpt_block_bwd(wk, blk, c, dx, Bh, T)
     return dx
 
 
@@ -36,7 +36,7 @@ for s in (1, 2, 3, 4):
     for mode in ("one", "two"):
         for p in model.parameters():
             p.grad = None
-        model._begin_backward()
+        model._begin_backward(wk)
         model.overlap_wgrad = True
 
         def run():
