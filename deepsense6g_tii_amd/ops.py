@@ -761,3 +761,94 @@ def attention_bwd_bf16io(q, k, v, o, d_o, lse, B, T, nh, ws: Workspace, drop_p=0
     _fn("attention_bwd_bf16io", q.dtype)(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, T, nh,
                                C // nh, ldq, C, ldd, float(drop_p), seed, seed_off, ws.ptr, ws.nbytes, _stream())
     return dq, dk, dv
+
+
+# ------------------------------------------------------------------------------------------------
+# Mamba layer (csrc/mamba.hip): token-major [B*L, D] operands that may be column blocks of a wider matrix
+def _rows_al(t, M, C):
+    ld = _rows(t, M, C)
+    assert t.data_ptr() % 16 == 0 and (M == 1 or ld >= C), (t.data_ptr(), ld, C)
+    return max(ld, C)   # a one-row view reports an arbitrary stride
+
+
+def _vec(t, *shape):
+    assert t.dtype == F32 and t.is_cuda and t.is_contiguous() and t.numel() == _prod(shape) and t.data_ptr() % 16 == 0, \
+        (t.dtype, t.device, tuple(t.shape), shape)
+    return t.data_ptr()
+
+
+def _prod(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
+
+
+def selective_scan_chunk():
+    return int(lib().selective_scan_chunk())
+
+
+def copy_cols(src, dst):
+    """dst[:, :] = src[:, :] for two [M, C] views of different row strides (C % 4 == 0)"""
+    M, C = src.shape
+    assert C % 4 == 0 and M > 0
+    lib().copy_cols(_p(src), _rows_al(src, M, C), _p(dst), _rows_al(dst, M, C), M, C, _stream())
+    return dst
+
+
+def causal_conv1d_silu_fwd(x, w, bias, B, L, reverse=False):
+    """silu(causal depthwise conv1d(x) + bias): x [B*L, D] (a column block allowed), w conv1d.weight (D, 1, 4) -> [B*L, D]"""
+    M, D = x.shape
+    assert M == B * L and D % 128 == 0
+    y = torch.empty((M, D), dtype=F32, device=x.device)
+    lib().causal_conv1d_silu_fwd(_p(x), _rows_al(x, M, D), _vec(w, D, 1, 4), _vec(bias, D), _p(y), D, B, L, D, int(reverse),
+                                 _stream())
+    return y
+
+
+def causal_conv1d_silu_bwd(x, w, bias, dy, dx, B, L, ws: Workspace, reverse=False):
+    """-> (dw (D, 1, 4), dbias (D,)); dx [B*L, D] is written in place (a column block allowed)"""
+    M, D = x.shape
+    assert M == B * L and D % 128 == 0
+    assert ws.nbytes >= int(lib().causal_conv1d_workspace_bytes(B, L, D)), "workspace too small for causal_conv1d_silu_bwd"
+    dw = torch.empty((D, 1, 4), dtype=F32, device=x.device)
+    db = torch.empty((D,), dtype=F32, device=x.device)
+    lib().causal_conv1d_silu_bwd(_p(x), _rows_al(x, M, D), _vec(w, D, 1, 4), _vec(bias, D), _p(dy), _rows_al(dy, M, D),
+                                 _p(dx), _rows_al(dx, M, D), _p(dw), _p(db), B, L, D, int(reverse), ws.ptr, ws.nbytes,
+                                 _stream())
+    return dw, db
+
+
+def selective_scan_fwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, B, L, ws: Workspace, reverse=False, save=False):
+    """-> (y [B*L, D], saved or None).  u / delta_raw / z: [B*L, D], Bm / Cm: [B*L, 16] (column blocks allowed);
+    dt_bias, Dp: (D,), A_log: (D, 16).  save: also return the chunk-start states selective_scan_bwd needs."""
+    M, D = u.shape
+    assert M == B * L and D % 128 == 0
+    assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_fwd"
+    y = torch.empty((M, D), dtype=F32, device=u.device)
+    saved = torch.empty(int(lib().selective_scan_saved_floats(B, L, D)), dtype=F32, device=u.device) if save else None
+    lib().selective_scan_fwd(_p(u), _rows_al(u, M, D), _p(delta_raw), _rows_al(delta_raw, M, D), _vec(dt_bias, D),
+                             _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16), _vec(Dp, D),
+                             _p(z), _rows_al(z, M, D), _p(y), D, _p(saved), B, L, D, int(reverse), ws.ptr, ws.nbytes,
+                             _stream())
+    return y, saved
+
+
+def selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, du, ddelta, dBm, dCm, dz, B, L,
+                       ws: Workspace, reverse=False):
+    """writes du, ddelta (= d delta_raw), dz [B*L, D] and dBm, dCm [B*L, 16] in place (column blocks allowed)
+    -> (dA_log (D, 16), dD (D,))"""
+    M, D = u.shape
+    assert M == B * L and D % 128 == 0
+    assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_bwd"
+    assert saved.dtype == F32 and saved.is_cuda and saved.is_contiguous() and \
+        saved.numel() == int(lib().selective_scan_saved_floats(B, L, D)), tuple(saved.shape)
+    dA = torch.empty((D, 16), dtype=F32, device=u.device)
+    dD = torch.empty((D,), dtype=F32, device=u.device)
+    lib().selective_scan_bwd(_p(u), _rows_al(u, M, D), _p(delta_raw), _rows_al(delta_raw, M, D), _vec(dt_bias, D),
+                             _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16), _vec(Dp, D),
+                             _p(z), _rows_al(z, M, D), _p(dy), _rows_al(dy, M, D), _p(saved), _p(du), _rows_al(du, M, D),
+                             _p(ddelta), _rows_al(ddelta, M, D), _p(dBm), _rows_al(dBm, M, 16), _p(dCm),
+                             _rows_al(dCm, M, 16), _p(dz), _rows_al(dz, M, D), _p(dA), _p(dD), B, L, D, int(reverse),
+                             ws.ptr, ws.nbytes, _stream())
+    return dA, dD

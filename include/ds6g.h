@@ -323,6 +323,47 @@ int ds6g_gru_head_fwd(const float* h0, const float* w_ih, const float* w_hh, con
 int ds6g_gru_head_bwd(const float* dpred, const float* h0, const float* saved, const float* w_ih, const float* w_hh,
                       const float* w_out, float* dh0, float* slabs, int B, int T, int H, void* stream);
 
+/* ---- mamba.hip : the two non-GEMM operators of mamba_ssm.Mamba(d_model, d_state=16, d_conv=4, expand=2), the layer under
+ * every model the reference's training script builds (mambafuser_seq.py:83-101 MambaBlock's forward / backward_mamba pair,
+ * :240 MambaFusion, :261-263 TimeMamba); the four projections are ds6g_linear_*.  Token-major fp32: row = b * L + t, D =
+ * d_inner channels contiguous; every operand is pointer + row stride in floats (stride >= width, % 4 == 0, pointers 16-byte
+ * aligned), so x / z are read as the column halves of in_proj's output and dt / Bm / Cm as column slices of x_proj's.
+ * D % 128 == 0.  reverse != 0 walks each sequence back to front (the result of flip -> op -> flip, without the copies).
+ *   causal_conv1d_silu   y_t = silu(bias + sum_k w[d][k] x_{t-3+k}), zeros before t = 0; w: conv1d.weight (D, 1, 4).  bwd
+ *                        recomputes the pre-activation from x; dw / dbias are written (not accumulated) from per-workgroup
+ *                        partials reduced in a fixed order.  ws >= ds6g_causal_conv1d_workspace_bytes.
+ *   selective_scan_fwd   delta = softplus(delta_raw + dt_bias) (v > 20: v); h_t = exp(delta_t A) h_{t-1} + delta_t u_t Bm_t,
+ *                        A = -exp(A_log) (D, 16); y_t = (<h_t, Cm_t> + Dp u_t) silu(z_t).  The sequence is cut into chunks
+ *                        of ds6g_selective_scan_chunk() positions that run in parallel (state pass, carry over the chunks,
+ *                        emitting pass).  saved (nullable): ds6g_selective_scan_saved_floats floats, the states at the chunk
+ *                        starts (B, chunks, D, 16) - the only tape the backward needs beside the operands.
+ *   selective_scan_bwd   du, d delta_raw, dz (D wide each), dBm / dCm (16 wide; summed over the channels), dA_log (D, 16)
+ *                        and dD (D) (summed over the tokens), all written, not accumulated.  Recomputes the states of a chunk
+ *                        from its checkpoint; never divides by exp(delta A).  Deterministic (partial slabs, fixed order).
+ *   ws of both scans >= ds6g_selective_scan_workspace_bytes.  The three size queries are host-only.
+ *   copy_cols            dst[r][0..cols) = src[r][0..cols) between two row strides (packs the dt slice of x_proj's output
+ *                        for the dt_proj GEMM and unpacks its gradient); cols % 4 == 0. */
+int ds6g_selective_scan_chunk(void);
+size_t ds6g_selective_scan_saved_floats(int B, int L, int D);
+size_t ds6g_selective_scan_workspace_bytes(int B, int L, int D);
+size_t ds6g_causal_conv1d_workspace_bytes(int B, int L, int D);
+int ds6g_causal_conv1d_silu_fwd(const float* x, int ld_x, const float* w, const float* bias, float* y, int ld_y, int B,
+                                int L, int D, int reverse, void* stream);
+int ds6g_causal_conv1d_silu_bwd(const float* x, int ld_x, const float* w, const float* bias, const float* dy, int ld_dy,
+                                float* dx, int ld_dx, float* dw, float* dbias, int B, int L, int D, int reverse, void* ws,
+                                size_t ws_bytes, void* stream);
+int ds6g_selective_scan_fwd(const float* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                            const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                            const float* z, int ld_z, float* y, int ld_y, float* saved, int B, int L, int D, int reverse,
+                            void* ws, size_t ws_bytes, void* stream);
+int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                            const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                            const float* z, int ld_z, const float* dy, int ld_dy, const float* saved, float* du, int ld_du,
+                            float* ddelta, int ld_ddelta, float* dBm, int ld_dbm, float* dCm, int ld_dcm, float* dz,
+                            int ld_dz, float* dA_log, float* dD, int B, int L, int D, int reverse, void* ws,
+                            size_t ws_bytes, void* stream);
+int ds6g_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, long rows, int cols, void* stream);
+
 /* ---- spatial.hip -------------------------------------------------------------------------------*/
 /* normalize_imagenet + stack + NCHW->NHWC: model2_seq.py:36-45,481-482,491-493 */
 int ds6g_pack_input(const float* src, float* dst, int B, int Cs, int H, int W, int Cd, int frames_per_sample, int t,

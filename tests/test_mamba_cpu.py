@@ -1,0 +1,158 @@
+"""CPU-side checks of the Mamba layer: the pure-torch restatement (tests/mamba_ref.py) is self-consistent, the module keeps
+mamba_ssm's parameter contract, and every new C entry point refuses bad arguments on the host before any launch."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from deepsense6g_tii_amd import _lib
+from tests import mamba_ref as mr
+
+
+@pytest.mark.parametrize("wide", [False, True])
+def test_restatement_fp32_tracks_fp64(wide):
+    p = mr.make_params(64, seed=3, wide=wide)
+    u, dout = mr.make_input(64, 2, 37, seed=3, wide=wide)
+    for reverse in (False, True):
+        r64 = mr.layer_run(p, u, dout, reverse, torch.float64)
+        r32 = mr.layer_run(p, u, dout, reverse, torch.float32)
+        for k in r64:
+            assert mr.rel_err(r32[k], r64[k]) <= 1e-5, k
+
+
+def test_restatement_reverse_is_flip_forward_flip():
+    p = mr.make_params(64, seed=4)
+    u, _ = mr.make_input(64, 2, 19, seed=4)
+    with torch.no_grad():
+        a = mr.mamba_ref(p, u, reverse=True)
+        b = mr.mamba_ref(p, u.flip(1), reverse=False).flip(1)
+    assert torch.equal(a, b)
+
+
+def test_restatement_single_token_has_zero_dA_log():
+    p = mr.make_params(64, seed=5)
+    u, dout = mr.make_input(64, 2, 1, seed=5)
+    r = mr.layer_run(p, u, dout, False, torch.float64)
+    assert (r["A_log"] == 0).all() and r["out"].abs().max() > 0
+
+
+def test_module_contract():
+    from deepsense6g_tii_amd.mamba import Mamba
+    torch.manual_seed(0)
+    m = Mamba(64)
+    sd = m.state_dict()
+    want = mr.shapes(64)
+    assert set(sd) == set(mr.NAMES) and len(sd) == 9
+    for k in mr.NAMES:
+        assert tuple(sd[k].shape) == want[k] and sd[k].dtype == torch.float32, k
+    assert torch.equal(sd["A_log"], torch.log(torch.arange(1, 17, dtype=torch.float32)).repeat(128, 1))
+    assert (sd["D"] == 1).all()
+    dt = F.softplus(sd["dt_proj.bias"])
+    assert dt.min() >= 1e-3 * (1 - 1e-5) and dt.max() <= 0.1 * (1 + 1e-5)
+    assert sd["dt_proj.weight"].abs().max() <= 4 ** -0.5
+    assert {n for n, _ in m.named_parameters()} == set(mr.NAMES)
+    p = {k: v.float() for k, v in mr.make_params(64, seed=1, wide=True).items()}
+    m.load_state_dict(p, strict=True)
+    for k in mr.NAMES:
+        assert torch.equal(m.state_dict()[k], p[k]), k
+    for kw in (dict(d_state=8), dict(d_conv=3), dict(bias=True), dict(conv_bias=False), dict(dtype=torch.bfloat16)):
+        with pytest.raises(ValueError):
+            Mamba(64, **kw)
+    with pytest.raises(ValueError):
+        Mamba(48)
+    assert Mamba(128, dt_rank="auto").dt_rank == 8 and Mamba(512).x_proj.weight.shape == (64, 1024)
+    with pytest.raises(RuntimeError):
+        m(torch.zeros(1, 4, 64))
+
+
+P = 0x1000   # a non-NULL, 16-byte aligned stand-in: every call below must be refused before anything is launched
+
+
+def _conv_fwd(L, x=P, w=P, bias=P, y=P, ld_x=128, ld_y=128, B=2, Lq=8, D=128):
+    return L.causal_conv1d_silu_fwd(x, ld_x, w, bias, y, ld_y, B, Lq, D, 0, 0)
+
+
+def _conv_bwd(L, ptrs=(P,) * 7, lds=(128,) * 3, B=2, Lq=8, D=128, ws=P, ws_bytes=1 << 20):
+    x, w, bias, dy, dx, dw, db = ptrs
+    return L.causal_conv1d_silu_bwd(x, lds[0], w, bias, dy, lds[1], dx, lds[2], dw, db, B, Lq, D, 0, ws, ws_bytes, 0)
+
+
+def _scan_fwd(L, ptrs=(P,) * 9, lds=(128, 128, 16, 16, 128, 128), B=2, Lq=8, D=128, ws=P, ws_bytes=1 << 24):
+    u, raw, dtb, A, Bm, Cm, Dp, z, y = ptrs
+    return L.selective_scan_fwd(u, lds[0], raw, lds[1], dtb, A, Bm, lds[2], Cm, lds[3], Dp, z, lds[4], y, lds[5], 0, B, Lq, D,
+                                0, ws, ws_bytes, 0)
+
+
+def _scan_bwd(L, ptrs=(P,) * 17, lds=(128, 128, 16, 16, 128, 128, 128, 128, 16, 16, 128), B=2, Lq=8, D=128, ws=P,
+              ws_bytes=1 << 24):
+    u, raw, dtb, A, Bm, Cm, Dp, z, dy, saved, du, dd, dB, dC, dz, dA, dD = ptrs
+    return L.selective_scan_bwd(u, lds[0], raw, lds[1], dtb, A, Bm, lds[2], Cm, lds[3], Dp, z, lds[4], dy, lds[5], saved, du,
+                                lds[6], dd, lds[7], dB, lds[8], dC, lds[9], dz, lds[10], dA, dD, B, Lq, D, 0, ws, ws_bytes, 0)
+
+
+def _each_null(n):
+    for i in range(n):
+        yield tuple(0 if j == i else P for j in range(n))
+
+
+def _each_short(lds):
+    for i, ld in enumerate(lds):
+        yield tuple(ld - 4 if j == i else v for j, v in enumerate(lds))
+        yield tuple(ld + 2 if j == i else v for j, v in enumerate(lds))   # not a multiple of 4
+
+
+def test_entry_points_reject_bad_arguments_without_launching():
+    L = _lib.lib()
+    E = _lib.Ds6gError
+    for bad in (dict(x=0), dict(w=0), dict(bias=0), dict(y=0), dict(Lq=0), dict(Lq=-3), dict(B=0), dict(D=64), dict(ld_x=124),
+                dict(ld_y=124), dict(ld_x=130), dict(x=P + 4)):
+        with pytest.raises(E, match="code 1$"):
+            _conv_fwd(L, **bad)
+    for ptrs in _each_null(7):
+        with pytest.raises(E, match="code 1$"):
+            _conv_bwd(L, ptrs=ptrs)
+    for lds in _each_short((128,) * 3):
+        with pytest.raises(E, match="code 1$"):
+            _conv_bwd(L, lds=lds)
+    for bad in (dict(Lq=0), dict(ws=0), dict(ws_bytes=int(L.causal_conv1d_workspace_bytes(2, 8, 128)) - 1)):
+        with pytest.raises(E, match="code 1$"):
+            _conv_bwd(L, **bad)
+    for ptrs in _each_null(9):
+        with pytest.raises(E, match="code 1$"):
+            _scan_fwd(L, ptrs=ptrs)
+    for lds in _each_short((128, 128, 16, 16, 128, 128)):
+        with pytest.raises(E, match="code 1$"):
+            _scan_fwd(L, lds=lds)
+    need = int(L.selective_scan_workspace_bytes(2, 8, 128))
+    for bad in (dict(Lq=0), dict(Lq=-1), dict(B=0), dict(D=0), dict(D=144), dict(ws=0), dict(ws_bytes=need - 1)):
+        with pytest.raises(E, match="code 1$"):
+            _scan_fwd(L, **bad)
+    for ptrs in _each_null(17):
+        with pytest.raises(E, match="code 1$"):
+            _scan_bwd(L, ptrs=ptrs)
+    for lds in _each_short((128, 128, 16, 16, 128, 128, 128, 128, 16, 16, 128)):
+        with pytest.raises(E, match="code 1$"):
+            _scan_bwd(L, lds=lds)
+    for bad in (dict(Lq=0), dict(ws=0), dict(ws_bytes=need - 1)):
+        with pytest.raises(E, match="code 1$"):
+            _scan_bwd(L, **bad)
+    for args in ((0, 8, P, 8, 4, 4), (P, 8, 0, 8, 4, 4), (P, 8, P, 8, 0, 4), (P, 8, P, 8, 4, 6), (P, 4, P, 8, 4, 8),
+                 (P, 8, P, 4, 4, 8), (P, 6, P, 8, 4, 4)):
+        with pytest.raises(E, match="code 1$"):
+            L.copy_cols(*args, 0)
+
+
+def test_size_queries_are_host_only_and_monotone():
+    L = _lib.lib()
+    c = L.selective_scan_chunk()
+    assert isinstance(c, int) and 8 <= c <= 128
+    for q in (L.selective_scan_saved_floats, L.selective_scan_workspace_bytes, L.causal_conv1d_workspace_bytes):
+        base = q(2, 2 * c, 128)
+        assert base > 0
+        assert q(3, 2 * c, 128) > base and q(2, 2 * c, 256) > base
+        assert q(2, 2 * c + 1, 128) >= base and q(2, 8 * c, 128) > base
+    B, Lq, D = 12, 962, 1024
+    nc = math.ceil(Lq / c)
+    assert L.selective_scan_saved_floats(B, Lq, D) == B * nc * D * 16   # chunk-start states only: B * L * D * 16 / chunk
+    assert L.selective_scan_workspace_bytes(B, Lq, D) < (1 << 30)
