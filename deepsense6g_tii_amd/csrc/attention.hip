@@ -1347,23 +1347,16 @@ int ds6g_attention_fwd_bf16out(const float* q, const float* k, const float* v, v
     return attention_fwd_impl(q, k, v, 0, (float*)o, 1, lse, B, T, nh, hd, ld_qkv, ld, drop_p, seed, seed_off, ws, ws_bytes,
                               stream);
 }
-// bf16-storage path, all operands bf16 in HBM: q / k / v [B*T][ld_qkv] and o [B*T][ld] bf16 (tiles reach the bf16 MFMA
-// unconverted: bf16 LDS images, transposed LDS reads for the P.V product); lse and the split scratch fp32
-int ds6g_attention_fwd_bf16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh, int hd,
-                            int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                            void* stream) {
+// 16-bit-storage path, all operands bf16 / f16 (st16) in HBM: q / k / v [B*T][ld_qkv] and o [B*T][ld] (tiles reach the
+// 16-bit MFMA unconverted: 16-bit LDS images, transposed LDS reads for the P.V product; f16: P tiles rounded to f16 on their
+// way into v_mfma_f32_32x32x16_f16); lse and the split scratch fp32
+int ds6g_attention_fwd_h16(int st16, const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh,
+                           int hd, int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                           size_t ws_bytes, void* stream) {
+    DS6G_CHECK_ST16(st16);
     DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0);
-    return attention_fwd_impl((const float*)q, (const float*)k, (const float*)v, 1, (float*)o, 1, lse, B, T, nh, hd, ld_qkv, ld,
-                              drop_p, seed, seed_off, ws, ws_bytes, stream);
-}
-
-// the same on f16 storage (o written as f16; P tiles rounded to f16 on their way into v_mfma_f32_32x32x16_f16)
-int ds6g_attention_fwd_f16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh, int hd,
-                           int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                           void* stream) {
-    DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0);
-    return attention_fwd_impl((const float*)q, (const float*)k, (const float*)v, 2, (float*)o, 2, lse, B, T, nh, hd, ld_qkv, ld,
-                              drop_p, seed, seed_off, ws, ws_bytes, stream);
+    return attention_fwd_impl((const float*)q, (const float*)k, (const float*)v, st16, (float*)o, st16, lse, B, T, nh, hd, ld_qkv,
+                              ld, drop_p, seed, seed_off, ws, ws_bytes, stream);
 }
 
 // gradients of the above; delta is a [B][nh][T] scratch (rowsum(dO*O)), written then read
@@ -1506,26 +1499,16 @@ int ds6g_attention_bwd_bf16(const float* q, const float* k, const float* v, cons
     return attention_bwd_impl(q, k, v, 0, (const float*)o, 1, d_o, lse, delta, (float*)dq, (float*)dk, (float*)dv, 1, B, T, nh, hd,
                               ld_qkv, ld, ld_dqkv, drop_p, seed, seed_off, ws, ws_bytes, stream);
 }
-// all operands bf16: q / k / v / o / d_o in, dq / dk / dv out (the hand-over tiles in ws, lse and delta stay fp32)
-int ds6g_attention_bwd_bf16io(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
-                              float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd, int ld_qkv, int ld,
-                              int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                              void* stream) {
+// all operands bf16 / f16 (st16): q / k / v / o / d_o in, dq / dk / dv out; lse and delta stay fp32
+int ds6g_attention_bwd_h16io(int st16, const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                             const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd,
+                             int ld_qkv, int ld, int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                             size_t ws_bytes, void* stream) {
+    DS6G_CHECK_ST16(st16);
     DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0 && ld_dqkv % 4 == 0);
-    return attention_bwd_impl((const float*)q, (const float*)k, (const float*)v, 1, (const float*)o, 1, (const float*)d_o, lse, delta,
-                              (float*)dq, (float*)dk, (float*)dv, 1, B, T, nh, hd, ld_qkv, ld, ld_dqkv, drop_p, seed, seed_off, ws,
-                              ws_bytes, stream);
-}
-
-// the same on f16 storage (dS tiles handed over as f16)
-int ds6g_attention_bwd_f16io(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
-                             float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd, int ld_qkv, int ld,
-                             int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                             void* stream) {
-    DS6G_CHECK_ARG(ld_qkv % 8 == 0 && ld % 8 == 0 && ld_dqkv % 4 == 0);
-    return attention_bwd_impl((const float*)q, (const float*)k, (const float*)v, 2, (const float*)o, 2, (const float*)d_o, lse, delta,
-                              (float*)dq, (float*)dk, (float*)dv, 2, B, T, nh, hd, ld_qkv, ld, ld_dqkv, drop_p, seed, seed_off, ws,
-                              ws_bytes, stream);
+    return attention_bwd_impl((const float*)q, (const float*)k, (const float*)v, st16, (const float*)o, st16, (const float*)d_o,
+                              lse, delta, (float*)dq, (float*)dk, (float*)dv, st16, B, T, nh, hd, ld_qkv, ld, ld_dqkv, drop_p,
+                              seed, seed_off, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -778,19 +778,15 @@ static int h16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int 
     p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
     return launch_bgemm<B_FWD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
 }
-int ds6g_bf16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
-                         int stride, int pad, void* stream) {
-    return h16_conv2d_fwd<__bf16>(x, w, y, out16, N, H, W, C, K, R, S, stride, pad, stream);
-}
-int ds6g_f16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
-                        int stride, int pad, void* stream) {
-    return h16_conv2d_fwd<_Float16>(x, w, y, out16, N, H, W, C, K, R, S, stride, pad, stream);
+int ds6g_h16_conv2d_fwd(int st16, const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R,
+                        int S, int stride, int pad, void* stream) {
+    DS6G_RETURN_H16(st16, h16_conv2d_fwd, x, w, y, out16, N, H, W, C, K, R, S, stride, pad, stream);
 }
 
 // y = conv(x, w) as above with a bf16 output, plus the train-mode BatchNorm statistics of y (batch mean / invstd, running
 // statistics updated in place when given) from per-tile column partials written by the conv's epilogue: the statistics are
-// those of the STORED bf16 tensor (what ds6g_bf16_bn_stats would compute), without a pass over it.
-// ws: >= ds6g_bf16_conv_bnstats_workspace_bytes(N * Ho * Wo, K).
+// those of the STORED bf16 tensor (what ds6g_h16_bn_stats would compute), without a pass over it.
+// ws: >= ds6g_h16_conv_bnstats_workspace_bytes(N * Ho * Wo, K).
 extern "C++" template <typename T16>
 static int h16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
                                  int stride, int pad, float eps, float momentum, float* mean, float* invstd,
@@ -812,21 +808,15 @@ static int h16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, 
     return ds6g_internal_bn_stats_finalize(p.bn_partial, nblk, (long)p.Mg, K, eps, momentum, mean, invstd, running_mean,
                                            running_var, (hipStream_t)stream);
 }
-int ds6g_bf16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
-                                 int stride, int pad, float eps, float momentum, float* mean, float* invstd,
-                                 float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream) {
-    return h16_conv2d_fwd_bnstats<__bf16>(x, w, y, N, H, W, C, K, R, S, stride, pad, eps, momentum, mean, invstd, running_mean,
-                                          running_var, ws, ws_bytes, stream);
-}
-int ds6g_f16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
-                                int stride, int pad, float eps, float momentum, float* mean, float* invstd, float* running_mean,
-                                float* running_var, void* ws, size_t ws_bytes, void* stream) {
-    return h16_conv2d_fwd_bnstats<_Float16>(x, w, y, N, H, W, C, K, R, S, stride, pad, eps, momentum, mean, invstd,
-                                            running_mean, running_var, ws, ws_bytes, stream);
+int ds6g_h16_conv2d_fwd_bnstats(int st16, const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R,
+                                int S, int stride, int pad, float eps, float momentum, float* mean, float* invstd,
+                                float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, h16_conv2d_fwd_bnstats, x, w, y, N, H, W, C, K, R, S, stride, pad, eps, momentum, mean, invstd,
+                    running_mean, running_var, ws, ws_bytes, stream);
 }
 
 // inference form of Conv2d + eval-mode BatchNorm2d (+ identity) (+ ReLU) on 16-bit storage: the BN is folded into w (16-bit,
-// ds6g_bn_fold_bf16 / _f16) and bias (fp32); y = act(conv(x, w) + bias [+ residual]), relu 0 none / 1 before / 2 after the
+// ds6g_bn_fold_h16) and bias (fp32); y = act(conv(x, w) + bias [+ residual]), relu 0 none / 1 before / 2 after the
 // residual add - the contract of ds6g_conv2d_bias_act_fwd.  x, w, residual, y 16-bit; accumulation, bias and the residual add
 // fp32, one rounding.  C % 64 == 0, K % 8 == 0.
 extern "C++" template <typename T16>
@@ -848,17 +838,12 @@ static int h16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bi
     ds6g_prof_close(rec, (hipStream_t)stream);
     return rc;
 }
-int ds6g_bf16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H,
-                                  int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
-    return h16_conv2d_bias_act_fwd<__bf16>(x, w, bias, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream);
-}
-int ds6g_f16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H,
-                                 int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
-    return h16_conv2d_bias_act_fwd<_Float16>(x, w, bias, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream);
+int ds6g_h16_conv2d_bias_act_fwd(int st16, const void* x, const void* w, const float* bias, const void* residual, void* y,
+                                 int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
+    DS6G_RETURN_H16(st16, h16_conv2d_bias_act_fwd, x, w, bias, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream);
 }
 
-size_t ds6g_bf16_conv_bnstats_workspace_bytes(long M, int K) { return (size_t)cdiv(M, 64) * 2 * K * sizeof(double); }
-size_t ds6g_f16_conv_bnstats_workspace_bytes(long M, int K) { return ds6g_bf16_conv_bnstats_workspace_bytes(M, K); }
+size_t ds6g_h16_conv_bnstats_workspace_bytes(long M, int K) { return (size_t)cdiv(M, 64) * 2 * K * sizeof(double); }
 
 // dx (+)= conv^T(dy, w): dy bf16, w bf16, dx bf16 / fp32.  K % 64 == 0, C % 8 == 0; stride 1, or 2 with even H, W (the four
 // input-pixel parity classes of a stride-2 layer run as one launch).
@@ -882,13 +867,9 @@ static int h16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, 
     p.Mg = N * H * W; p.Ng = C; p.Kg = R * S * K;
     return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
 }
-int ds6g_bf16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R, int S,
-                           int stride, int pad, int accumulate, void* stream) {
-    return h16_conv2d_dgrad<__bf16>(dy, w, dx, out16, N, H, W, C, K, R, S, stride, pad, accumulate, stream);
-}
-int ds6g_f16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R, int S,
-                          int stride, int pad, int accumulate, void* stream) {
-    return h16_conv2d_dgrad<_Float16>(dy, w, dx, out16, N, H, W, C, K, R, S, stride, pad, accumulate, stream);
+int ds6g_h16_conv2d_dgrad(int st16, const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K,
+                          int R, int S, int stride, int pad, int accumulate, void* stream) {
+    DS6G_RETURN_H16(st16, h16_conv2d_dgrad, dy, w, dx, out16, N, H, W, C, K, R, S, stride, pad, accumulate, stream);
 }
 
 // dw (+)= dy^T im2col(x): x, dy bf16 -> dw fp32 [K][R][S][C] (the gradient arena).  ws: split-K slabs.
@@ -905,13 +886,9 @@ static int h16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int
     p.Mg = K; p.Ng = R * S * C; p.Kg = N * p.Ho * p.Wo;
     return run_wgrad<T16>(p, dw, accumulate, nullptr, ws, ws_bytes, (hipStream_t)stream);
 }
-int ds6g_bf16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
-                           int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
-    return h16_conv2d_wgrad<__bf16>(x, dy, dw, N, H, W, C, K, R, S, stride, pad, accumulate, ws, ws_bytes, stream);
-}
-int ds6g_f16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S, int stride,
-                          int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
-    return h16_conv2d_wgrad<_Float16>(x, dy, dw, N, H, W, C, K, R, S, stride, pad, accumulate, ws, ws_bytes, stream);
+int ds6g_h16_conv2d_wgrad(int st16, const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
+                          int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, h16_conv2d_wgrad, x, dy, dw, N, H, W, C, K, R, S, stride, pad, accumulate, ws, ws_bytes, stream);
 }
 
 // y[M][N] = residual + dropout(act(x[M][K] @ w[N][K]^T + bias)): x, w bf16; bias, residual fp32; y bf16 (out16) or fp32.
@@ -933,13 +910,9 @@ static int h16_linear_fwd(const void* x, const void* w, const float* bias, void*
     p.Mg = M; p.Ng = N; p.Kg = K;
     return launch_bgemm<B_FWD, T16>(p, out16, 1, pick_tile(M, N, 1), (hipStream_t)stream);
 }
-int ds6g_bf16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
-                         const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
-    return h16_linear_fwd<__bf16>(x, w, bias, y, out16, M, N, K, relu, residual, drop_p, seed, seed_off, stream);
-}
-int ds6g_f16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
-                        const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
-    return h16_linear_fwd<_Float16>(x, w, bias, y, out16, M, N, K, relu, residual, drop_p, seed, seed_off, stream);
+int ds6g_h16_linear_fwd(int st16, const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K,
+                        int relu, const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
+    DS6G_RETURN_H16(st16, h16_linear_fwd, x, w, bias, y, out16, M, N, K, relu, residual, drop_p, seed, seed_off, stream);
 }
 
 // dx[M][K] (+)= (dy[M][N] @ w[N][K]) * (mask_src > 0): dy, w bf16; mask_src [M][K] bf16 (mask16) or fp32, bf16 output only;
@@ -959,13 +932,9 @@ static int h16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, 
     p.Mg = M; p.Ng = K; p.Kg = N;
     return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(M, K, 1), (hipStream_t)stream);
 }
-int ds6g_bf16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
-                           int mask16, int accumulate, void* stream) {
-    return h16_linear_dgrad<__bf16>(dy, w, dx, out16, M, N, K, mask_src, mask16, accumulate, stream);
-}
-int ds6g_f16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
-                          int mask16, int accumulate, void* stream) {
-    return h16_linear_dgrad<_Float16>(dy, w, dx, out16, M, N, K, mask_src, mask16, accumulate, stream);
+int ds6g_h16_linear_dgrad(int st16, const void* dy, const void* w, void* dx, int out16, int M, int N, int K,
+                          const void* mask_src, int mask16, int accumulate, void* stream) {
+    DS6G_RETURN_H16(st16, h16_linear_dgrad, dy, w, dx, out16, M, N, K, mask_src, mask16, accumulate, stream);
 }
 
 // dw[N][K] (+)= dy[M][N]^T @ x[M][K] (fp32, the gradient arena); dbias[N] (+)= column sums of dy (nullable): x, dy bf16.
@@ -982,13 +951,9 @@ static int h16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbi
     p.Mg = N; p.Ng = K; p.Kg = M;
     return run_wgrad<T16>(p, dw, accumulate, dbias, ws, ws_bytes, (hipStream_t)stream);
 }
-int ds6g_bf16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
-                           float* ws, size_t ws_bytes, void* stream) {
-    return h16_linear_wgrad<__bf16>(x, dy, dw, dbias, M, N, K, accumulate, ws, ws_bytes, stream);
-}
-int ds6g_f16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
+int ds6g_h16_linear_wgrad(int st16, const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
                           float* ws, size_t ws_bytes, void* stream) {
-    return h16_linear_wgrad<_Float16>(x, dy, dw, dbias, M, N, K, accumulate, ws, ws_bytes, stream);
+    DS6G_RETURN_H16(st16, h16_linear_wgrad, x, dy, dw, dbias, M, N, K, accumulate, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -18,6 +18,18 @@
         }                                                                                      \
     } while (0)
 
+// Storage code `st16`, the first argument of every ds6g_h16_* / *_h16* entry point (include/ds6g.h): the values of in16 /
+// out16 / dp16 inside the library; 0 (fp32) has entry points of its own and is refused with every other value.
+#define DS6G_ST_BF16 1
+#define DS6G_ST_F16 2
+#define DS6G_CHECK_ST16(st16) DS6G_CHECK_ARG((st16) == DS6G_ST_BF16 || (st16) == DS6G_ST_F16)
+// the whole body of such an entry point over a template on the storage type: the refusal, then fn<__bf16> or fn<_Float16>
+#define DS6G_RETURN_H16(st16, fn, ...)                                                         \
+    do {                                                                                       \
+        DS6G_CHECK_ST16(st16);                                                                 \
+        return (st16) == DS6G_ST_BF16 ? fn<__bf16>(__VA_ARGS__) : fn<_Float16>(__VA_ARGS__);   \
+    } while (0)
+
 // hipGetLastError() is sticky per thread: a benign failure inside the caller's runtime (e.g. PyTorch probing a
 // host pointer) would otherwise be reported by our next launch check.  Every entry point clears it first.
 #define DS6G_ENTER() (void)hipGetLastError()

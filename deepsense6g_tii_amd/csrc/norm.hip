@@ -574,7 +574,7 @@ static int ln_bwd_launch(const TDY* dy, const float* x, const float* mean, const
     return DS6G_OK;
 }
 
-// bgemm.hip: the conv epilogue wrote the partials (ds6g_bf16_conv2d_fwd_bnstats)
+// bgemm.hip: the conv epilogue wrote the partials (ds6g_h16_conv2d_fwd_bnstats)
 int ds6g_internal_bn_stats_finalize(const double* partial, int nblk, long M, int C, float eps, float momentum, float* mean,
                                     float* invstd, float* running_mean, float* running_var, hipStream_t st) {
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(cdiv(C, BNF_COLS)), dim3(256), 0, st, partial, nblk, M, C, eps,
@@ -605,13 +605,9 @@ static int h16_bn_stats(const void* x, long M, int C, float eps, float momentum,
     return bn_stats_run<T16>((const T16*)x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
                                 stream);
 }
-int ds6g_bf16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd, float* running_mean,
-                       float* running_var, void* ws, size_t ws_bytes, void* stream) {
-    return h16_bn_stats<__bf16>(x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
-}
-int ds6g_f16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd, float* running_mean,
-                      float* running_var, void* ws, size_t ws_bytes, void* stream) {
-    return h16_bn_stats<_Float16>(x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
+int ds6g_h16_bn_stats(int st16, const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd,
+                      float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, h16_bn_stats, x, M, C, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
 }
 
 int ds6g_bn_eval_prepare(const float* running_mean, const float* running_var, int C, float eps, float* mean,
@@ -636,13 +632,9 @@ static int h16_bn_apply(const void* x, const float* mean, const float* invstd, c
     return bn_apply_run<T16>((const T16*)x, mean, invstd, gamma, beta, (const T16*)residual, (T16*)y, M, C, relu,
                                 stream);
 }
-int ds6g_bf16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                       const void* residual, void* y, long M, int C, int relu, void* stream) {
-    return h16_bn_apply<__bf16>(x, mean, invstd, gamma, beta, residual, y, M, C, relu, stream);
-}
-int ds6g_f16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+int ds6g_h16_bn_apply(int st16, const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                       const void* residual, void* y, long M, int C, int relu, void* stream) {
-    return h16_bn_apply<_Float16>(x, mean, invstd, gamma, beta, residual, y, M, C, relu, stream);
+    DS6G_RETURN_H16(st16, h16_bn_apply, x, mean, invstd, gamma, beta, residual, y, M, C, relu, stream);
 }
 
 int ds6g_bn_bwd(const float* dy, const float* y_mask, const float* x, const float* mean, const float* invstd,
@@ -666,17 +658,11 @@ static int h16_bn_bwd(const void* dy, const void* y_mask, const void* x, const f
                                       gamma, relu_beta, (T16*)dx, dgamma, dbeta, (T16*)dres, M, C,
                                       accumulate_param_grads, ws, ws_bytes, stream);
 }
-int ds6g_bf16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
-                     const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres, long M,
-                     int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
-    return h16_bn_bwd<__bf16>(dy, y_mask, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, dres, M, C,
-                              accumulate_param_grads, ws, ws_bytes, stream);
-}
-int ds6g_f16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
+int ds6g_h16_bn_bwd(int st16, const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
                     const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres, long M,
                     int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
-    return h16_bn_bwd<_Float16>(dy, y_mask, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, dres, M, C,
-                                accumulate_param_grads, ws, ws_bytes, stream);
+    DS6G_RETURN_H16(st16, h16_bn_bwd, dy, y_mask, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, dres, M, C,
+                    accumulate_param_grads, ws, ws_bytes, stream);
 }
 
 // BN -> ReLU -> 3x3/2 max-pool (the ResNet stem, model2_seq.py:495-500 via torchvision) backward in one pass over x: the
@@ -699,23 +685,15 @@ int ds6g_bn_bwd_maxpool(const float* dpool, const uint8_t* idx, const float* x, 
     return bn_bwd_maxpool_impl(dpool, 0, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
                                accumulate_param_grads, ws, ws_bytes, stream);
 }
-// bf16-storage path: the stem's conv output x and its gradient dx stay fp32 (the 4-channel stem keeps the fp32-storage
-// kernels), the gradient of the pooled tensor arrives as bf16
-int ds6g_bn_bwd_maxpool_bf16in(const void* dpool, const uint8_t* idx, const float* x, const float* mean,
-                               const float* invstd, const float* gamma, const float* relu_beta, float* dx, float* dgamma,
-                               float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
-                               size_t ws_bytes, void* stream) {
-    DS6G_ENTER();
-    return bn_bwd_maxpool_impl(dpool, 1, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
-                               accumulate_param_grads, ws, ws_bytes, stream);
-}
-// the same with an f16 pool gradient (f16-storage path)
-int ds6g_bn_bwd_maxpool_f16in(const void* dpool, const uint8_t* idx, const float* x, const float* mean,
+// 16-bit-storage path: the stem's conv output x and its gradient dx stay fp32 (the 4-channel stem keeps the fp32-storage
+// kernels), the gradient of the pooled tensor arrives as bf16 / f16
+int ds6g_bn_bwd_maxpool_h16in(int st16, const void* dpool, const uint8_t* idx, const float* x, const float* mean,
                               const float* invstd, const float* gamma, const float* relu_beta, float* dx, float* dgamma,
                               float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
                               size_t ws_bytes, void* stream) {
+    DS6G_CHECK_ST16(st16);
     DS6G_ENTER();
-    return bn_bwd_maxpool_impl(dpool, 2, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
+    return bn_bwd_maxpool_impl(dpool, st16, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
                                accumulate_param_grads, ws, ws_bytes, stream);
 }
 
@@ -732,17 +710,12 @@ static int h16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const 
     return bn_bwd_run<T16, T16>(nullptr, pg, nullptr, (const T16*)x, mean, invstd, gamma, relu_beta, (T16*)dx,
                                       dgamma, dbeta, nullptr, (long)N * H * W, C, accumulate_param_grads, ws, ws_bytes, stream);
 }
-int ds6g_bf16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean, const float* invstd,
-                                  const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, int N,
-                                  int H, int W, int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
-    return h16_stem_bn_bwd_maxpool<__bf16>(dpool, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
-                                           accumulate_param_grads, ws, ws_bytes, stream);
-}
-int ds6g_f16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean, const float* invstd,
-                                 const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, int N,
-                                 int H, int W, int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream) {
-    return h16_stem_bn_bwd_maxpool<_Float16>(dpool, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
-                                             accumulate_param_grads, ws, ws_bytes, stream);
+int ds6g_h16_stem_bn_bwd_maxpool(int st16, const void* dpool, const uint8_t* idx, const void* x, const float* mean,
+                                 const float* invstd, const float* gamma, const float* relu_beta, void* dx, float* dgamma,
+                                 float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, h16_stem_bn_bwd_maxpool, dpool, idx, x, mean, invstd, gamma, relu_beta, dx, dgamma, dbeta, N, H, W, C,
+                    accumulate_param_grads, ws, ws_bytes, stream);
 }
 
 int ds6g_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
@@ -762,13 +735,9 @@ static int layernorm_fwd_h16out(const float* x, const float* gamma, const float*
     DS6G_CHECK_ARG(C % 64 == 0 && C <= 512);
     return ln_fwd_launch<T16>(x, gamma, beta, (T16*)y, mean, rstd, M, C, eps, (hipStream_t)stream);
 }
-int ds6g_layernorm_fwd_bf16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M,
-                               int C, float eps, void* stream) {
-    return layernorm_fwd_h16out<__bf16>(x, gamma, beta, y, mean, rstd, M, C, eps, stream);
-}
-int ds6g_layernorm_fwd_f16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M,
-                              int C, float eps, void* stream) {
-    return layernorm_fwd_h16out<_Float16>(x, gamma, beta, y, mean, rstd, M, C, eps, stream);
+int ds6g_layernorm_fwd_h16out(int st16, const float* x, const float* gamma, const float* beta, void* y, float* mean,
+                              float* rstd, int M, int C, float eps, void* stream) {
+    DS6G_RETURN_H16(st16, layernorm_fwd_h16out, x, gamma, beta, y, mean, rstd, M, C, eps, stream);
 }
 
 size_t ds6g_layernorm_bwd_workspace_bytes(int M, int C) { return (size_t)cdiv(M, LN_BWD_ROWS) * 2 * C * sizeof(float); }
@@ -799,19 +768,12 @@ static int layernorm_bwd_h16(const void* dy, int dy16, const float* x, const flo
                                         accumulate_param_grads, (T16*)dx_drop, drop_p, seed, seed_off, ws, ws_bytes,
                                         (hipStream_t)stream);
 }
-int ds6g_layernorm_bwd_bf16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd, const float* gamma,
-                            const float* add, float* dx, float* dgamma, float* dbeta, int M, int C, int accumulate_param_grads,
-                            void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                            void* stream) {
-    return layernorm_bwd_h16<__bf16>(dy, dy16, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C, accumulate_param_grads,
-                                     dx_drop, drop_p, seed, seed_off, ws, ws_bytes, stream);
-}
-int ds6g_layernorm_bwd_f16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd, const float* gamma,
-                           const float* add, float* dx, float* dgamma, float* dbeta, int M, int C, int accumulate_param_grads,
-                           void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                           void* stream) {
-    return layernorm_bwd_h16<_Float16>(dy, dy16, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C, accumulate_param_grads,
-                                       dx_drop, drop_p, seed, seed_off, ws, ws_bytes, stream);
+int ds6g_layernorm_bwd_h16(int st16, const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
+                           const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
+                           int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                           size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, layernorm_bwd_h16, dy, dy16, x, mean, rstd, gamma, add, dx, dgamma, dbeta, M, C,
+                    accumulate_param_grads, dx_drop, drop_p, seed, seed_off, ws, ws_bytes, stream);
 }
 
 constexpr int COLSUM_ROWS = 32;
@@ -855,17 +817,17 @@ int ds6g_bn_fold(const float* w, const float* gamma, const float* beta, const fl
     return bn_fold_run<float>(w, gamma, beta, running_mean, running_var, eps, w_out, bias_out, K, taps, cin, cpad, stream);
 }
 // the same fold with a 16-bit w_out (one rounding of the fp32 product) and an fp32 bias_out
-int ds6g_bn_fold_bf16(const float* w, const float* gamma, const float* beta, const float* running_mean,
-                      const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin, int cpad,
-                      void* stream) {
-    return bn_fold_run<__bf16>(w, gamma, beta, running_mean, running_var, eps, (__bf16*)w_out, bias_out, K, taps, cin, cpad,
-                               stream);
+extern "C++" template <typename T16>
+static int bn_fold_h16(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin, int cpad,
+                       void* stream) {
+    return bn_fold_run<T16>(w, gamma, beta, running_mean, running_var, eps, (T16*)w_out, bias_out, K, taps, cin, cpad, stream);
 }
-int ds6g_bn_fold_f16(const float* w, const float* gamma, const float* beta, const float* running_mean,
+int ds6g_bn_fold_h16(int st16, const float* w, const float* gamma, const float* beta, const float* running_mean,
                      const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin, int cpad,
                      void* stream) {
-    return bn_fold_run<_Float16>(w, gamma, beta, running_mean, running_var, eps, (_Float16*)w_out, bias_out, K, taps, cin, cpad,
-                                 stream);
+    DS6G_RETURN_H16(st16, bn_fold_h16, w, gamma, beta, running_mean, running_var, eps, w_out, bias_out, K, taps, cin, cpad,
+                    stream);
 }
 
 }  // extern "C"

@@ -488,13 +488,9 @@ static int pack_input_h16(const float* src, void* dst, int B, int Cs, int H, int
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_pack_input_bf16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
-                         int normalize_imagenet, void* stream) {
-    return pack_input_h16<__bf16>(src, dst, B, Cs, H, W, frames_per_sample, t, normalize_imagenet, stream);
-}
-int ds6g_pack_input_f16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
+int ds6g_pack_input_h16(int st16, const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
                         int normalize_imagenet, void* stream) {
-    return pack_input_h16<_Float16>(src, dst, B, Cs, H, W, frames_per_sample, t, normalize_imagenet, stream);
+    DS6G_RETURN_H16(st16, pack_input_h16, src, dst, B, Cs, H, W, frames_per_sample, t, normalize_imagenet, stream);
 }
 
 int ds6g_pad_channels(const float* src, float* dst, long rows, int cin, int cout, int unpad, int accumulate,
@@ -686,13 +682,9 @@ static int bn_relu_maxpool3x3s2_fwd_h16out(const float* x, const float* mean, co
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bn_relu_maxpool3x3s2_fwd_bf16out(const float* x, const float* mean, const float* invstd, const float* gamma,
-                                          const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
-    return bn_relu_maxpool3x3s2_fwd_h16out<__bf16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
-}
-int ds6g_bn_relu_maxpool3x3s2_fwd_f16out(const float* x, const float* mean, const float* invstd, const float* gamma,
+int ds6g_bn_relu_maxpool3x3s2_fwd_h16out(int st16, const float* x, const float* mean, const float* invstd, const float* gamma,
                                          const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
-    return bn_relu_maxpool3x3s2_fwd_h16out<_Float16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
+    DS6G_RETURN_H16(st16, bn_relu_maxpool3x3s2_fwd_h16out, x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
 }
 
 // bf16 stem (csrc/stem.hip): the conv output x is bf16 as well
@@ -707,16 +699,12 @@ static int h16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const 
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
-                                       const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
-    return h16_stem_bn_relu_maxpool_fwd<__bf16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
-}
-int ds6g_f16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
+int ds6g_h16_stem_bn_relu_maxpool_fwd(int st16, const void* x, const float* mean, const float* invstd, const float* gamma,
                                       const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
-    return h16_stem_bn_relu_maxpool_fwd<_Float16>(x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
+    DS6G_RETURN_H16(st16, h16_stem_bn_relu_maxpool_fwd, x, mean, invstd, gamma, beta, y, idx, N, H, W, C, stream);
 }
 
-// index-free 3x3 / 2 / pad 1 max-pool of a 16-bit NHWC map (the inference stem: after ds6g_*_stem_bias_relu_fwd); C % 8 == 0
+// index-free 3x3 / 2 / pad 1 max-pool of a 16-bit NHWC map (the inference stem: after ds6g_h16_stem_bias_relu_fwd); C % 8 == 0
 extern "C++" template <typename T16>
 static int h16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
     DS6G_ENTER();
@@ -727,11 +715,8 @@ static int h16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
-    return h16_maxpool3x3s2_fwd<__bf16>(x, y, N, H, W, C, stream);
-}
-int ds6g_f16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
-    return h16_maxpool3x3s2_fwd<_Float16>(x, y, N, H, W, C, stream);
+int ds6g_h16_maxpool3x3s2_fwd(int st16, const void* x, void* y, int N, int H, int W, int C, void* stream) {
+    DS6G_RETURN_H16(st16, h16_maxpool3x3s2_fwd, x, y, N, H, W, C, stream);
 }
 
 extern "C++" template <typename T16>
@@ -746,17 +731,11 @@ static int h16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float*
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
-                                 int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed, uint64_t seed_off,
-                                 void* stream) {
-    return h16_avgpool_tokens_fwd<__bf16>(feat, pos_emb, tokens, N, H, C, frames_per_sample, mod_off, T, drop_p, seed, seed_off,
-                                          stream);
-}
-int ds6g_f16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
+int ds6g_h16_avgpool_tokens_fwd(int st16, const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
                                 int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed, uint64_t seed_off,
                                 void* stream) {
-    return h16_avgpool_tokens_fwd<_Float16>(feat, pos_emb, tokens, N, H, C, frames_per_sample, mod_off, T, drop_p, seed,
-                                            seed_off, stream);
+    DS6G_RETURN_H16(st16, h16_avgpool_tokens_fwd, feat, pos_emb, tokens, N, H, C, frames_per_sample, mod_off, T, drop_p, seed,
+                    seed_off, stream);
 }
 
 extern "C++" template <typename T16>
@@ -769,13 +748,9 @@ static int h16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void*
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
-                                 int frames_per_sample, int mod_off, int T, void* stream) {
-    return h16_avgpool_tokens_bwd<__bf16>(dtok, dfeat_in, dfeat, N, H, C, frames_per_sample, mod_off, T, stream);
-}
-int ds6g_f16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
+int ds6g_h16_avgpool_tokens_bwd(int st16, const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
                                 int frames_per_sample, int mod_off, int T, void* stream) {
-    return h16_avgpool_tokens_bwd<_Float16>(dtok, dfeat_in, dfeat, N, H, C, frames_per_sample, mod_off, T, stream);
+    DS6G_RETURN_H16(st16, h16_avgpool_tokens_bwd, dtok, dfeat_in, dfeat, N, H, C, frames_per_sample, mod_off, T, stream);
 }
 
 extern "C++" template <typename T16>
@@ -788,13 +763,9 @@ static int h16_upsample_add_fwd(const void* feat, const float* tokens, void* out
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C, int frames_per_sample,
-                               int mod_off, int T, void* stream) {
-    return h16_upsample_add_fwd<__bf16>(feat, tokens, out, N, H, C, frames_per_sample, mod_off, T, stream);
-}
-int ds6g_f16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C, int frames_per_sample,
-                              int mod_off, int T, void* stream) {
-    return h16_upsample_add_fwd<_Float16>(feat, tokens, out, N, H, C, frames_per_sample, mod_off, T, stream);
+int ds6g_h16_upsample_add_fwd(int st16, const void* feat, const float* tokens, void* out, int N, int H, int C,
+                              int frames_per_sample, int mod_off, int T, void* stream) {
+    DS6G_RETURN_H16(st16, h16_upsample_add_fwd, feat, tokens, out, N, H, C, frames_per_sample, mod_off, T, stream);
 }
 
 extern "C++" template <typename T16>
@@ -807,13 +778,9 @@ static int h16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off, int T,
-                               void* stream) {
-    return h16_upsample_add_bwd<__bf16>(dout, dtok, N, H, C, frames_per_sample, mod_off, T, stream);
-}
-int ds6g_f16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off, int T,
-                              void* stream) {
-    return h16_upsample_add_bwd<_Float16>(dout, dtok, N, H, C, frames_per_sample, mod_off, T, stream);
+int ds6g_h16_upsample_add_bwd(int st16, const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
+                              int T, void* stream) {
+    DS6G_RETURN_H16(st16, h16_upsample_add_bwd, dout, dtok, N, H, C, frames_per_sample, mod_off, T, stream);
 }
 
 extern "C++" template <typename T16>
@@ -825,11 +792,8 @@ static int h16_global_pool(const void* feat, float* pooled, int N, int C, void* 
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_global_pool(const void* feat, float* pooled, int N, int C, void* stream) {
-    return h16_global_pool<__bf16>(feat, pooled, N, C, stream);
-}
-int ds6g_f16_global_pool(const void* feat, float* pooled, int N, int C, void* stream) {
-    return h16_global_pool<_Float16>(feat, pooled, N, C, stream);
+int ds6g_h16_global_pool(int st16, const void* feat, float* pooled, int N, int C, void* stream) {
+    DS6G_RETURN_H16(st16, h16_global_pool, feat, pooled, N, C, stream);
 }
 
 extern "C++" template <typename T16>
@@ -841,11 +805,8 @@ static int h16_head_bwd(const float* dfused, void* dfeat, int N, int C, int fram
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream) {
-    return h16_head_bwd<__bf16>(dfused, dfeat, N, C, frames_per_sample, stream);
-}
-int ds6g_f16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream) {
-    return h16_head_bwd<_Float16>(dfused, dfeat, N, C, frames_per_sample, stream);
+int ds6g_h16_head_bwd(int st16, const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream) {
+    DS6G_RETURN_H16(st16, h16_head_bwd, dfused, dfeat, N, C, frames_per_sample, stream);
 }
 
 }  // extern "C"

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void stem_pack_weights_kernel(const float* __r
     w16[i] = (T16)v;
 }
 
-// the inference engine's filter: BN-folded and already rounded to 16 bits, [64][7][7][4] (ds6g_bn_fold_bf16 / _f16 with 4 padded
+// the inference engine's filter: BN-folded and already rounded to 16 bits, [64][7][7][4] (ds6g_bn_fold_h16 with 4 padded
 // channels) -> the forward's [64][7][8][4] layout (tap s' = s + 1, tap 0 zero).  Pure data movement, done once per snapshot.
 template <typename T16>
 __global__ __launch_bounds__(256) void stem_pack_filter16_kernel(const T16* __restrict__ w, T16* __restrict__ w16) {
@@ -350,12 +350,11 @@ constexpr int STEM_GRID_FWD = 512, STEM_GRID_WGRAD = 256;
 
 extern "C" {
 
-size_t ds6g_bf16_stem_workspace_bytes(void) {
+size_t ds6g_h16_stem_workspace_bytes(void) {
     const size_t fwd = (size_t)KO * WROW * 2 + 1024 + (size_t)STEM_GRID_FWD * 2 * KO * sizeof(double);
     const size_t wg = (size_t)STEM_GRID_WGRAD * KO * 7 * 32 * sizeof(float);
     return fwd > wg ? fwd : wg;
 }
-size_t ds6g_f16_stem_workspace_bytes(void) { return ds6g_bf16_stem_workspace_bytes(); }
 
 // y = conv7x7/2(x, w) on bf16 storage + the train-mode BatchNorm statistics of y.  x [N][H][W][4] bf16 (channels >= cin
 // zero), w: the fp32 master filter [64][7][7][cin] (OHWI), y [N][H/2][W/2][64] bf16; H % 16 == 0, W % 32 == 0.
@@ -365,7 +364,7 @@ static int h16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, 
                        float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
                        void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_bf16_stem_workspace_bytes());
+    DS6G_CHECK_ARG(x && w && y && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_h16_stem_workspace_bytes());
     StemParams p{};
     DS6G_CHECK_ARG(stem_geometry(p, N, H, W) == DS6G_OK);
     T16* w16 = (T16*)ws;
@@ -382,21 +381,15 @@ static int h16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, 
     return ds6g_internal_bn_stats_finalize(p.bn_partial, grid, (long)N * p.Ho * p.Wo, KO, eps, momentum, mean, invstd,
                                            running_mean, running_var, st);
 }
-int ds6g_bf16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
-                       float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
-                       void* stream) {
-    return h16_stem_fwd<__bf16>(x, w, cin, y, N, H, W, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
-                                stream);
-}
-int ds6g_f16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
+int ds6g_h16_stem_fwd(int st16, const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
                       float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
                       void* stream) {
-    return h16_stem_fwd<_Float16>(x, w, cin, y, N, H, W, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes,
-                                  stream);
+    DS6G_RETURN_H16(st16, h16_stem_fwd, x, w, cin, y, N, H, W, eps, momentum, mean, invstd, running_mean, running_var, ws,
+                    ws_bytes, stream);
 }
 
-// inference stem: the filter is prepared once per snapshot (ds6g_bn_fold_bf16 / _f16 with cpad = 4 -> w [64][7][7][4], then
-// ds6g_*_stem_pack_filter -> w_packed [64][7][8][4]); the forward is y = relu(conv7x7/2(x, w_packed) + bias), one launch, no
+// inference stem: the filter is prepared once per snapshot (ds6g_bn_fold_h16 with cpad = 4 -> w [64][7][7][4], then
+// ds6g_h16_stem_pack_filter -> w_packed [64][7][8][4]); the forward is y = relu(conv7x7/2(x, w_packed) + bias), one launch, no
 // workspace.  x [N][H][W][4], y [N][H/2][W/2][64] 16-bit, bias fp32 [64]; H % 16 == 0, W % 32 == 0.
 extern "C++" template <typename T16>
 static int h16_stem_pack_filter(const void* w, void* w_packed, void* stream) {
@@ -407,8 +400,9 @@ static int h16_stem_pack_filter(const void* w, void* w_packed, void* stream) {
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_stem_pack_filter(const void* w, void* w_packed, void* stream) { return h16_stem_pack_filter<__bf16>(w, w_packed, stream); }
-int ds6g_f16_stem_pack_filter(const void* w, void* w_packed, void* stream) { return h16_stem_pack_filter<_Float16>(w, w_packed, stream); }
+int ds6g_h16_stem_pack_filter(int st16, const void* w, void* w_packed, void* stream) {
+    DS6G_RETURN_H16(st16, h16_stem_pack_filter, w, w_packed, stream);
+}
 
 extern "C++" template <typename T16>
 static int h16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
@@ -423,13 +417,9 @@ static int h16_stem_bias_relu_fwd(const void* x, const void* w_packed, const flo
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
-                                 void* stream) {
-    return h16_stem_bias_relu_fwd<__bf16>(x, w_packed, bias, y, N, H, W, stream);
-}
-int ds6g_f16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
+int ds6g_h16_stem_bias_relu_fwd(int st16, const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
                                 void* stream) {
-    return h16_stem_bias_relu_fwd<_Float16>(x, w_packed, bias, y, N, H, W, stream);
+    DS6G_RETURN_H16(st16, h16_stem_bias_relu_fwd, x, w_packed, bias, y, N, H, W, stream);
 }
 
 // dw[64][7][7][cin] (+)= weight gradient of the same convolution from x [N][H][W][4] bf16 and dy [N][H/2][W/2][64] bf16
@@ -437,7 +427,7 @@ extern "C++" template <typename T16>
 static int h16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
                          size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && dy && dw && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_bf16_stem_workspace_bytes());
+    DS6G_CHECK_ARG(x && dy && dw && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_h16_stem_workspace_bytes());
     StemParams p{};
     DS6G_CHECK_ARG(stem_geometry(p, N, H, W) == DS6G_OK);
     p.x = (const __bf16*)x; p.dy = (const __bf16*)dy; p.slabs = (float*)ws;
@@ -449,13 +439,9 @@ static int h16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_bf16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
-                         size_t ws_bytes, void* stream) {
-    return h16_stem_wgrad<__bf16>(x, dy, dw, cin, N, H, W, accumulate, ws, ws_bytes, stream);
-}
-int ds6g_f16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
-                        size_t ws_bytes, void* stream) {
-    return h16_stem_wgrad<_Float16>(x, dy, dw, cin, N, H, W, accumulate, ws, ws_bytes, stream);
+int ds6g_h16_stem_wgrad(int st16, const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate,
+                        void* ws, size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, h16_stem_wgrad, x, dy, dw, cin, N, H, W, accumulate, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

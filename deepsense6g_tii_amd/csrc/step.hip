@@ -509,8 +509,9 @@ static int cast_f32_h16(const float* src, void* dst, long n, void* stream) {
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-int ds6g_cast_f32_bf16(const float* src, void* dst, long n, void* stream) { return cast_f32_h16<__bf16>(src, dst, n, stream); }
-int ds6g_cast_f32_f16(const float* src, void* dst, long n, void* stream) { return cast_f32_h16<_Float16>(src, dst, n, stream); }
+int ds6g_cast_f32_h16(int st16, const float* src, void* dst, long n, void* stream) {
+    DS6G_RETURN_H16(st16, cast_f32_h16, src, dst, n, stream);
+}
 
 // Multi-GPU rehearsal on one GPU (tests/test_dp_gpu.py, tools/coresidency.py): `workgroups` workgroups of 256 threads, each
 // holding `lds_bytes` of LDS, stay resident for `microseconds` (100 MHz real-time counter; every wave leaves when the time is
@@ -534,7 +535,7 @@ int ds6g_set_dropout_salt(const uint64_t* dev_ptr) {
     return DS6G_OK;
 }
 
-int ds6g_version(void) { return 2; }
+int ds6g_version(void) { return 3; }
 
 // 0 - 3: g_ds6g_bf16 (the operand mode of the fp32-storage kernels); 5: f16 storage, whose fp32-storage kernels run in
 // operand mode 0 - the storage type is kept apart (g_ds6g_storage) so that no reader of g_ds6g_bf16 sees a 5; 4: unused

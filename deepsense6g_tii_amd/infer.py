@@ -8,7 +8,7 @@ model's weights do not change, so the engine does that work ONCE, into memory it
   "f32"     BN-folded fp32 filter + bias of every conv; the            fp32 copies
             Winograd-transformed filter u of every 3x3 / stride-1 conv
   "bf16",   BN folded in fp32, rounded once to the 16-bit type          16-bit copies of the key|query|value, proj, fc1, fc2
-  "f16"     (ds6g_bn_fold_bf16 / _f16); fp32 bias; the stem filter     weights; biases, LayerNorm, pos_emb, vel_emb*, join
+  "f16"     (ds6g_bn_fold_h16); fp32 bias; the stem filter             weights; biases, LayerNorm, pos_emb, vel_emb*, join
             also in the stem kernel's packed layout                     (and decoder / output of the 30->5 head) fp32
 
 The engine is a SNAPSHOT: between ``refresh()`` calls it never reads the model's parameters or buffers, so the model may go

@@ -326,7 +326,7 @@ class TransFuser(nn.Module):
         self.overlap_wgrad = True  # GPT-stage weight gradients on a second stream, overlapping the dgrad / attention chain
         self._wg_map, self._wg_used, self._wg_keep = {}, {}, []
         self.overlap_wgrad_trunks = False  # measured: no gain on top of the three concurrent trunk streams
-        # bf16 configuration: train-mode BatchNorm statistics come out of the conv's epilogue (ds6g_bf16_conv2d_fwd_bnstats)
+        # bf16 configuration: train-mode BatchNorm statistics come out of the conv's epilogue (ds6g_h16_conv2d_fwd_bnstats)
         self.fuse_bn_stats16 = os.environ.get("DS6G_FUSE_BN_STATS16", "1") != "0"
         self.use_winograd = True  # 3x3 / stride-1 convs (forward and data gradient) as Winograd F(2x2, 3x3) in fp32 mode
         self.fold_bn_eval = True  # eval(): BatchNorm folded into the conv weights (no BN kernels at inference)
@@ -734,16 +734,12 @@ class TransFuser(nn.Module):
             assert frames.dim() == 4 and frames.shape[3] == 4 and frames.dtype == F32 and frames.is_contiguous() \
                 and frames.device == self.device
             return frames if dtype == F32 else ops.cast_bf16(frames, dtype=dtype)
-        L, st = lib(), ops._stream()
         B, S = frames[0].shape[0], len(frames)
         H, W = frames[0].shape[2:]
         x = torch.empty((B * S, H, W, 4), dtype=dtype, device=self.device)
         for t, f in enumerate(frames):
             assert f.shape == (B, cin, H, W), (f.shape, (B, cin, H, W))
-            if dtype == F32:
-                L.pack_input(f.data_ptr(), x.data_ptr(), B, cin, H, W, 4, S, t, int(normalize), st)
-            else:
-                ops._fn("pack_input_bf16", dtype)(f.data_ptr(), x.data_ptr(), B, cin, H, W, S, t, int(normalize), st)
+            ops.pack_input(f, x, t, normalize)
         return x
 
     def _stem_fwd(self, wk, trunk, cin, normalize, frames):
@@ -951,10 +947,8 @@ class TransFuser(nn.Module):
         pos = wk.w(gpt.pos_emb)
         fdt = feats[0].dtype   # 16-bit storage: feature maps bf16 / f16, tokens fp32
         for m in range(3):
-            N, H = feats[m].shape[0], feats[m].shape[1]
-            assert feats[m].shape == (B * fps[m], H, H, C) and feats[m].dtype == fdt
-            ops._fn("bf16_avgpool_tokens_fwd", fdt)(
-                feats[m].data_ptr(), pos, x0.data_ptr(), N, H, C, fps[m], offs[m], T, pe, self._seed, off_e, st)
+            assert feats[m].shape[0] == B * fps[m] and feats[m].shape[3] == C and feats[m].dtype == fdt
+            ops.avgpool_tokens_fwd(feats[m], pos, x0, fps[m], offs[m], T, pe, self._seed, off_e)
         _, gptr, rpg, gstride, K = gps_src
         gemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
         L.small_linear_fwd(gptr, wk.w(vel.weight), wk.w(vel.bias), gemb.data_ptr(), 2 * B, C, K, rpg, gstride, 0, st)
@@ -967,10 +961,8 @@ class TransFuser(nn.Module):
         xo, mf, rf = ops.layernorm_fwd(x, wk.w(gpt.ln_f.weight), wk.w(gpt.ln_f.bias), gpt.ln_f.eps)
         outs = []
         for m in range(3):
-            N, H = feats[m].shape[0], feats[m].shape[1]
             o = torch.empty_like(feats[m])
-            ops._fn("bf16_upsample_add_fwd", fdt)(
-                feats[m].data_ptr(), xo.data_ptr(), o.data_ptr(), N, H, C, fps[m], offs[m], T, st)
+            ops.upsample_add_fwd(feats[m], xo, o, fps[m], offs[m], T)
             outs.append(o)
         return outs, xo, _StageRec(s, C, T, fps, offs, pe, off_e, gps_src, blk_ctx, x, mf, rf, [f.shape for f in feats])
 
@@ -1059,7 +1051,7 @@ class TransFuser(nn.Module):
             N = feats[m].shape[0]
             assert feats[m].shape[1:] == (8, 8, 512)
             pl = torch.empty((N, 512), dtype=F32, device=self.device)
-            ops._fn("bf16_global_pool", feats[m].dtype)(feats[m].data_ptr(), pl.data_ptr(), N, 512, st)
+            ops.global_pool(feats[m], pl)
             pooled.append(pl)
         fused = torch.empty((B, 512), dtype=F32, device=self.device)
         L.head_sum(pooled[0].data_ptr(), pooled[1].data_ptr(), pooled[2].data_ptr(), xo.data_ptr(), fused.data_ptr(), B,
@@ -1243,9 +1235,8 @@ class TransFuser(nn.Module):
         vel = getattr(self.encoder, f"vel_emb{s}")
         dxo = torch.empty((B * T, C), dtype=F32, device=self.device)
         for m in range(3):
-            N, H = fshapes[m][0], fshapes[m][1]
-            ops._fn("bf16_upsample_add_bwd", dfeats_out[m].dtype)(dfeats_out[m].data_ptr(), dxo.data_ptr(), N, H, C, fps[m],
-                                                                  offs[m], T, st)
+            assert dfeats_out[m].shape == tuple(fshapes[m])
+            ops.upsample_add_bwd(dfeats_out[m], dxo, fps[m], offs[m], T)
         gsrc, bcast = dgps_tok
         L.gps_rows(gsrc.data_ptr(), dxo.data_ptr(), B, C, T, 1, 0, int(bcast), st)
         gfw, af = wk.g(gpt.ln_f.weight)
@@ -1263,10 +1254,8 @@ class TransFuser(nn.Module):
         L.batch_sum(dpre.data_ptr(), gpos, T * C, B, T * C, apos, st)
         dfeats = []
         for m in range(3):
-            N, H = fshapes[m][0], fshapes[m][1]
             d = torch.empty(tuple(fshapes[m]), dtype=dfeats_out[m].dtype, device=self.device)
-            ops._fn("bf16_avgpool_tokens_bwd", dfeats_out[m].dtype)(dpre.data_ptr(), dfeats_out[m].data_ptr(), d.data_ptr(),
-                                                                    N, H, C, fps[m], offs[m], T, st)
+            ops.avgpool_tokens_bwd(dpre, dfeats_out[m], d, fps[m], offs[m], T)
             dfeats.append(d)
         dgemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
         L.gps_rows(dpre.data_ptr(), dgemb.data_ptr(), B, C, T, 0, 0, 0, st)
@@ -1359,7 +1348,7 @@ class TransFuser(nn.Module):
         for m in range(3):
             d = torch.empty(tuple(fshapes[m]), dtype=fdtype, device=self.device)
             fps = cfg.n_views * S if m == 0 else S
-            ops._fn("bf16_head_bwd", fdtype)(dfused.data_ptr(), d.data_ptr(), fshapes[m][0], 512, fps, st)
+            ops.head_bwd(dfused, d, fps)
             dfeats.append(d)
         dgps = (dfused, True)
         for s in range(4, 0, -1):

@@ -119,9 +119,9 @@ def bn_fold(w_ohwi_ptr, bn, K, taps, cin, cpad=None, dtype=F32, out=None):
         w_out = torch.empty((K, taps, cpad), dtype=dtype, device=dev)
         b_out = torch.empty((K,), dtype=F32, device=dev)
     assert dtype in (F32, BF16, F16), dtype
-    fold = lib().bn_fold if dtype == F32 else _fn("bn_fold_bf16", dtype)
-    fold(w_ohwi_ptr, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-         bn.running_var.data_ptr(), float(bn.eps), w_out.data_ptr(), b_out.data_ptr(), K, taps, cin, cpad, _stream())
+    _launch(lib().bn_fold, lib().bn_fold_h16, dtype, w_ohwi_ptr, bn.weight.data_ptr(), bn.bias.data_ptr(),
+            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps), w_out.data_ptr(), b_out.data_ptr(), K, taps,
+            cin, cpad)
     return w_out, b_out
 
 
@@ -402,11 +402,21 @@ def get_compute_mode() -> str:
 
 
 # ------------------------------------------------------------------------------------------------
-# 16-bit stored operands (csrc/bgemm.hip): activations / weight shadow bf16 or f16, accumulation fp32.  The bf16_* wrappers
-# below dispatch by the dtype of their 16-bit operand: torch.float16 tensors go to the f16-storage twins (ds6g_f16_*,
-# *_f16*) of the same kernels; outputs take the operand's dtype.
+# 16-bit stored operands (csrc/bgemm.hip): activations / weight shadow bf16 or f16, accumulation fp32.  Each kernel has one
+# entry point (ds6g_h16_*, *_h16*) whose first argument names the storage type; the bf16_* wrappers below pass the code of
+# their 16-bit operand's dtype, and outputs take that dtype.
 BF16 = torch.bfloat16
 F16 = torch.float16
+_ST16 = {BF16: 1, F16: 2}   # DS6G_ST_BF16 / DS6G_ST_F16 of include/ds6g.h
+
+
+def _launch(f32_entry, h16_entry, dtype, *args):
+    """a kernel that exists for all three storages, on the current stream: its fp32 entry point, or the 16-bit one with the
+    storage code of `dtype` in front"""
+    if dtype == F32:
+        f32_entry(*args, _stream())
+    else:
+        h16_entry(_ST16[dtype], *args, _stream())
 
 
 def _chk16(t, *shape, dtype=None):
@@ -417,14 +427,6 @@ def _chk16(t, *shape, dtype=None):
         assert tuple(t.shape) == tuple(shape), (tuple(t.shape), shape)
 
 
-def _fn(name, dtype):
-    """the C entry point `name` (a bf16 one) for storage `dtype`: its f16 twin, or (a "bf16_" name) the fp32 kernel it mirrors"""
-    if dtype != BF16:
-        assert dtype in (F32, F16), dtype
-        name = name.replace("bf16", "f16") if dtype == F16 else name.removeprefix("bf16_")
-    return getattr(lib(), name)
-
-
 def bf16_linear_fwd(x, w16_ptr, b_ptr, N, relu=False, residual=None, drop_p=0.0, seed=0, seed_off=0, out16=True):
     """y = residual + dropout(act(x w^T + b)): x [M, K] bf16, w [N, K] bf16; y bf16, or fp32 (always with a residual)"""
     M, K = x.shape
@@ -433,8 +435,8 @@ def bf16_linear_fwd(x, w16_ptr, b_ptr, N, relu=False, residual=None, drop_p=0.0,
     y = torch.empty((M, N), dtype=x.dtype if out16 else F32, device=x.device)
     if residual is not None:
         _chk(residual, M, N)
-    _fn("bf16_linear_fwd", x.dtype)(_p(x), w16_ptr, b_ptr, _p(y), int(out16), M, N, K, int(relu), _p(residual), float(drop_p), seed,
-                          seed_off, _stream())
+    lib().h16_linear_fwd(_ST16[x.dtype], _p(x), w16_ptr, b_ptr, _p(y), int(out16), M, N, K, int(relu), _p(residual), float(drop_p), seed,
+                         seed_off, _stream())
     return y
 
 
@@ -449,7 +451,7 @@ def bf16_linear_dgrad(dy, w16_ptr, K, relu_mask_src=None, out16=True, out=None, 
         assert tuple(relu_mask_src.shape) == (M, K) and relu_mask_src.is_contiguous() and out16
         mask16 = int(relu_mask_src.dtype != F32)
         assert relu_mask_src.dtype in (F32, dy.dtype)
-    _fn("bf16_linear_dgrad", dy.dtype)(_p(dy), w16_ptr, _p(dx), int(out16), M, N, K, _p(relu_mask_src), mask16, int(accumulate), _stream())
+    lib().h16_linear_dgrad(_ST16[dy.dtype], _p(dy), w16_ptr, _p(dx), int(out16), M, N, K, _p(relu_mask_src), mask16, int(accumulate), _stream())
     return dx
 
 
@@ -460,7 +462,7 @@ def bf16_linear_wgrad(x, dy, dw_ptr, ws: Workspace, accumulate=False, dbias_ptr=
     assert M == M2
     _chk16(x)
     _chk16(dy, dtype=x.dtype)
-    _fn("bf16_linear_wgrad", x.dtype)(_p(x), _p(dy), dw_ptr, dbias_ptr, M, N, K, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    lib().h16_linear_wgrad(_ST16[x.dtype], _p(x), _p(dy), dw_ptr, dbias_ptr, M, N, K, int(accumulate), ws.ptr, ws.nbytes, _stream())
 
 
 def bf16_conv2d_fwd(x, w16_ptr, K, R, S, stride, pad, out16=True):
@@ -468,7 +470,7 @@ def bf16_conv2d_fwd(x, w16_ptr, K, R, S, stride, pad, out16=True):
     _chk16(x)
     Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
     y = torch.empty((N, Ho, Wo, K), dtype=x.dtype if out16 else F32, device=x.device)
-    _fn("bf16_conv2d_fwd", x.dtype)(_p(x), w16_ptr, _p(y), int(out16), N, H, W, C, K, R, S, stride, pad, _stream())
+    lib().h16_conv2d_fwd(_ST16[x.dtype], _p(x), w16_ptr, _p(y), int(out16), N, H, W, C, K, R, S, stride, pad, _stream())
     return y
 
 
@@ -482,8 +484,8 @@ def bf16_conv2d_bias_act_fwd(x, w16_ptr, bias_ptr, K, R, S, stride, pad, relu=0,
     y = torch.empty((N, Ho, Wo, K), dtype=x.dtype, device=x.device)
     if residual is not None:
         _chk16(residual, N, Ho, Wo, K, dtype=x.dtype)
-    _fn("bf16_conv2d_bias_act_fwd", x.dtype)(_p(x), w16_ptr, bias_ptr, _p(residual), _p(y), N, H, W, C, K, R, S, stride, pad,
-                                             int(relu), _stream())
+    lib().h16_conv2d_bias_act_fwd(_ST16[x.dtype], _p(x), w16_ptr, bias_ptr, _p(residual), _p(y), N, H, W, C, K, R, S, stride, pad,
+                                  int(relu), _stream())
     return y
 
 
@@ -496,8 +498,8 @@ def bf16_conv2d_fwd_bnstats(x, w16_ptr, K, R, S, stride, pad, mean, invstd, rm_p
     _chk(invstd, K)
     Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
     y = torch.empty((N, Ho, Wo, K), dtype=x.dtype, device=x.device)
-    _fn("bf16_conv2d_fwd_bnstats", x.dtype)(_p(x), w16_ptr, _p(y), N, H, W, C, K, R, S, stride, pad, eps, momentum, _p(mean),
-                                  _p(invstd), rm_ptr, rv_ptr, ws.ptr, ws.nbytes, _stream())
+    lib().h16_conv2d_fwd_bnstats(_ST16[x.dtype], _p(x), w16_ptr, _p(y), N, H, W, C, K, R, S, stride, pad, eps, momentum, _p(mean),
+                                 _p(invstd), rm_ptr, rv_ptr, ws.ptr, ws.nbytes, _stream())
     return y
 
 
@@ -508,7 +510,7 @@ def bf16_conv2d_dgrad(dy, w16_ptr, x_shape, R, S, stride, pad, out16=True, out=N
     _chk16(dy, N, Ho, Wo, K)
     dx = out if out is not None else torch.empty(x_shape, dtype=dy.dtype if out16 else F32, device=dy.device)
     assert dx.dtype == (dy.dtype if out16 else F32) and tuple(dx.shape) == tuple(x_shape) and dx.is_contiguous()
-    _fn("bf16_conv2d_dgrad", dy.dtype)(_p(dy), w16_ptr, _p(dx), int(out16), N, H, W, C, K, R, S, stride, pad, int(accumulate), _stream())
+    lib().h16_conv2d_dgrad(_ST16[dy.dtype], _p(dy), w16_ptr, _p(dx), int(out16), N, H, W, C, K, R, S, stride, pad, int(accumulate), _stream())
     return dx
 
 
@@ -518,7 +520,7 @@ def bf16_conv2d_wgrad(x, dy, dw_ptr, R, S, stride, pad, ws: Workspace, accumulat
     Ho, Wo = conv_out_hw(H, W, R, S, stride, pad)
     K = dy.shape[3]
     _chk16(dy, N, Ho, Wo, K, dtype=x.dtype)
-    _fn("bf16_conv2d_wgrad", x.dtype)(_p(x), _p(dy), dw_ptr, N, H, W, C, K, R, S, stride, pad, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    lib().h16_conv2d_wgrad(_ST16[x.dtype], _p(x), _p(dy), dw_ptr, N, H, W, C, K, R, S, stride, pad, int(accumulate), ws.ptr, ws.nbytes, _stream())
 
 
 def cast_bf16(src, out=None, dtype=BF16):
@@ -526,7 +528,7 @@ def cast_bf16(src, out=None, dtype=BF16):
     _chk(src)
     dst = out if out is not None else torch.empty(src.shape, dtype=dtype, device=src.device)
     assert dst.dtype in (BF16, F16) and dst.numel() == src.numel() and dst.is_contiguous()
-    _fn("cast_f32_bf16", dst.dtype)(_p(src), _p(dst), src.numel(), _stream())
+    lib().cast_f32_h16(_ST16[dst.dtype], _p(src), _p(dst), src.numel(), _stream())
     return dst
 
 
@@ -537,7 +539,7 @@ def layernorm_fwd_bf16(x, gamma_ptr, beta_ptr, eps=1e-5, dtype=BF16):
     y = torch.empty((M, C), dtype=dtype, device=x.device)
     mean = torch.empty(M, dtype=F32, device=x.device)
     rstd = torch.empty(M, dtype=F32, device=x.device)
-    _fn("layernorm_fwd_bf16out", dtype)(_p(x), gamma_ptr, beta_ptr, _p(y), _p(mean), _p(rstd), M, C, eps, _stream())
+    lib().layernorm_fwd_h16out(_ST16[dtype], _p(x), gamma_ptr, beta_ptr, _p(y), _p(mean), _p(rstd), M, C, eps, _stream())
     return y, mean, rstd
 
 
@@ -553,8 +555,8 @@ def layernorm_bwd_bf16(dy, x, mean, rstd, gamma_ptr, dgamma_ptr, dbeta_ptr, ws: 
     dx = torch.empty_like(x)
     dxd = torch.empty((M, C), dtype=dtype, device=x.device) if want_drop else None
     p, seed, off = drop if drop is not None else (0.0, 0, 0)
-    _fn("layernorm_bwd_bf16", dtype)(_p(dy), int(dy.dtype != F32), _p(x), _p(mean), _p(rstd), gamma_ptr, _p(add), _p(dx), dgamma_ptr,
-                             dbeta_ptr, M, C, int(accumulate), _p(dxd), float(p), seed, off, ws.ptr, ws.nbytes, _stream())
+    lib().layernorm_bwd_h16(_ST16[dtype], _p(dy), int(dy.dtype != F32), _p(x), _p(mean), _p(rstd), gamma_ptr, _p(add), _p(dx), dgamma_ptr,
+                            dbeta_ptr, M, C, int(accumulate), _p(dxd), float(p), seed, off, ws.ptr, ws.nbytes, _stream())
     return dx, dxd
 
 
@@ -596,7 +598,7 @@ def attention_bwd_bf16(q, k, v, o16, d_o, lse, B, T, nh, ws: Workspace, drop_p=0
 # ---- bf16-storage path: BatchNorm / pooling / resampling on bf16 feature maps (statistics and arithmetic fp32) ----
 def bf16_bn_stats(x2d_rows, C, x, mean, invstd, rm_ptr, rv_ptr, ws: Workspace, eps=1e-5, momentum=0.1):
     _chk16(x)
-    _fn("bf16_bn_stats", x.dtype)(_p(x), x2d_rows, C, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr, ws.nbytes, _stream())
+    lib().h16_bn_stats(_ST16[x.dtype], _p(x), x2d_rows, C, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr, ws.nbytes, _stream())
 
 
 def bf16_bn_apply(x, mean, invstd, gamma_ptr, beta_ptr, relu, residual=None):
@@ -605,8 +607,8 @@ def bf16_bn_apply(x, mean, invstd, gamma_ptr, beta_ptr, relu, residual=None):
     y = torch.empty_like(x)
     if residual is not None:
         _chk16(residual, *x.shape, dtype=x.dtype)
-    _fn("bf16_bn_apply", x.dtype)(_p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(residual), _p(y), x.numel() // C, C, int(relu),
-                        _stream())
+    lib().h16_bn_apply(_ST16[x.dtype], _p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(residual), _p(y), x.numel() // C, C, int(relu),
+                       _stream())
     return y
 
 
@@ -619,8 +621,8 @@ def bf16_bn_bwd(dy, y_mask, x, mean, invstd, gamma_ptr, dgamma_ptr, dbeta_ptr, w
     C = x.shape[-1]
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
-    _fn("bf16_bn_bwd", x.dtype)(_p(dy), _p(y_mask), _p(x), _p(mean), _p(invstd), gamma_ptr, relu_beta_ptr, _p(dx), dgamma_ptr, dbeta_ptr,
-                      _p(dres), x.numel() // C, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    lib().h16_bn_bwd(_ST16[x.dtype], _p(dy), _p(y_mask), _p(x), _p(mean), _p(invstd), gamma_ptr, relu_beta_ptr, _p(dx), dgamma_ptr, dbeta_ptr,
+                     _p(dres), x.numel() // C, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
     return dx, dres
 
 
@@ -631,7 +633,7 @@ def bn_relu_maxpool_bf16out(x, mean, invstd, gamma_ptr, beta_ptr, dtype=BF16):
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     y = torch.empty((N, Ho, Wo, C), dtype=dtype, device=x.device)
     idx = torch.empty((N, Ho, Wo, C), dtype=torch.uint8, device=x.device)
-    _fn("bn_relu_maxpool3x3s2_fwd_bf16out", dtype)(_p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
+    lib().bn_relu_maxpool3x3s2_fwd_h16out(_ST16[dtype], _p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
     return y, idx
 
 
@@ -640,8 +642,8 @@ def bn_bwd_maxpool_bf16in(dpool, idx, x, mean, invstd, gamma_ptr, beta_ptr, dgam
     _chk(x)
     _chk16(dpool, N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C)
     dx = torch.empty_like(x)
-    _fn("bn_bwd_maxpool_bf16in", dpool.dtype)(_p(dpool), _p(idx), _p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
-                                dbeta_ptr, N, H, W, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    lib().bn_bwd_maxpool_h16in(_ST16[dpool.dtype], _p(dpool), _p(idx), _p(x), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
+                               dbeta_ptr, N, H, W, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
     return dx
 
 
@@ -655,11 +657,11 @@ def bf16_stem_fwd(x16, w_ohwi_ptr, cin, ws: Workspace, stats=None, rm_ptr=0, rv_
     tensors: also the train-mode BatchNorm statistics of y (running statistics updated in place)"""
     N, H, W, C4 = x16.shape
     _chk16(x16)
-    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(_fn("bf16_stem_workspace_bytes", x16.dtype)())
+    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(lib().h16_stem_workspace_bytes())
     y = torch.empty((N, H // 2, W // 2, 64), dtype=x16.dtype, device=x16.device)
     mean, invstd = stats if stats is not None else (None, None)
-    _fn("bf16_stem_fwd", x16.dtype)(_p(x16), w_ohwi_ptr, cin, _p(y), N, H, W, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr,
-                        ws.nbytes, _stream())
+    lib().h16_stem_fwd(_ST16[x16.dtype], _p(x16), w_ohwi_ptr, cin, _p(y), N, H, W, eps, momentum, _p(mean), _p(invstd), rm_ptr, rv_ptr, ws.ptr,
+                       ws.nbytes, _stream())
     return y
 
 
@@ -668,7 +670,7 @@ def bf16_stem_pack_filter(w16, out=None):
     _chk16(w16, 64, 49, 4)
     wp = out if out is not None else torch.empty((64, 7, 8, 4), dtype=w16.dtype, device=w16.device)
     _chk16(wp, 64, 7, 8, 4, dtype=w16.dtype)
-    _fn("bf16_stem_pack_filter", w16.dtype)(_p(w16), _p(wp), _stream())
+    lib().h16_stem_pack_filter(_ST16[w16.dtype], _p(w16), _p(wp), _stream())
     return wp
 
 
@@ -680,7 +682,7 @@ def bf16_stem_bias_relu_fwd(x16, w_packed, bias):
     _chk(bias, 64)
     assert C4 == 4 and bf16_stem_ok(H, W), tuple(x16.shape)
     y = torch.empty((N, H // 2, W // 2, 64), dtype=x16.dtype, device=x16.device)
-    _fn("bf16_stem_bias_relu_fwd", x16.dtype)(_p(x16), _p(w_packed), _p(bias), _p(y), N, H, W, _stream())
+    lib().h16_stem_bias_relu_fwd(_ST16[x16.dtype], _p(x16), _p(w_packed), _p(bias), _p(y), N, H, W, _stream())
     return y
 
 
@@ -690,7 +692,7 @@ def bf16_maxpool3x3s2_fwd(x16):
     _chk16(x16)
     assert C % 8 == 0, C
     y = torch.empty((N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C), dtype=x16.dtype, device=x16.device)
-    _fn("bf16_maxpool3x3s2_fwd", x16.dtype)(_p(x16), _p(y), N, H, W, C, _stream())
+    lib().h16_maxpool3x3s2_fwd(_ST16[x16.dtype], _p(x16), _p(y), N, H, W, C, _stream())
     return y
 
 
@@ -698,8 +700,8 @@ def bf16_stem_wgrad(x16, dy16, dw_ptr, cin, ws: Workspace, accumulate=False):
     N, H, W, C4 = x16.shape
     _chk16(x16)
     _chk16(dy16, N, H // 2, W // 2, 64, dtype=x16.dtype)
-    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(_fn("bf16_stem_workspace_bytes", x16.dtype)())
-    _fn("bf16_stem_wgrad", x16.dtype)(_p(x16), _p(dy16), dw_ptr, cin, N, H, W, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    assert C4 == 4 and bf16_stem_ok(H, W) and ws.nbytes >= int(lib().h16_stem_workspace_bytes())
+    lib().h16_stem_wgrad(_ST16[x16.dtype], _p(x16), _p(dy16), dw_ptr, cin, N, H, W, int(accumulate), ws.ptr, ws.nbytes, _stream())
 
 
 def bf16_stem_bn_relu_maxpool(x16, mean, invstd, gamma_ptr, beta_ptr):
@@ -708,7 +710,7 @@ def bf16_stem_bn_relu_maxpool(x16, mean, invstd, gamma_ptr, beta_ptr):
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     y = torch.empty((N, Ho, Wo, C), dtype=x16.dtype, device=x16.device)
     idx = torch.empty((N, Ho, Wo, C), dtype=torch.uint8, device=x16.device)
-    _fn("bf16_stem_bn_relu_maxpool_fwd", x16.dtype)(_p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
+    lib().h16_stem_bn_relu_maxpool_fwd(_ST16[x16.dtype], _p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(y), _p(idx), N, H, W, C, _stream())
     return y, idx
 
 
@@ -717,8 +719,8 @@ def bf16_stem_bn_bwd_maxpool(dpool, idx, x16, mean, invstd, gamma_ptr, beta_ptr,
     _chk16(x16)
     _chk16(dpool, N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C, dtype=x16.dtype)
     dx = torch.empty_like(x16)
-    _fn("bf16_stem_bn_bwd_maxpool", x16.dtype)(_p(dpool), _p(idx), _p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
-                                   dbeta_ptr, N, H, W, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
+    lib().h16_stem_bn_bwd_maxpool(_ST16[x16.dtype], _p(dpool), _p(idx), _p(x16), _p(mean), _p(invstd), gamma_ptr, beta_ptr, _p(dx), dgamma_ptr,
+                                  dbeta_ptr, N, H, W, C, int(accumulate), ws.ptr, ws.nbytes, _stream())
     return dx
 
 
@@ -736,8 +738,8 @@ def attention_fwd_bf16(q, k, v, B, T, nh, ws: Workspace, drop_p=0.0, seed=0, see
     assert _rows16(k, M, C) == ldq and _rows16(v, M, C) == ldq and q.dtype == k.dtype == v.dtype
     o = torch.empty((M, C), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, nh, T), dtype=F32, device=q.device)
-    _fn("attention_fwd_bf16", q.dtype)(_p(q), _p(k), _p(v), _p(o), _p(lse), B, T, nh, C // nh, ldq, C, float(drop_p), seed, seed_off,
-                             ws.ptr, ws.nbytes, _stream())
+    lib().attention_fwd_h16(_ST16[q.dtype], _p(q), _p(k), _p(v), _p(o), _p(lse), B, T, nh, C // nh, ldq, C, float(drop_p), seed, seed_off,
+                            ws.ptr, ws.nbytes, _stream())
     return o, lse
 
 
@@ -758,9 +760,85 @@ def attention_bwd_bf16io(q, k, v, o, d_o, lse, B, T, nh, ws: Workspace, drop_p=0
         assert t.dtype == q.dtype and tuple(t.shape) == (M, C) and t.stride(1) == 1 and t.stride(0) % 4 == 0
     ldd = dq.stride(0)
     assert dk.stride(0) == ldd and dv.stride(0) == ldd
-    _fn("attention_bwd_bf16io", q.dtype)(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, T, nh,
-                               C // nh, ldq, C, ldd, float(drop_p), seed, seed_off, ws.ptr, ws.nbytes, _stream())
+    lib().attention_bwd_h16io(_ST16[q.dtype], _p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, T, nh,
+                              C // nh, ldq, C, ldd, float(drop_p), seed, seed_off, ws.ptr, ws.nbytes, _stream())
     return dq, dk, dv
+
+
+# ---- feature-map kernels of the model walk (csrc/spatial.hip): NHWC maps of the walk's storage (fp32 / bf16 / f16, one dtype per
+# call), tokens (B * T * C elements) and pooled vectors fp32; every output is the caller's tensor ----
+def _chkmap(t, *shape, dtype=None):
+    (_chk if t.dtype == F32 else _chk16)(t, *shape)
+    assert dtype is None or t.dtype == dtype, (t.dtype, dtype)
+
+
+def pack_input(src, dst, t, normalize):
+    """NCHW fp32 frames src [B, cin, H, W] -> frame slot t of the stem input dst [B * S, H, W, 4], normalize_imagenet fused"""
+    B, cin, H, W = src.shape
+    S = dst.shape[0] // B
+    _chkmap(dst, B * S, H, W, 4)
+    assert src.dtype == F32 and src.is_cuda and 0 <= t < S, (src.dtype, src.device, t, S)
+    if dst.dtype == F32:
+        lib().pack_input(_p(src), _p(dst), B, cin, H, W, 4, S, t, int(normalize), _stream())
+    else:
+        lib().pack_input_h16(_ST16[dst.dtype], _p(src), _p(dst), B, cin, H, W, S, t, int(normalize), _stream())
+
+
+def avgpool_tokens_fwd(feat, pos_emb_ptr, tokens, frames_per_sample, mod_off, T, drop_p=0.0, seed=0, seed_off=0):
+    """token rows mod_off.. of each sample = embd_drop(8 x 8 average pool of its frames in feat [N, H, H, C] + pos_emb)"""
+    N, H, _, C = feat.shape
+    _chkmap(feat, N, H, H, C)
+    _chk(tokens, N // frames_per_sample, T, C)
+    _launch(lib().avgpool_tokens_fwd, lib().h16_avgpool_tokens_fwd, feat.dtype, _p(feat), pos_emb_ptr, _p(tokens), N, H, C,
+            frames_per_sample, mod_off, T, float(drop_p), seed, seed_off)
+
+
+def avgpool_tokens_bwd(dtok, dfeat_in, dfeat, frames_per_sample, mod_off, T):
+    """dfeat = dfeat_in + the token gradient dtok spread back over the pooling windows"""
+    N, H, _, C = dfeat.shape
+    _chkmap(dfeat, N, H, H, C)
+    _chkmap(dfeat_in, N, H, H, C, dtype=dfeat.dtype)
+    _chk(dtok)
+    assert dtok.numel() == N // frames_per_sample * T * C, (tuple(dtok.shape), N, frames_per_sample, T, C)
+    _launch(lib().avgpool_tokens_bwd, lib().h16_avgpool_tokens_bwd, dfeat.dtype, _p(dtok), _p(dfeat_in), _p(dfeat), N, H, C,
+            frames_per_sample, mod_off, T)
+
+
+def upsample_add_fwd(feat, tokens, out, frames_per_sample, mod_off, T):
+    """out = feat [N, H, H, C] + the bilinear upsampling of each frame's 8 x 8 token block"""
+    N, H, _, C = feat.shape
+    _chkmap(feat, N, H, H, C)
+    _chkmap(out, N, H, H, C, dtype=feat.dtype)
+    _chk(tokens)
+    assert tokens.numel() == N // frames_per_sample * T * C, (tuple(tokens.shape), N, frames_per_sample, T, C)
+    _launch(lib().upsample_add_fwd, lib().h16_upsample_add_fwd, feat.dtype, _p(feat), _p(tokens), _p(out), N, H, C,
+            frames_per_sample, mod_off, T)
+
+
+def upsample_add_bwd(dout, dtok, frames_per_sample, mod_off, T):
+    """the token gradient of upsample_add_fwd, written to the token rows of dtok that the forward read"""
+    N, H, _, C = dout.shape
+    _chkmap(dout, N, H, H, C)
+    _chk(dtok)
+    assert dtok.numel() == N // frames_per_sample * T * C, (tuple(dtok.shape), N, frames_per_sample, T, C)
+    _launch(lib().upsample_add_bwd, lib().h16_upsample_add_bwd, dout.dtype, _p(dout), _p(dtok), N, H, C, frames_per_sample,
+            mod_off, T)
+
+
+def global_pool(feat, pooled):
+    """pooled [N, C] = mean over the positions of feat [N, 8, 8, C]"""
+    N, C = pooled.shape
+    _chkmap(feat, N, 8, 8, C)
+    _chk(pooled)
+    _launch(lib().global_pool, lib().h16_global_pool, feat.dtype, _p(feat), _p(pooled), N, C)
+
+
+def head_bwd(dfused, dfeat, frames_per_sample):
+    """dfeat [N, 8, 8, C] = backward of global_pool + the sum over frames, from dfused [B, C]"""
+    N, _, _, C = dfeat.shape
+    _chkmap(dfeat, N, 8, 8, C)
+    _chk(dfused, N // frames_per_sample, C)
+    _launch(lib().head_bwd, lib().h16_head_bwd, dfeat.dtype, _p(dfused), _p(dfeat), N, C, frames_per_sample)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -22,6 +22,12 @@
 extern "C" {
 #endif
 
+/* 16-bit storage: a ds6g_h16_* / *_h16* entry point is ONE kernel over the type of its 16-bit tensors, named by its first
+ * argument st16; any other value (0, fp32, has entry points of its own) returns DS6G_ERR_ARG before anything is launched.  Their
+ * comments say "bf16"; with DS6G_ST_F16 read IEEE half: same layouts, v_mfma_f32_32x32x16_f16 for ..._bf16, round to nearest
+ * even, beyond 65504 +-inf (never clamped: the loss scaler of step.hip finds it in the fp32 gradients and skips the step). */
+#define DS6G_ST_BF16 1
+#define DS6G_ST_F16 2
 int ds6g_version(void);
 /* which implicit-GEMM instantiation the last conv/linear call launched: 10000*wide + 1000*epilogue + 100*walk +
  * 10*mode + tile (wide 1 = 32-column k-tiles, 0 = 16; epilogue 1 = fused bias/ReLU/dropout/residual epilogue, 0 = plain
@@ -47,8 +53,8 @@ int ds6g_debug_occupy_cus(int workgroups, int lds_bytes, int microseconds, void*
  *   1           "bf16"  the "bf16 forward/backward" throughput configuration of BASELINE.json configs[1] / [4]: the
  *                       fp32-storage entry points round their operands to bf16 (RNE) between the LDS fragment and the
  *                       matrix core; the host (model.py) additionally routes every conv / linear but the 4-channel
- *                       stems, and attention, to the bf16-STORAGE entry points (ds6g_bf16_*: activations, their
- *                       gradients and a per-step shadow of the weights are bf16 in HBM; fp32 master weights).
+ *                       stems, and attention, to the 16-bit-STORAGE entry points (ds6g_h16_*, *_h16*) with DS6G_ST_BF16:
+ *                       activations, their gradients and a per-step weight shadow are bf16 in HBM; fp32 master weights.
  *   2           "f32x3" split bf16: each fp32 operand a = hi + lo with hi = bf16(a), lo = bf16(a - hi); a*b is
  *                       evaluated as hi*hi + hi*lo + lo*hi on the bf16 matrix cores with fp32 accumulation - relative
  *                       product error <= ~2^-16 (between fp32 and TF32), fp32 storage.
@@ -57,7 +63,7 @@ int ds6g_debug_occupy_cus(int workgroups, int lds_bytes, int microseconds, void*
  *                       convs keep the fp32 Winograd kernels.
  *   4                   unused (refused).
  *   5           "f16"   f16 storage: the host routes the same convs / linears / attention / BN / LN / pooling as in "bf16" to
- *                       the f16-storage twins (ds6g_f16_*, *_f16*); every fp32-storage kernel runs exactly as in mode 0
+ *                       the same entry points with st16 = DS6G_ST_F16; every fp32-storage kernel runs exactly as in mode 0
  *                       (their operand mode stays 0), so eval, the small linears and the fp32 stems are exact fp32. */
 int ds6g_set_compute_mode(int mode);
 int ds6g_get_compute_mode(void);
@@ -96,14 +102,10 @@ int ds6g_bn_fold(const float* w, const float* gamma, const float* beta, const fl
                  const float* running_var, float eps, float* w_out, float* bias_out, int K, int taps, int cin, int cpad,
                  void* stream);
 /* the same fold for the frozen inference engine's 16-bit filters (TransFuser.freeze_inference): the scale is applied in
- * fp32 and the product rounded ONCE (nearest even) to bf16 / f16 on the store; bias_out stays fp32.  w_out: [K][taps][cpad]
- * bf16 / f16. */
-int ds6g_bn_fold_bf16(const float* w, const float* gamma, const float* beta, const float* running_mean,
-                      const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin,
-                      int cpad, void* stream);
-int ds6g_bn_fold_f16(const float* w, const float* gamma, const float* beta, const float* running_mean,
-                     const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin,
-                     int cpad, void* stream);
+ * fp32 and the product rounded ONCE (nearest even) on the store to w_out [K][taps][cpad] bf16 / f16; bias_out stays fp32. */
+int ds6g_bn_fold_h16(int st16, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                     const float* running_var, float eps, void* w_out, float* bias_out, int K, int taps, int cin, int cpad,
+                     void* stream);
 /* ---- winograd.hip : Winograd F(2x2, 3x3) for the 3x3 / stride 1 / pad 1 convolutions of the BasicBlocks
  * (model2_seq.py:510-512,528-530,546-548,565-567): 16 GEMMs on transformed 4x4 tiles, 2.25x fewer MFMA FLOPs.
  * winograd_weights builds U[16][K][C] = G g G^T from the OHWI filter (transpose_flip = 1: the dgrad filter, i.e.
@@ -141,62 +143,62 @@ int ds6g_linear_wgrad(const float* x, const float* dy, float* dw, float* dbias, 
  * residual: fp32.  Tiles travel HBM -> LDS as bf16 by LDS-DMA and feed v_mfma_f32_32x32x16_bf16 without conversion.
  * Shape limits (every layer of the model but the 4-channel stems): the reduction channel count is a multiple of 64, the
  * other a multiple of 8; dgrad: stride 1, or 2 with even H, W; wgrad: Wo % 64 == 0, or 64 % Wo == 0 with Ho % (64 / Wo) == 0, or a Linear. */
-int ds6g_bf16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
-                         int stride, int pad, void* stream);
+int ds6g_h16_conv2d_fwd(int st16, const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R,
+                        int S, int stride, int pad, void* stream);
 /* inference form of Conv2d + eval-mode BatchNorm2d (+ identity) (+ ReLU) on 16-bit storage (the BasicBlock convs under
- * model.eval(), model2_seq.py:510-512,528-530,546-548,565-567): the BN is folded into w (bf16, ds6g_bn_fold_bf16) and bias
+ * model.eval(), model2_seq.py:510-512,528-530,546-548,565-567): the BN is folded into w (bf16, ds6g_bn_fold_h16) and bias
  * (fp32); y = act(conv(x, w) + bias [+ residual]); relu: 0 none, 1 before the residual add, 2 after it - the contract of
  * ds6g_conv2d_bias_act_fwd.  x, w, residual (nullable), y: bf16; bias and the residual are added to the fp32 accumulator
- * and the result is rounded once.  Shape limits of ds6g_bf16_conv2d_fwd. */
-int ds6g_bf16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N,
-                                  int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream);
+ * and the result is rounded once.  Shape limits of ds6g_h16_conv2d_fwd. */
+int ds6g_h16_conv2d_bias_act_fwd(int st16, const void* x, const void* w, const float* bias, const void* residual, void* y,
+                                 int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream);
 /* conv (bf16 output) + the train-mode BatchNorm statistics of its output in one call (the BasicBlock pairs conv1 / bn1,
  * conv2 / bn2, downsample.0 / .1 of torchvision's ResNet, model2_seq.py:510-512,528-530,546-548,565-567): the conv's epilogue
  * writes per-tile column sums / sums of squares of the STORED bf16 tile, a small finalize kernel turns them into mean /
- * invstd and updates the running statistics - what ds6g_bf16_bn_stats(y) computes, without its pass over y. */
-size_t ds6g_bf16_conv_bnstats_workspace_bytes(long M, int K);
-int ds6g_bf16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
-                                 int stride, int pad, float eps, float momentum, float* mean, float* invstd,
-                                 float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
-int ds6g_bf16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R,
-                           int S, int stride, int pad, int accumulate, void* stream);
-int ds6g_bf16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
-                           int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream);
+ * invstd and updates the running statistics - what ds6g_h16_bn_stats(y) computes, without its pass over y. */
+size_t ds6g_h16_conv_bnstats_workspace_bytes(long M, int K);
+int ds6g_h16_conv2d_fwd_bnstats(int st16, const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R,
+                                int S, int stride, int pad, float eps, float momentum, float* mean, float* invstd,
+                                float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_conv2d_dgrad(int st16, const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K,
+                          int R, int S, int stride, int pad, int accumulate, void* stream);
+int ds6g_h16_conv2d_wgrad(int st16, const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
+                          int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream);
 /* nn.Linear of the GPT blocks (model2_seq.py:97-99,109,121-126,131-132) on bf16 operands; a fused residual add writes the
  * fp32 residual stream (out16 must be 0 then); mask_src [M][K]: bf16 (mask16) or fp32, with a bf16 dx only. */
-int ds6g_bf16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
-                         const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
-int ds6g_bf16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
-                           int mask16, int accumulate, void* stream);
-int ds6g_bf16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
-                           float* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_linear_fwd(int st16, const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K,
+                        int relu, const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
+int ds6g_h16_linear_dgrad(int st16, const void* dy, const void* w, void* dx, int out16, int M, int N, int K,
+                          const void* mask_src, int mask16, int accumulate, void* stream);
+int ds6g_h16_linear_wgrad(int st16, const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
+                          float* ws, size_t ws_bytes, void* stream);
 
 /* ---- stem.hip : the 7x7 / stride 2 / pad 3 stem convs (torchvision ResNet conv1 via model2_seq.py:495,500,505) of the
- * bf16 configuration.  x [N][H][W][4] bf16 (ds6g_pack_input_bf16; channels >= cin zero), w: the fp32 master filter
+ * bf16 configuration.  x [N][H][W][4] bf16 (ds6g_pack_input_h16; channels >= cin zero), w: the fp32 master filter
  * [64][7][7][cin] (OHWI), y / dy [N][H/2][W/2][64] bf16; H % 16 == 0, W % 32 == 0.  The forward also delivers the train-mode
- * BatchNorm statistics of y (mean == NULL: convolution only); ws >= ds6g_bf16_stem_workspace_bytes().  The BN -> ReLU ->
- * MaxPool pass over the bf16 conv output and its backward: ds6g_bf16_stem_bn_relu_maxpool_fwd / ds6g_bf16_stem_bn_bwd_maxpool. */
-size_t ds6g_bf16_stem_workspace_bytes(void);
-int ds6g_bf16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
-                       float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
-                       void* stream);
-int ds6g_bf16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
-                         size_t ws_bytes, void* stream);
-int ds6g_bf16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
-                                       const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream);
-int ds6g_bf16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean,
-                                  const float* invstd, const float* gamma, const float* relu_beta, void* dx, float* dgamma,
-                                  float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
-                                  size_t ws_bytes, void* stream);
+ * BatchNorm statistics of y (mean == NULL: convolution only); ws >= ds6g_h16_stem_workspace_bytes().  The BN -> ReLU ->
+ * MaxPool pass over the bf16 conv output and its backward: ds6g_h16_stem_bn_relu_maxpool_fwd / ds6g_h16_stem_bn_bwd_maxpool. */
+size_t ds6g_h16_stem_workspace_bytes(void);
+int ds6g_h16_stem_fwd(int st16, const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
+                      float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
+                      void* stream);
+int ds6g_h16_stem_wgrad(int st16, const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate,
+                        void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_stem_bn_relu_maxpool_fwd(int st16, const void* x, const float* mean, const float* invstd, const float* gamma,
+                                      const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream);
+int ds6g_h16_stem_bn_bwd_maxpool(int st16, const void* dpool, const uint8_t* idx, const void* x, const float* mean,
+                                 const float* invstd, const float* gamma, const float* relu_beta, void* dx, float* dgamma,
+                                 float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
+                                 size_t ws_bytes, void* stream);
 /* inference stem (conv1 + bn1 + relu + maxpool under model.eval(), model2_seq.py:495-507): the filter is prepared once per
- * snapshot - ds6g_bn_fold_bf16 with cpad = 4 gives w [64][7][7][4] bf16 and the fp32 bias, ds6g_bf16_stem_pack_filter lays
+ * snapshot - ds6g_bn_fold_h16 with cpad = 4 gives w [64][7][7][4] bf16 and the fp32 bias, ds6g_h16_stem_pack_filter lays
  * it out as the forward reads it, w_packed [64][7][8][4] - then y = relu(conv7x7/2(x, w_packed) + bias) in one launch with
- * the bias added before the one rounding (no workspace, no statistics), and ds6g_bf16_maxpool3x3s2_fwd is the 3x3 / 2 /
+ * the bias added before the one rounding (no workspace, no statistics), and ds6g_h16_maxpool3x3s2_fwd is the 3x3 / 2 /
  * pad 1 max-pool of a bf16 NHWC map without an arg-max index (C % 8 == 0). */
-int ds6g_bf16_stem_pack_filter(const void* w, void* w_packed, void* stream);
-int ds6g_bf16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
-                                 void* stream);
-int ds6g_bf16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream);
+int ds6g_h16_stem_pack_filter(int st16, const void* w, void* w_packed, void* stream);
+int ds6g_h16_stem_bias_relu_fwd(int st16, const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
+                                void* stream);
+int ds6g_h16_maxpool3x3s2_fwd(int st16, const void* x, void* y, int N, int H, int W, int C, void* stream);
 
 /* ---- norm.hip ----------------------------------------------------------------------------------
  * BatchNorm2d in train mode (+ReLU, +residual add of BasicBlock): torchvision BasicBlock via
@@ -226,22 +228,22 @@ int ds6g_layernorm_bwd(const float* dy, const float* x, const float* mean, const
                        void* ws, size_t ws_bytes, void* stream);
 /* bf16-storage path of BatchNorm2d: conv outputs, activations and their gradients are bf16 in HBM (x / residual / y /
  * dy / y_mask / dx / dres), the statistics, running stats, parameter gradients and every reduction stay fp32 / fp64. */
-int ds6g_bf16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd,
-                       float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
-int ds6g_bf16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                       const void* residual, void* y, long M, int C, int relu, void* stream);
-int ds6g_bf16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
-                     const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres, long M,
-                     int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_bn_stats(int st16, const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd,
+                      float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_bn_apply(int st16, const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                      const void* residual, void* y, long M, int C, int relu, void* stream);
+int ds6g_h16_bn_bwd(int st16, const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
+                    const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres, long M,
+                    int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream);
 /* bf16-storage path (GEMM-facing tensors are bf16; statistics, the residual stream and all arithmetic stay fp32):
- * layernorm_fwd_bf16out writes y as bf16; layernorm_bwd_bf16 reads dy as bf16 (dy16) or fp32, writes dx fp32 and dx_drop
+ * layernorm_fwd_h16out writes y as bf16; layernorm_bwd_h16 reads dy as bf16 (dy16) or fp32, writes dx fp32 and dx_drop
  * (nullable) = dropout(dx) as bf16 (drop_p = 0: a bf16 copy of dx, the next GEMM's operand). */
-int ds6g_layernorm_fwd_bf16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                               int M, int C, float eps, void* stream);
-int ds6g_layernorm_bwd_bf16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
-                            const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
-                            int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off,
-                            void* ws, size_t ws_bytes, void* stream);
+int ds6g_layernorm_fwd_h16out(int st16, const float* x, const float* gamma, const float* beta, void* y, float* mean,
+                              float* rstd, int M, int C, float eps, void* stream);
+int ds6g_layernorm_bwd_h16(int st16, const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
+                           const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
+                           int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                           size_t ws_bytes, void* stream);
 /* bias gradients: out[c] (+)= sum_r x[r][c] */
 size_t ds6g_colsum_workspace_bytes(long M, int C);
 int ds6g_colsum(const float* x, long M, int C, float* out, int accumulate, void* ws, size_t ws_bytes, void* stream);
@@ -278,13 +280,13 @@ int ds6g_attention_bwd_bf16(const float* q, const float* k, const float* v, cons
  * staged as bf16 LDS images by LDS-DMA and reach v_mfma_f32_32x32x16_bf16 unconverted (row reads: ds_read_b128, transposed
  * reads for the P.V / dS^T.Q / P^T.dO / dS.K products: ds_read_b64_tr_b16); lse, delta, the split slabs and the dS / P
  * hand-over tiles stay fp32.  ld_qkv and ld multiples of 8. */
-int ds6g_attention_fwd_bf16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh, int hd,
-                            int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                            void* stream);
-int ds6g_attention_bwd_bf16io(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
-                              float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd, int ld_qkv, int ld,
-                              int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                              void* stream);
+int ds6g_attention_fwd_h16(int st16, const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh,
+                           int hd, int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                           size_t ws_bytes, void* stream);
+int ds6g_attention_bwd_h16io(int st16, const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                             const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd,
+                             int ld_qkv, int ld, int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
+                             size_t ws_bytes, void* stream);
 
 /* ---- input.hip : device-side counterpart of CARLA_Data.__getitem__, data2_seq.py:42-173 --------
  * pack_image_u8: decoded RGB frame batch [B][H][W][3] uint8 (data2_seq.py:110-141, before its HWC->CHW transpose) ->
@@ -368,8 +370,8 @@ int ds6g_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, long ro
 /* normalize_imagenet + stack + NCHW->NHWC: model2_seq.py:36-45,481-482,491-493 */
 int ds6g_pack_input(const float* src, float* dst, int B, int Cs, int H, int W, int Cd, int frames_per_sample, int t,
                     int normalize_imagenet, void* stream);
-int ds6g_pack_input_bf16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
-                         int normalize_imagenet, void* stream);
+int ds6g_pack_input_h16(int st16, const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
+                        int normalize_imagenet, void* stream);
 int ds6g_pad_channels(const float* src, float* dst, long rows, int cin, int cout, int unpad, int accumulate,
                       void* stream);
 /* MaxPool2d(3,2,1) of the stems: model2_seq.py:498,503,508 */
@@ -386,26 +388,25 @@ int ds6g_bn_bwd_maxpool(const float* dpool, const uint8_t* idx, const float* x, 
                         int W, int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream);
 /* bf16-storage path: the 4-channel stem keeps the fp32-storage conv kernels (x, dx fp32); its pooled output is written as
  * bf16 (first tensor of the bf16 trunk) and the gradient of the pooled tensor arrives as bf16 */
-int ds6g_bn_relu_maxpool3x3s2_fwd_bf16out(const float* x, const float* mean, const float* invstd, const float* gamma,
-                                          const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C,
-                                          void* stream);
-int ds6g_bn_bwd_maxpool_bf16in(const void* dpool, const uint8_t* idx, const float* x, const float* mean,
-                               const float* invstd, const float* gamma, const float* relu_beta, float* dx, float* dgamma,
-                               float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
-                               size_t ws_bytes, void* stream);
+int ds6g_bn_relu_maxpool3x3s2_fwd_h16out(int st16, const float* x, const float* mean, const float* invstd, const float* gamma,
+                                         const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream);
+int ds6g_bn_bwd_maxpool_h16in(int st16, const void* dpool, const uint8_t* idx, const float* x, const float* mean,
+                              const float* invstd, const float* gamma, const float* relu_beta, float* dx, float* dgamma,
+                              float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws, size_t ws_bytes,
+                              void* stream);
 /* bf16-storage path of the pooling / resampling / head kernels below: feature maps (feat, out, dfeat, dout) bf16, tokens /
  * pos_emb / pooled vectors fp32 */
-int ds6g_bf16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
-                                 int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed,
-                                 uint64_t seed_off, void* stream);
-int ds6g_bf16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
-                                 int frames_per_sample, int mod_off, int T, void* stream);
-int ds6g_bf16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C,
-                               int frames_per_sample, int mod_off, int T, void* stream);
-int ds6g_bf16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
-                               int T, void* stream);
-int ds6g_bf16_global_pool(const void* feat, float* pooled, int N, int C, void* stream);
-int ds6g_bf16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream);
+int ds6g_h16_avgpool_tokens_fwd(int st16, const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
+                                int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed, uint64_t seed_off,
+                                void* stream);
+int ds6g_h16_avgpool_tokens_bwd(int st16, const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
+                                int frames_per_sample, int mod_off, int T, void* stream);
+int ds6g_h16_upsample_add_fwd(int st16, const void* feat, const float* tokens, void* out, int N, int H, int C,
+                              int frames_per_sample, int mod_off, int T, void* stream);
+int ds6g_h16_upsample_add_bwd(int st16, const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
+                              int T, void* stream);
+int ds6g_h16_global_pool(int st16, const void* feat, float* pooled, int N, int C, void* stream);
+int ds6g_h16_head_bwd(int st16, const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream);
 /* AdaptiveAvgPool2d((8,8)) + token pack + pos_emb + embd dropout: model2_seq.py:414,515-517,261-272 */
 int ds6g_avgpool_tokens_fwd(const float* feat, const float* pos_emb, float* tokens, int N, int H, int C,
                             int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed,
@@ -480,89 +481,7 @@ int ds6g_adamw_step_scaled(float* p, const float* g, float* m, float* v, float* 
                            const void* scaler_state, float beta1, float beta2, float eps, float wd, float ema_decay,
                            float grad_scale, void* stream);
 /* dst (bf16, RNE) = src (fp32): refreshes the bf16 shadow of the parameter arena for the bf16-storage path */
-int ds6g_cast_f32_bf16(const float* src, void* dst, long n, void* stream);
-/* ---- f16-STORAGE twins (compute mode 5, "f16"): the same kernels as the bf16-storage entry points above - same signatures,
- * arguments and layouts - with every 16-bit tensor (activations, their gradients, the weight shadow, the attention P / dS
- * hand-over tiles) stored as IEEE half and fed to v_mfma_f32_32x32x16_f16; accumulation, statistics, master weights and
- * gradients stay fp32.  Values are rounded to nearest even; a value beyond 65504 becomes +-inf (never clamped: the
- * dynamic loss scaler below finds it in the fp32 gradient arena and skips the step).  ds6g_bn_bwd_maxpool_f16in / ds6g_bn_relu_maxpool3x3s2_fwd_f16out are
- * the twins of the *_bf16in / *_bf16out stem kernels, ds6g_cast_f32_f16 of ds6g_cast_f32_bf16. */
-int ds6g_f16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R,
-                        int S, int stride, int pad, void* stream);
-int ds6g_f16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
-                                int stride, int pad, float eps, float momentum, float* mean, float* invstd,
-                                float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
-size_t ds6g_f16_conv_bnstats_workspace_bytes(long M, int K);
-int ds6g_f16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R,
-                          int S, int stride, int pad, int accumulate, void* stream);
-int ds6g_f16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
-                          int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream);
-int ds6g_f16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K,
-                        int relu, const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
-int ds6g_f16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
-                          int mask16, int accumulate, void* stream);
-int ds6g_f16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
-                          float* ws, size_t ws_bytes, void* stream);
-int ds6g_f16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N,
-                                 int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream);
-int ds6g_f16_stem_pack_filter(const void* w, void* w_packed, void* stream);
-int ds6g_f16_stem_bias_relu_fwd(const void* x, const void* w_packed, const float* bias, void* y, int N, int H, int W,
-                                void* stream);
-int ds6g_f16_maxpool3x3s2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream);
-size_t ds6g_f16_stem_workspace_bytes(void);
-int ds6g_f16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, int H, int W, float eps, float momentum,
-                      float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
-                      void* stream);
-int ds6g_f16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate,
-                        void* ws, size_t ws_bytes, void* stream);
-int ds6g_f16_bn_stats(const void* x, long M, int C, float eps, float momentum, float* mean, float* invstd,
-                      float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
-int ds6g_f16_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                      const void* residual, void* y, long M, int C, int relu, void* stream);
-int ds6g_f16_bn_bwd(const void* dy, const void* y_mask, const void* x, const float* mean, const float* invstd,
-                    const float* gamma, const float* relu_beta, void* dx, float* dgamma, float* dbeta, void* dres,
-                    long M, int C, int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream);
-int ds6g_bn_bwd_maxpool_f16in(const void* dpool, const uint8_t* idx, const float* x, const float* mean,
-                              const float* invstd, const float* gamma, const float* relu_beta, float* dx, float* dgamma,
-                              float* dbeta, int N, int H, int W, int C, int accumulate_param_grads, void* ws,
-                              size_t ws_bytes, void* stream);
-int ds6g_f16_stem_bn_bwd_maxpool(const void* dpool, const uint8_t* idx, const void* x, const float* mean,
-                                 const float* invstd, const float* gamma, const float* relu_beta, void* dx,
-                                 float* dgamma, float* dbeta, int N, int H, int W, int C, int accumulate_param_grads,
-                                 void* ws, size_t ws_bytes, void* stream);
-int ds6g_layernorm_fwd_f16out(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                              int M, int C, float eps, void* stream);
-int ds6g_layernorm_bwd_f16(const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
-                           const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
-                           int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off,
-                           void* ws, size_t ws_bytes, void* stream);
-int ds6g_pack_input_f16(const float* src, void* dst, int B, int Cs, int H, int W, int frames_per_sample, int t,
-                        int normalize_imagenet, void* stream);
-int ds6g_bn_relu_maxpool3x3s2_fwd_f16out(const float* x, const float* mean, const float* invstd, const float* gamma,
-                                         const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C,
-                                         void* stream);
-int ds6g_f16_stem_bn_relu_maxpool_fwd(const void* x, const float* mean, const float* invstd, const float* gamma,
-                                      const float* beta, void* y, uint8_t* idx, int N, int H, int W, int C,
-                                      void* stream);
-int ds6g_f16_avgpool_tokens_fwd(const void* feat, const float* pos_emb, float* tokens, int N, int H, int C,
-                                int frames_per_sample, int mod_off, int T, float drop_p, uint64_t seed,
-                                uint64_t seed_off, void* stream);
-int ds6g_f16_avgpool_tokens_bwd(const float* dtok, const void* dfeat_in, void* dfeat, int N, int H, int C,
-                                int frames_per_sample, int mod_off, int T, void* stream);
-int ds6g_f16_upsample_add_fwd(const void* feat, const float* tokens, void* out, int N, int H, int C,
-                              int frames_per_sample, int mod_off, int T, void* stream);
-int ds6g_f16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
-                              int T, void* stream);
-int ds6g_f16_global_pool(const void* feat, float* pooled, int N, int C, void* stream);
-int ds6g_f16_head_bwd(const float* dfused, void* dfeat, int N, int C, int frames_per_sample, void* stream);
-int ds6g_attention_fwd_f16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int nh,
-                           int hd, int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
-                           size_t ws_bytes, void* stream);
-int ds6g_attention_bwd_f16io(const void* q, const void* k, const void* v, const void* o, const void* d_o,
-                             const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int T, int nh, int hd,
-                             int ld_qkv, int ld, int ld_dqkv, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
-                             size_t ws_bytes, void* stream);
-int ds6g_cast_f32_f16(const float* src, void* dst, long n, void* stream);
+int ds6g_cast_f32_h16(int st16, const float* src, void* dst, long n, void* stream);
 /* vel_emb1..4 and the join MLP: model2_seq.py:422-425,518,536,555,574,863-869 */
 int ds6g_small_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K,
                           int rows_per_group, long group_stride, int relu, void* stream);

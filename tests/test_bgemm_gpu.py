@@ -144,8 +144,8 @@ def test_bf16_conv_fwd_dgrad_wgrad(dev, case):
 @pytest.mark.parametrize("case", [CONV[0], CONV[1], CONV[2], CONV[4], CONV[5], CONV[7], (60, 16, 16, 256, 256, 3, 1, 1)],
                          ids=lambda c: "x".join(map(str, c)))
 def test_bf16_conv_with_fused_batchnorm_statistics(dev, case):
-    """ds6g_bf16_conv2d_fwd_bnstats: the conv output is bit-identical to ds6g_bf16_conv2d_fwd's, and mean / invstd / the
-    running statistics equal what ds6g_bf16_bn_stats computes from the stored bf16 tensor (same quantity, different
+    """ds6g_h16_conv2d_fwd_bnstats: the conv output is bit-identical to ds6g_h16_conv2d_fwd's, and mean / invstd / the
+    running statistics equal what ds6g_h16_bn_stats computes from the stored bf16 tensor (same quantity, different
     summation order: 1e-6) and torch's batch_norm statistics of that tensor in fp64 (1e-5)."""
     from deepsense6g_tii_amd import ops
     N, H, W, C, K, R, st, pad = case
@@ -346,30 +346,30 @@ def test_bf16_stem_pool_layernorm_attention_and_spatial_variants(dev):
     feat = r16(torch.randn(Nf, Hf, Hf, Cf, generator=g)).cuda()
     pos = torch.randn(T2, Cf, generator=g).cuda()
     tok16, tok32 = torch.zeros(2, T2, Cf, device=dev), torch.zeros(2, T2, Cf, device=dev)
-    L.bf16_avgpool_tokens_fwd(feat.data_ptr(), pos.data_ptr(), tok16.data_ptr(), Nf, Hf, Cf, fps, 320, T2, 0.1, 7, 0, st)
+    L.h16_avgpool_tokens_fwd(1, feat.data_ptr(), pos.data_ptr(), tok16.data_ptr(), Nf, Hf, Cf, fps, 320, T2, 0.1, 7, 0, st)
     L.avgpool_tokens_fwd(feat.float().data_ptr(), pos.data_ptr(), tok32.data_ptr(), Nf, Hf, Cf, fps, 320, T2, 0.1, 7, 0, st)
     assert same32(tok16, tok32)
     xo = torch.randn(2 * T2, Cf, generator=g).cuda()
     o16_, o32_ = torch.empty_like(feat), torch.empty(feat.shape, device=dev)
-    L.bf16_upsample_add_fwd(feat.data_ptr(), xo.data_ptr(), o16_.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
+    L.h16_upsample_add_fwd(1, feat.data_ptr(), xo.data_ptr(), o16_.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
     L.upsample_add_fwd(feat.float().data_ptr(), xo.data_ptr(), o32_.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
     one_rounding(o16_, o32_)
     dtok16, dtok32 = torch.zeros(2 * T2, Cf, device=dev), torch.zeros(2 * T2, Cf, device=dev)
-    L.bf16_upsample_add_bwd(feat.data_ptr(), dtok16.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
+    L.h16_upsample_add_bwd(1, feat.data_ptr(), dtok16.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
     L.upsample_add_bwd(feat.float().data_ptr(), dtok32.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
     assert same32(dtok16, dtok32)
     d16, d32 = torch.empty_like(feat), torch.empty(feat.shape, device=dev)
-    L.bf16_avgpool_tokens_bwd(xo.data_ptr(), feat.data_ptr(), d16.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
+    L.h16_avgpool_tokens_bwd(1, xo.data_ptr(), feat.data_ptr(), d16.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
     L.avgpool_tokens_bwd(xo.data_ptr(), feat.float().data_ptr(), d32.data_ptr(), Nf, Hf, Cf, fps, 320, T2, st)
     one_rounding(d16, d32)
     f8 = r16(torch.randn(Nf, 8, 8, 512, generator=g)).cuda()
     pl16, pl32 = torch.empty(Nf, 512, device=dev), torch.empty(Nf, 512, device=dev)
-    L.bf16_global_pool(f8.data_ptr(), pl16.data_ptr(), Nf, 512, st)
+    L.h16_global_pool(1, f8.data_ptr(), pl16.data_ptr(), Nf, 512, st)
     L.global_pool(f8.float().data_ptr(), pl32.data_ptr(), Nf, 512, st)
     assert same32(pl16, pl32)
     dfu = torch.randn(2, 512, generator=g).cuda()
     h16, h32 = torch.empty_like(f8), torch.empty(f8.shape, device=dev)
-    L.bf16_head_bwd(dfu.data_ptr(), h16.data_ptr(), Nf, 512, fps, st)
+    L.h16_head_bwd(1, dfu.data_ptr(), h16.data_ptr(), Nf, 512, fps, st)
     L.head_bwd(dfu.data_ptr(), h32.data_ptr(), Nf, 512, fps, st)
     one_rounding(h16, h32)
     torch.cuda.synchronize()

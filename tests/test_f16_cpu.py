@@ -1,5 +1,5 @@
 """CPU: the f16-storage mode at the C-ABI boundary (host state only, no launch): "f16" is compute mode 5, 4 stays
-refused, and every bf16-storage entry point has an f16 twin with the same signature."""
+refused, and every 16-bit-storage entry point names its storage type (bf16 / f16) by its first argument."""
 import pytest
 
 from deepsense6g_tii_amd import _lib
@@ -23,14 +23,30 @@ def test_f16_mode_round_trips_and_4_stays_refused():
     assert L.get_compute_mode() == 0
 
 
-def test_f16_twins_mirror_the_bf16_storage_entry_points():
+BF16_ONLY = ("ds6g_attention_fwd_bf16out", "ds6g_attention_bwd_bf16")   # fp32 operands in, bf16 out: no f16 form
+SIZE_QUERIES = ("ds6g_h16_conv_bnstats_workspace_bytes", "ds6g_h16_stem_workspace_bytes")   # the same for either storage
+
+
+def test_16bit_storage_entry_points_take_a_storage_code():
+    """one entry point per 16-bit-storage kernel: `h16` in its name, the storage code (1 bf16, 2 f16) as its first argument,
+    and every other code refused on the host before anything is launched"""
+    import ctypes
     protos = _lib.parse_header()
-    bf16 = [n for n in protos if "bf16" in n and n not in ("ds6g_attention_fwd_bf16out", "ds6g_attention_bwd_bf16")]
-    assert len(bf16) >= 29
-    for name in bf16:
-        twin = name.replace("bf16", "f16")
-        assert twin in protos, twin
-        assert protos[twin] == protos[name], twin
+    assert not [n for n in protos if "f16" in n.replace("bf16", "")]
+    assert sorted(n for n in protos if "bf16" in n) == sorted(BF16_ONLY)
+    h16 = [n for n in protos if "h16" in n]
+    assert len(h16) >= 33
+    assert all(q in h16 for q in SIZE_QUERIES)
+    L = _lib.lib()
+    for name in h16:
+        if name in SIZE_QUERIES:
+            continue
+        argtypes = protos[name][1]
+        assert argtypes[0] is ctypes.c_int, name
+        zeros = [0.0 if t is ctypes.c_float else 0 for t in argtypes[1:]]
+        for st16 in (0, 3, -1):
+            with pytest.raises(_lib.Ds6gError):
+                getattr(L, name[len("ds6g_"):])(st16, *zeros)
 
 
 def test_f16_winograd_gating_follows_f32():
