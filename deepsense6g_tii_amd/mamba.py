@@ -29,60 +29,80 @@ F32 = torch.float32
 _MIN_WS = 64 << 20   # room for the split-K slabs of the projection weight gradients
 
 
+def layer_forward(mod, ws, reverse, save, u2, Bsz, L, params):
+    """the layer on token rows u2 [B*L, d_model] (contiguous) -> (out [B*L, d_model], tape or None).  `params`: the nine
+    parameters in Mamba._params() order; `ws`: a Workspace of at least mod.workspace_bytes(B, L).  Shared by _MambaFn and by
+    the block-level Function of mamba_fusion.py, which runs two layers inside one autograd node."""
+    w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
+    M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
+    xz = ops.linear_fwd(u2, w_in.data_ptr(), 0, 2 * D)
+    z = xz[:, D:]
+    xc = ops.causal_conv1d_silu_fwd(xz[:, :D], conv_w, conv_b, Bsz, L, reverse)
+    x_dbl = ops.linear_fwd(xc, w_x.data_ptr(), 0, r + 32)
+    dt = ops.copy_cols(x_dbl[:, :r], torch.empty((M, r), dtype=F32, device=u2.device))
+    draw = ops.linear_fwd(dt, w_dt.data_ptr(), 0, D)       # dt_proj.bias is added inside the scan
+    y, saved = ops.selective_scan_fwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, z, Bsz, L, ws,
+                                      reverse, save)
+    out = ops.linear_fwd(y, w_out.data_ptr(), 0, dm)
+    return out, ((u2, xz, xc, x_dbl, dt, draw, y, saved) if save else None)
+
+
+def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None):
+    """-> (du [B*L, d_model], the nine parameter gradients in Mamba._params() order).  du_out: an existing gradient of the
+    layer's input that du is ADDED to (the in_proj data-gradient GEMM accumulates into it)"""
+    u2, xz, xc, x_dbl, dt, draw, y, saved = tape
+    w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
+    M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
+    dev = dout2.device
+
+    def empty(*shape):
+        return torch.empty(shape, dtype=F32, device=dev)
+
+    g_out = empty(dm, D)
+    ops.linear_wgrad(y, dout2, g_out.data_ptr(), ws)
+    dy = ops.linear_dgrad(dout2, w_out.data_ptr(), D)
+    dxz, dxdbl, dxc, ddraw = empty(M, 2 * D), empty(M, r + 32), empty(M, D), empty(M, D)
+    g_A, g_D = ops.selective_scan_bwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, xz[:, D:], dy, saved,
+                                      dxc, ddraw, dxdbl[:, r:r + 16], dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse)
+    g_dtw, g_dtb = empty(D, r), empty(D)
+    ops.linear_wgrad(dt, ddraw, g_dtw.data_ptr(), ws, dbias_ptr=g_dtb.data_ptr())
+    ops.copy_cols(ops.linear_dgrad(ddraw, w_dt.data_ptr(), r), dxdbl[:, :r])
+    g_x = empty(r + 32, D)
+    ops.linear_wgrad(xc, dxdbl, g_x.data_ptr(), ws)
+    ops.linear_dgrad(dxdbl, w_x.data_ptr(), D, out=dxc, accumulate=True)
+    g_cw, g_cb = ops.causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc, dxz[:, :D], Bsz, L, ws, reverse)
+    g_in = empty(2 * D, dm)
+    ops.linear_wgrad(u2, dxz, g_in.data_ptr(), ws)
+    if du_out is None:
+        du = ops.linear_dgrad(dxz, w_in.data_ptr(), dm)
+    else:
+        du = ops.linear_dgrad(dxz, w_in.data_ptr(), dm, out=du_out, accumulate=True)
+    return du, (g_in, g_cw, g_cb, g_x, g_dtw, g_dtb, g_A, g_D, g_out)
+
+
 class _MambaFn(torch.autograd.Function):
     """forward + backward of the whole layer; inputs after `reverse` are the nine parameters in _PARAMS order"""
 
     @staticmethod
-    def forward(ctx, mod, reverse, save, u, w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out):
+    def forward(ctx, mod, reverse, save, u, *params):
         Bsz, L, dm = u.shape
-        M, D, r = Bsz * L, mod.d_inner, mod.dt_rank
         ws = mod._workspace(u.device, Bsz, L)
-        u2 = u.detach().reshape(M, dm).contiguous()
-        xz = ops.linear_fwd(u2, w_in.data_ptr(), 0, 2 * D)
-        z = xz[:, D:]
-        xc = ops.causal_conv1d_silu_fwd(xz[:, :D], conv_w, conv_b, Bsz, L, reverse)
-        x_dbl = ops.linear_fwd(xc, w_x.data_ptr(), 0, r + 32)
-        dt = ops.copy_cols(x_dbl[:, :r], torch.empty((M, r), dtype=F32, device=u.device))
-        draw = ops.linear_fwd(dt, w_dt.data_ptr(), 0, D)       # dt_proj.bias is added inside the scan
-        y, saved = ops.selective_scan_fwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, z, Bsz, L, ws,
-                                          reverse, save)
-        out = ops.linear_fwd(y, w_out.data_ptr(), 0, dm)
+        u2 = u.detach().reshape(Bsz * L, dm).contiguous()
+        out, tape = layer_forward(mod, ws, reverse, save, u2, Bsz, L, params)
         if save:
             ctx.mod, ctx.reverse, ctx.dims = mod, reverse, (Bsz, L, dm)
-            ctx.save_for_backward(u2, xz, xc, x_dbl, dt, draw, y, saved, w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp,
-                                  w_out)
+            ctx.save_for_backward(*tape, *params)
         return out.view(Bsz, L, dm)
 
     @staticmethod
     def backward(ctx, dout):
-        (u2, xz, xc, x_dbl, dt, draw, y, saved, w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out) = ctx.saved_tensors
+        tape, params = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
         mod, reverse = ctx.mod, ctx.reverse
         Bsz, L, dm = ctx.dims
-        M, D, r = Bsz * L, mod.d_inner, mod.dt_rank
-        dev = dout.device
-        ws = mod._workspace(dev, Bsz, L)
-        dout2 = dout.reshape(M, dm).contiguous()
-
-        def empty(*shape):
-            return torch.empty(shape, dtype=F32, device=dev)
-
-        g_out = empty(dm, D)
-        ops.linear_wgrad(y, dout2, g_out.data_ptr(), ws)
-        dy = ops.linear_dgrad(dout2, w_out.data_ptr(), D)
-        dxz, dxdbl, dxc, ddraw = empty(M, 2 * D), empty(M, r + 32), empty(M, D), empty(M, D)
-        g_A, g_D = ops.selective_scan_bwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, xz[:, D:], dy, saved,
-                                          dxc, ddraw, dxdbl[:, r:r + 16], dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse)
-        g_dtw, g_dtb = empty(D, r), empty(D)
-        ops.linear_wgrad(dt, ddraw, g_dtw.data_ptr(), ws, dbias_ptr=g_dtb.data_ptr())
-        ops.copy_cols(ops.linear_dgrad(ddraw, w_dt.data_ptr(), r), dxdbl[:, :r])
-        g_x = empty(r + 32, D)
-        ops.linear_wgrad(xc, dxdbl, g_x.data_ptr(), ws)
-        ops.linear_dgrad(dxdbl, w_x.data_ptr(), D, out=dxc, accumulate=True)
-        g_cw, g_cb = ops.causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc, dxz[:, :D], Bsz, L, ws, reverse)
-        g_in = empty(2 * D, dm)
-        ops.linear_wgrad(u2, dxz, g_in.data_ptr(), ws)
-        du = ops.linear_dgrad(dxz, w_in.data_ptr(), dm).view(Bsz, L, dm)
-        return None, None, None, du, g_in, g_cw, g_cb, g_x, g_dtw, g_dtb, g_A, g_D, g_out
+        ws = mod._workspace(dout.device, Bsz, L)
+        dout2 = dout.reshape(Bsz * L, dm).contiguous()
+        du, grads = layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2)
+        return (None, None, None, du.view(Bsz, L, dm), *grads)
 
 
 class Mamba(nn.Module):
@@ -137,11 +157,14 @@ class Mamba(nn.Module):
         self.out_proj = nn.Linear(d_inner, d_model, bias=False, **kw)
         self._ws = {}   # raw stream handle -> ops.Workspace (per instance; stream order makes the reuse safe)
 
-    def _workspace(self, device, B, L):
+    def workspace_bytes(self, B, L):
         from ._lib import lib
         D = self.d_inner
-        need = max(int(lib().selective_scan_workspace_bytes(B, L, D)), int(lib().causal_conv1d_workspace_bytes(B, L, D)),
+        return max(int(lib().selective_scan_workspace_bytes(B, L, D)), int(lib().causal_conv1d_workspace_bytes(B, L, D)),
                    _MIN_WS)
+
+    def _workspace(self, device, B, L):
+        need = self.workspace_bytes(B, L)
         key = (device.index, ops._stream())
         ws = self._ws.get(key)
         if ws is None or ws.nbytes < need:

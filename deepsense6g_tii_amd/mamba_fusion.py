@@ -1,0 +1,281 @@
+"""The bi-branch Mamba fusion stage of the reference (mambafuser_seq.py:74-231) on the gfx950 kernels: MambaBlock and
+MambaFusion, drop-in fp32 nn.Modules whose state dicts are interchangeable with the reference's.
+
+    MambaBlock      x1  = fc1(ln1(x))                    ln1 = LayerNorm((T, C)): one mean / variance per SAMPLE
+                    fm  = forward_mamba(x1)
+                    xf  = flip(x1, 1);  bm = backward_mamba(xf)
+                    out = bm * LeakyReLU_0.2(fc2(xf)) + fm * bm
+    There is no residual, and bm and fc2(xf) are never flipped back: token t of the output pairs fm[t] with the reversed
+    branch at L-1-t.  Here bmN = backward_mamba(x1, reverse=True) and f2N = fc2(x1) stay in natural order and the gate kernel
+    reads them back to front (out[b, t] = bmN[b, L-1-t] * (leaky(f2N[b, L-1-t]) + fm[b, t])): no flip copy, forward or backward.
+
+    MambaFusion     tokens = drop(pos_emb + cat(channel-swapped image / lidar / radar tokens, gps))
+                    tokens = ln_f(mambablocks(tokens));  unpack to the three NCHW maps and the two gps rows
+    Token rows are modality-major (image, lidar, radar; then frame, h, w), the gps rows last.  Token channel c of modality m
+    comes from modality (m + seg(c)) % 3, seg = 0 / 1 / 2 for c < C//3, c < C//3*2, the rest.
+
+One block is ONE autograd node: the three gradients that reach x1 (forward Mamba, reverse Mamba, fc2) are summed by the
+data-gradient GEMMs accumulating into one buffer, not by autograd.  The LayerNorm, gate, pack and unpack are
+csrc/mamba_fusion.hip, the two Mamba layers csrc/mamba.hip (mamba.layer_forward / layer_backward), fc1 / fc2 the fp32
+implicit-GEMM linears, ln_f the row LayerNorm kernel.
+
+Initialisation follows the reference's self.apply(_init_weights) to the letter: EVERY nn.Linear under the stage is redrawn
+N(0, 0.02) with a zero bias - also the four inside each Mamba, so dt_proj.bias ends up 0 and dt_proj.weight loses its
+dt_rank**-0.5 scale - LayerNorm is (1, 0) and pos_emb zeros; A_log, D and conv1d keep the Mamba layer's own initialisation.
+That is not what mamba_ssm intends for dt_proj (its _no_reinit mark is not honoured by the reference's hook), and it is what
+the reference trains.
+
+Supported: fp32, HIP device only, n_embd in {64, 128, 256, 512}, d_state 16, d_conv 4, 8 x 8 anchors, config.n_views == 1 (the
+reference's cat of the three modalities only lines up then), ln_size == (T, n_embd).  Train and eval; dropout is off in eval;
+no tape is kept when no gradient is needed.  Not covered: 16-bit storage, the frozen inference engine, TimeMamba,
+EncoderWithMamba / MambaFuser, missing-modality options.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from .mamba import Mamba, layer_forward, layer_backward
+
+F32 = torch.float32
+
+
+def _check_params(name, params, device):
+    for p in params:
+        if p.device != device:
+            raise RuntimeError(f"{name}: parameters and input must be on the same HIP device")
+        if p.dtype != F32 or not p.is_contiguous():
+            raise ValueError(f"{name}: parameters must be contiguous fp32 tensors")
+
+
+def _empty(dev, *shape):
+    return torch.empty(shape, dtype=F32, device=dev)
+
+
+class _BlockFn(torch.autograd.Function):
+    """the whole MambaBlock; inputs after x: ln1.weight, ln1.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, the nine
+    parameters of forward_mamba, the nine of backward_mamba"""
+
+    @staticmethod
+    def forward(ctx, blk, save, x, ln_w, ln_b, w1, b1, w2, b2, *mp):
+        B, T, C = x.shape
+        M = B * T
+        ws = blk._workspace(x.device, B, T)
+        x2 = x.detach().reshape(B, T * C).contiguous()
+        xl, mean, rstd = ops.sample_layernorm_fwd(x2, ln_w, ln_b, ws)
+        x1 = ops.linear_fwd(xl.view(M, C), w1.data_ptr(), b1.data_ptr(), C)
+        fm, tape_f = layer_forward(blk.forward_mamba, ws, False, save, x1, B, T, mp[:9])
+        bm, tape_b = layer_forward(blk.backward_mamba, ws, True, save, x1, B, T, mp[9:])
+        f2 = ops.linear_fwd(x1, w2.data_ptr(), b2.data_ptr(), C)
+        out = ops.bimamba_gate_fwd(fm, bm, f2, B, T)
+        if save:
+            ctx.blk, ctx.dims = blk, (B, T, C)
+            ctx.save_for_backward(x2, mean, rstd, xl, fm, bm, f2, ln_w, w1, w2, *tape_f, *tape_b, *mp)
+        return out.view(B, T, C)
+
+    @staticmethod
+    def backward(ctx, dout):
+        st = ctx.saved_tensors
+        x2, mean, rstd, xl, fm, bm, f2, ln_w, w1, w2 = st[:10]
+        tape_f, tape_b, mp = st[10:18], st[18:26], st[26:]
+        blk = ctx.blk
+        B, T, C = ctx.dims
+        M, dev = B * T, dout.device
+        ws = blk._workspace(dev, B, T)
+        x1 = tape_f[0]
+        dfm, dbm, df2 = ops.bimamba_gate_bwd(dout.reshape(M, C).contiguous(), fm, bm, f2, B, T)
+        g_w2, g_b2 = _empty(dev, C, C), _empty(dev, C)
+        ops.linear_wgrad(x1, df2, g_w2.data_ptr(), ws, dbias_ptr=g_b2.data_ptr())
+        dx1 = ops.linear_dgrad(df2, w2.data_ptr(), C)           # the two Mamba layers add their input gradients to it
+        _, g_f = layer_backward(blk.forward_mamba, ws, False, B, T, tape_f, mp[:9], dfm, du_out=dx1)
+        _, g_b = layer_backward(blk.backward_mamba, ws, True, B, T, tape_b, mp[9:], dbm, du_out=dx1)
+        g_w1, g_b1 = _empty(dev, C, C), _empty(dev, C)
+        ops.linear_wgrad(xl.view(M, C), dx1, g_w1.data_ptr(), ws, dbias_ptr=g_b1.data_ptr())
+        dxl = ops.linear_dgrad(dx1, w1.data_ptr(), C)
+        g_lw, g_lb = _empty(dev, T, C), _empty(dev, T, C)
+        dx = ops.sample_layernorm_bwd(dxl.view(B, T * C), x2, mean, rstd, ln_w, g_lw, g_lb, ws)
+        return (None, None, dx.view(B, T, C), g_lw, g_lb, g_w1, g_b1, g_w2, g_b2, *g_f, *g_b)
+
+
+class MambaBlock(nn.Module):
+    """a bi-branch Mamba block: the reference's constructor arguments, parameter names and shapes"""
+
+    def __init__(self, n_embd, ln_size, d_state, d_conv, expand, device=None):
+        super().__init__()
+        ln_size = tuple(int(v) for v in ln_size)
+        if len(ln_size) != 2 or ln_size[1] != n_embd or ln_size[0] < 1:
+            raise ValueError(f"MambaBlock: ln_size must be (T, {n_embd}), got {ln_size}")
+        kw = dict(device=device, dtype=F32)
+        self.n_embd, self.ln_size = n_embd, ln_size
+        self.ln1 = nn.LayerNorm(ln_size, **kw)       # parameter holders: the arithmetic is the HIP kernels'
+        self.fc1 = nn.Linear(n_embd, n_embd, **kw)
+        self.fc2 = nn.Linear(n_embd, n_embd, **kw)
+        self.forward_mamba = Mamba(d_model=n_embd, d_state=d_state, d_conv=d_conv, expand=expand, device=device)
+        self.backward_mamba = Mamba(d_model=n_embd, d_state=d_state, d_conv=d_conv, expand=expand, device=device)
+        self._ws = {}
+
+    def _workspace(self, device, B, T):
+        need = max(self.forward_mamba.workspace_bytes(B, T), ops.sample_layernorm_workspace_bytes(B, T * self.n_embd))
+        key = (device.index, ops._stream())
+        ws = self._ws.get(key)
+        if ws is None or ws.nbytes < need:
+            self._ws[key] = ws = ops.Workspace(device, need)
+        return ws
+
+    def _params(self):
+        return (self.ln1.weight, self.ln1.bias, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
+                *self.forward_mamba._params(), *self.backward_mamba._params())
+
+    def _check(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("deepsense6g_tii_amd.MambaBlock runs on MI355X HIP kernels only (no CPU path)")
+        if x.dim() != 3 or tuple(x.shape[1:]) != self.ln_size or x.dtype != F32 or x.shape[0] < 1:
+            raise ValueError(f"MambaBlock: expected a (B, {self.ln_size[0]}, {self.ln_size[1]}) fp32 tensor, got "
+                             f"{tuple(x.shape)} {x.dtype}")
+        params = self._params()
+        _check_params("MambaBlock", params, x.device)
+        return params
+
+    def forward(self, x):
+        """x: (B, T, n_embd) fp32 on the HIP device, (T, n_embd) == ln_size -> (B, T, n_embd)"""
+        params = self._check(x)
+        save = torch.is_grad_enabled() and self.training and (x.requires_grad or any(p.requires_grad for p in params))
+        with torch.cuda.device(x.device):
+            if save:
+                return _BlockFn.apply(self, True, x, *params)
+            with torch.no_grad():
+                return _BlockFn.apply(self, False, x, *params)
+
+
+class _PackFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, B, S, drop, image, lidar, radar, gps, pos_emb):
+        ctx.args = (B, S, drop)
+        return ops.swap_pack_fwd(image.detach().contiguous(), lidar.detach().contiguous(), radar.detach().contiguous(),
+                                 gps.detach().contiguous(), pos_emb, B, S, *drop)
+
+    @staticmethod
+    def backward(ctx, dtok):
+        B, S, drop = ctx.args
+        di, dl, dr, dg, dpos = ops.swap_pack_bwd(dtok.contiguous(), B, S, *drop)
+        return None, None, None, di, dl, dr, dg, dpos.unsqueeze(0)
+
+
+class _LnFFn(torch.autograd.Function):
+    """ln_f = LayerNorm(C) over token rows, on the row kernel"""
+
+    @staticmethod
+    def forward(ctx, mod, save, x, w, b):
+        B, T, C = x.shape
+        x2 = x.detach().reshape(B * T, C).contiguous()
+        y, mean, rstd = ops.layernorm_fwd(x2, w.data_ptr(), b.data_ptr())
+        if save:
+            ctx.mod, ctx.dims = mod, (B, T, C)
+            ctx.save_for_backward(x2, mean, rstd, w)
+        return y.view(B, T, C)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, mean, rstd, w = ctx.saved_tensors
+        B, T, C = ctx.dims
+        ws = ctx.mod.mambablocks[0]._workspace(dy.device, B, T)
+        g_w, g_b = _empty(dy.device, C), _empty(dy.device, C)
+        dx = ops.layernorm_bwd(dy.reshape(B * T, C).contiguous(), x2, mean, rstd, w.data_ptr(), g_w.data_ptr(), g_b.data_ptr(),
+                               ws)
+        return None, None, dx.view(B, T, C), g_w, g_b
+
+
+class _UnpackFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, B, S, tokens):
+        ctx.args = (B, S)
+        return ops.token_unpack_fwd(tokens.detach().contiguous(), B, S)
+
+    @staticmethod
+    def backward(ctx, di, dl, dr, dg):
+        B, S = ctx.args
+        return None, None, ops.token_unpack_bwd(di.contiguous(), dl.contiguous(), dr.contiguous(), dg.contiguous(), B, S)
+
+
+class MambaFusion(nn.Module):
+    """the reference's MambaFusion: constructor arguments, forward signature, state-dict names and initialisation"""
+
+    def __init__(self, n_embd, ln_size, d_state, d_conv, expand, n_layer, vert_anchors, horz_anchors, seq_len, embd_pdrop,
+                 config, device=None):
+        super().__init__()
+        if getattr(config, "n_views", 1) != 1:
+            raise ValueError(f"MambaFusion: config.n_views must be 1 (the reference's token cat only lines up then), got "
+                             f"{config.n_views}")
+        if vert_anchors != 8 or horz_anchors != 8:
+            raise ValueError(f"MambaFusion: 8 x 8 anchors only, got {vert_anchors} x {horz_anchors}")
+        if n_embd not in (64, 128, 256, 512):
+            raise ValueError(f"MambaFusion: n_embd must be 64, 128, 256 or 512, got {n_embd}")
+        if seq_len < 1 or n_layer < 1:
+            raise ValueError(f"MambaFusion: seq_len and n_layer must be positive, got {seq_len}, {n_layer}")
+        if not 0.0 <= float(embd_pdrop) < 1.0:
+            raise ValueError(f"MambaFusion: embd_pdrop must be in [0, 1), got {embd_pdrop}")
+        T = 3 * seq_len * 64 + 2
+        if tuple(int(v) for v in ln_size) != (T, n_embd):
+            raise ValueError(f"MambaFusion: ln_size must be ({T}, {n_embd}) for seq_len {seq_len}, got {tuple(ln_size)}")
+        self.n_embd, self.seq_len, self.vert_anchors, self.horz_anchors, self.config = n_embd, seq_len, 8, 8, config
+        self.embd_pdrop, self.n_tokens, self.block_size = float(embd_pdrop), T, seq_len
+        self.pos_emb = nn.Parameter(torch.zeros(1, T, n_embd, device=device, dtype=F32))
+        self.mambablocks = nn.Sequential(*[MambaBlock(n_embd, ln_size, d_state, d_conv, expand, device=device)
+                                           for _ in range(n_layer)])
+        self.ln_f = nn.LayerNorm(n_embd, device=device, dtype=F32)
+        self.apply(self._init_weights)
+        self._seed = int(torch.randint(0, 2 ** 31 - 1, ()).item())
+        self._seed_off = 0
+
+    def get_block_size(self):
+        return self.block_size
+
+    @staticmethod
+    def _init_weights(module):
+        if isinstance(module, nn.Linear):
+            module.weight.data.normal_(mean=0.0, std=0.02)
+            if module.bias is not None:
+                module.bias.data.zero_()
+        elif isinstance(module, nn.LayerNorm):
+            module.bias.data.zero_()
+            module.weight.data.fill_(1.0)
+
+    def set_dropout_seed(self, seed):
+        """embd_drop masks are a pure function of (seed, counter): restart the counter under this seed.  Without a call the
+        seed is one draw from torch's CPU generator at construction (so torch.manual_seed fixes it)"""
+        self._seed, self._seed_off = int(seed), 0
+
+    def forward(self, image_tensor, lidar_tensor, radar_tensor, gps):
+        """image / lidar / radar: (B * seq_len, n_embd, 8, 8), gps: (B, 2, n_embd), fp32 on the HIP device ->
+        (image_out, lidar_out, radar_out) of the input shapes and the two gps token rows (B, 2, n_embd)"""
+        S, C, T = self.seq_len, self.n_embd, self.n_tokens
+        ins = (image_tensor, lidar_tensor, radar_tensor, gps)
+        for t in ins:
+            if not t.is_cuda:
+                raise RuntimeError("deepsense6g_tii_amd.MambaFusion runs on MI355X HIP kernels only (no CPU path)")
+        dev = lidar_tensor.device
+        B = lidar_tensor.shape[0] // S
+        for t in ins[:3]:
+            if tuple(t.shape) != (B * S, C, 8, 8) or t.dtype != F32 or t.device != dev or B < 1:
+                raise ValueError(f"MambaFusion: expected three (B * {S}, {C}, 8, 8) fp32 maps, got {tuple(t.shape)} {t.dtype}")
+        if tuple(gps.shape) != (B, 2, C) or gps.dtype != F32 or gps.device != dev:
+            raise ValueError(f"MambaFusion: expected gps of shape ({B}, 2, {C}) fp32, got {tuple(gps.shape)} {gps.dtype}")
+        params = (self.pos_emb, self.ln_f.weight, self.ln_f.bias)
+        _check_params("MambaFusion", params, dev)
+        bparams = [blk._params() for blk in self.mambablocks]
+        for bp in bparams:
+            _check_params("MambaFusion", bp, dev)
+        needs = any(t.requires_grad for t in ins) or any(p.requires_grad for p in params) or \
+            any(p.requires_grad for bp in bparams for p in bp)
+        save = torch.is_grad_enabled() and self.training and needs
+        p = self.embd_pdrop if self.training else 0.0
+        drop = (p, self._seed, self._seed_off)
+        if p > 0.0:
+            self._seed_off += B * T * C          # the next training forward draws from the next counter range
+        with torch.cuda.device(dev), torch.set_grad_enabled(save):
+            x = _PackFn.apply(B, S, drop, image_tensor, lidar_tensor, radar_tensor, gps, self.pos_emb)
+            for blk, bp in zip(self.mambablocks, bparams):
+                x = _BlockFn.apply(blk, save, x, *bp)
+            x = _LnFFn.apply(self, save, x, self.ln_f.weight, self.ln_f.bias)
+            return _UnpackFn.apply(B, S, x)

@@ -930,3 +930,113 @@ def selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, d
                              _rows_al(dCm, M, 16), _p(dz), _rows_al(dz, M, D), _p(dA), _p(dD), B, L, D, int(reverse),
                              ws.ptr, ws.nbytes, _stream())
     return dA, dD
+
+
+# ------------------------------------------------------------------------------------------------
+# Mamba fusion stage (csrc/mamba_fusion.hip)
+def sample_layernorm_workspace_bytes(B, n):
+    return int(lib().sample_layernorm_workspace_bytes(B, n))
+
+
+def sample_layernorm_fwd(x, gamma, beta, ws: Workspace, eps=1e-5):
+    """LayerNorm over ALL n values of each sample: x [B, n], gamma / beta n elements -> (y, mean [B], rstd [B])"""
+    B, n = x.shape
+    _chk(x)
+    assert n % 4 == 0 and ws.nbytes >= sample_layernorm_workspace_bytes(B, n), (B, n, ws.nbytes)
+    y = torch.empty_like(x)
+    mean = torch.empty(B, dtype=F32, device=x.device)
+    rstd = torch.empty(B, dtype=F32, device=x.device)
+    lib().sample_layernorm_fwd(_p(x), _vec(gamma, n), _vec(beta, n), _p(y), _p(mean), _p(rstd), B, n, eps, ws.ptr, ws.nbytes,
+                               _stream())
+    return y, mean, rstd
+
+
+def sample_layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, ws: Workspace, accumulate=False):
+    """-> dx [B, n]; dgamma / dbeta (n elements each, the caller's tensors) are written, or added to when accumulate"""
+    B, n = x.shape
+    _chk(x)
+    _chk(dy, B, n)
+    _chk(mean, B)
+    _chk(rstd, B)
+    assert n % 4 == 0 and ws.nbytes >= sample_layernorm_workspace_bytes(B, n), (B, n, ws.nbytes)
+    dx = torch.empty_like(x)
+    lib().sample_layernorm_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _vec(gamma, n), _p(dx), _vec(dgamma, n), _vec(dbeta, n), B, n,
+                               int(accumulate), ws.ptr, ws.nbytes, _stream())
+    return dx
+
+
+def bimamba_gate_fwd(fm, bm, f2, B, L, out=None):
+    """out[b, t] = bm[b, L-1-t] * (leaky_relu_0.2(f2[b, L-1-t]) + fm[b, t]); operands [B*L, C], column blocks allowed"""
+    M, C = fm.shape
+    assert M == B * L and C % 4 == 0
+    o = out if out is not None else torch.empty((M, C), dtype=F32, device=fm.device)
+    lib().bimamba_gate_fwd(_p(fm), _rows_al(fm, M, C), _p(bm), _rows_al(bm, M, C), _p(f2), _rows_al(f2, M, C), _p(o),
+                           _rows_al(o, M, C), B, L, C, _stream())
+    return o
+
+
+def bimamba_gate_bwd(dout, fm, bm, f2, B, L, out=None):
+    """-> (dfm, dbm, df2), each in its producer's token order; `out`: three [B*L, C] destinations (column blocks allowed)"""
+    M, C = fm.shape
+    assert M == B * L and C % 4 == 0
+    if out is None:
+        out = tuple(torch.empty((M, C), dtype=F32, device=fm.device) for _ in range(3))
+    dfm, dbm, df2 = out
+    lib().bimamba_gate_bwd(_p(dout), _rows_al(dout, M, C), _p(fm), _rows_al(fm, M, C), _p(bm), _rows_al(bm, M, C), _p(f2),
+                           _rows_al(f2, M, C), _p(dfm), _rows_al(dfm, M, C), _p(dbm), _rows_al(dbm, M, C), _p(df2),
+                           _rows_al(df2, M, C), B, L, C, _stream())
+    return dfm, dbm, df2
+
+
+def _chk_maps(maps, gps, B, S, C):
+    assert C % 64 == 0 and B >= 1 and S >= 1, (B, S, C)
+    for t in maps:
+        _chk(t, B * S, C, 8, 8)
+    _chk(gps, B, 2, C)
+
+
+def swap_pack_fwd(image, lidar, radar, gps, pos_emb, B, S, drop_p=0.0, seed=0, seed_off=0):
+    """three NCHW [B*S, C, 8, 8] maps + gps [B, 2, C] + pos_emb (T * C elements) -> tokens [B, T, C] = dropout(pos_emb +
+    channel-swapped tokens), T = 192 S + 2"""
+    C = image.shape[1]
+    _chk_maps((image, lidar, radar), gps, B, S, C)
+    T = 192 * S + 2
+    tokens = torch.empty((B, T, C), dtype=F32, device=image.device)
+    lib().swap_pack_fwd(_p(image), _p(lidar), _p(radar), _p(gps), _vec(pos_emb, T, C), _p(tokens), B, S, C, float(drop_p), seed,
+                        seed_off, _stream())
+    return tokens
+
+
+def swap_pack_bwd(dtokens, B, S, drop_p=0.0, seed=0, seed_off=0):
+    """-> (dimage, dlidar, dradar, dgps, dpos_emb (T, C)) of swap_pack_fwd from the token gradient [B, T, C]"""
+    T, C = dtokens.shape[1], dtokens.shape[2]
+    _chk(dtokens, B, 192 * S + 2, C)
+    assert C % 64 == 0
+    dev = dtokens.device
+    dmaps = tuple(torch.empty((B * S, C, 8, 8), dtype=F32, device=dev) for _ in range(3))
+    dgps = torch.empty((B, 2, C), dtype=F32, device=dev)
+    dpos = torch.empty((T, C), dtype=F32, device=dev)
+    lib().swap_pack_bwd(_p(dtokens), _p(dmaps[0]), _p(dmaps[1]), _p(dmaps[2]), _p(dgps), _p(dpos), B, S, C, float(drop_p), seed,
+                        seed_off, _stream())
+    return (*dmaps, dgps, dpos)
+
+
+def token_unpack_fwd(tokens, B, S):
+    """tokens [B, T, C] -> (image, lidar, radar [B*S, C, 8, 8], gps rows [B, 2, C]), no channel swap"""
+    C = tokens.shape[2]
+    _chk(tokens, B, 192 * S + 2, C)
+    assert C % 64 == 0
+    dev = tokens.device
+    maps = tuple(torch.empty((B * S, C, 8, 8), dtype=F32, device=dev) for _ in range(3))
+    gps = torch.empty((B, 2, C), dtype=F32, device=dev)
+    lib().token_unpack_fwd(_p(tokens), _p(maps[0]), _p(maps[1]), _p(maps[2]), _p(gps), B, S, C, _stream())
+    return (*maps, gps)
+
+
+def token_unpack_bwd(dimage, dlidar, dradar, dgps, B, S):
+    """-> dtokens [B, T, C] from the gradients of token_unpack_fwd's four outputs"""
+    C = dimage.shape[1]
+    _chk_maps((dimage, dlidar, dradar), dgps, B, S, C)
+    dtok = torch.empty((B, 192 * S + 2, C), dtype=F32, device=dimage.device)
+    lib().token_unpack_bwd(_p(dimage), _p(dlidar), _p(dradar), _p(dgps), _p(dtok), B, S, C, _stream())
+    return dtok

@@ -366,6 +366,51 @@ int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, in
                             size_t ws_bytes, void* stream);
 int ds6g_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, long rows, int cols, void* stream);
 
+/* ---- mamba_fusion.hip : the bi-branch Mamba fusion stage around the Mamba layer, fp32 (mambafuser_seq.py:74-231) -------
+ * Pointers 16-byte aligned, row strides (ld_*) in floats and multiples of 4; bad arguments return DS6G_ERR_ARG before
+ * anything is launched.  No float atomics: every sum has a fixed order, two runs are bit-identical.
+ *   sample_layernorm_fwd  ln1 = nn.LayerNorm((T, C)) (:79,94): x [B][n], n = T * C (n % 4 == 0), ONE mean / variance per
+ *                         sample over its n values, gamma / beta [n]; -> y, mean [B], rstd [B].  Several workgroups per
+ *                         sample: each reduces a chunk to (mean, squared deviations from that mean), the chunks are combined
+ *                         in double in chunk order (Chan et al.); the variance is never formed as E[x^2] - E[x]^2.
+ *   sample_layernorm_bwd  dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma, means over the sample's n; dgamma [n] =
+ *                         sum_b dy xhat and dbeta [n] = sum_b dy in index order, added to the destination when
+ *                         accumulate_param_grads.  ws of both >= ds6g_sample_layernorm_workspace_bytes (host-only query).
+ *   bimamba_gate_fwd      (:100-107) out[b, t] = bmN[b, L-1-t] * (leaky_relu_0.2(f2N[b, L-1-t]) + fm[b, t]) on [B*L][C]
+ *                         operands: bmN = backward_mamba walked in reverse and f2N = fc2, both of the UNflipped fc1 output,
+ *                         i.e. in natural token order; the reference never flips them back, the kernel reads them back to
+ *                         front instead of copying.
+ *   bimamba_gate_bwd      dfm, dbmN, df2N from dout and the three forward operands (the LeakyReLU slope from f2N: 1 for
+ *                         f2N > 0, else 0.2), each written in its producer's natural order.
+ *   swap_pack_fwd         (:196-214) image / lidar / radar [B*S][C][8][8] (NCHW), gps [B][2][C], pos_emb [T][C], T = 192 S + 2
+ *                         -> tokens [B][T][C] = dropout(pos_emb + t): token row ((m S + s) 64 + h 8 + w) of modality m = 0, 1,
+ *                         2 takes channel c from the map of modality (m + seg(c)) % 3, seg = 0 for c < C/3, 1 for
+ *                         c < 2 (C/3), else 2 (integer division); the gps rows come last.  Dropout counter = seed_off + flat
+ *                         element index of tokens, the rule of ds6g_dropout.  C % 64 == 0.
+ *   swap_pack_bwd         the three map gradients and dgps (the masked token gradient, routed back), dpos_emb [T][C] = its
+ *                         sum over b in index order; all written, not accumulated.
+ *   token_unpack_fwd/bwd  (:219-231) tokens [B][T][C] <-> three NCHW maps + [B][2][C] without the channel swap.
+ * The NCHW <-> token transposes are staged through LDS: 256-byte rows on both sides. */
+size_t ds6g_sample_layernorm_workspace_bytes(int B, long n);
+int ds6g_sample_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                              int B, long n, float eps, void* ws, size_t ws_bytes, void* stream);
+int ds6g_sample_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                              float* dx, float* dgamma, float* dbeta, int B, long n, int accumulate_param_grads, void* ws,
+                              size_t ws_bytes, void* stream);
+int ds6g_bimamba_gate_fwd(const float* fm, int ld_fm, const float* bm, int ld_bm, const float* f2, int ld_f2, float* out,
+                          int ld_out, int B, int L, int C, void* stream);
+int ds6g_bimamba_gate_bwd(const float* dout, int ld_dout, const float* fm, int ld_fm, const float* bm, int ld_bm,
+                          const float* f2, int ld_f2, float* dfm, int ld_dfm, float* dbm, int ld_dbm, float* df2, int ld_df2,
+                          int B, int L, int C, void* stream);
+int ds6g_swap_pack_fwd(const float* image, const float* lidar, const float* radar, const float* gps, const float* pos_emb,
+                       float* tokens, int B, int S, int C, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
+int ds6g_swap_pack_bwd(const float* dtokens, float* dimage, float* dlidar, float* dradar, float* dgps, float* dpos_emb, int B,
+                       int S, int C, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
+int ds6g_token_unpack_fwd(const float* tokens, float* image, float* lidar, float* radar, float* gps, int B, int S, int C,
+                          void* stream);
+int ds6g_token_unpack_bwd(const float* dimage, const float* dlidar, const float* dradar, const float* dgps, float* dtokens,
+                          int B, int S, int C, void* stream);
+
 /* ---- spatial.hip -------------------------------------------------------------------------------*/
 /* normalize_imagenet + stack + NCHW->NHWC: model2_seq.py:36-45,481-482,491-493 */
 int ds6g_pack_input(const float* src, float* dst, int B, int Cs, int H, int W, int Cd, int frames_per_sample, int t,

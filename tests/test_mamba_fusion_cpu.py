@@ -1,0 +1,261 @@
+"""CPU-side checks of the Mamba fusion stage: the pure-torch restatement (tests/mamba_fusion_ref.py) equals the fixture made
+from the reference's own MambaFusion, its fp32 run tracks its fp64 run, the LeakyReLU kink condition holds for every seed
+the GPU tests use, the modules keep the reference's parameter contract and initialisation, and every new C entry point
+refuses bad arguments on the host before any launch."""
+import functools
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from deepsense6g_tii_amd import _lib
+from tests import mamba_fusion_ref as fr
+from tests import mamba_ref as mr
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mambafusion_golden.npz")
+
+
+@functools.lru_cache(maxsize=None)
+def _fusion_runs(case):
+    C, S, n_layer, B, spread, pseed, iseed = case
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    p = fr.make_fusion_params(C, S, n_layer, seed=pseed, spread=spread)
+    ins, douts = fr.make_fusion_inputs(C, B, S, seed=iseed)
+    return fr.fusion_run(p, ins, douts, n_layer, S, torch.float64), fr.fusion_run(p, ins, douts, n_layer, S, torch.float32)
+
+
+@pytest.mark.parametrize("tag,case", [("spread", fr.FUSION_CASES[0]), ("refinit", fr.FUSION_CASES[1])])
+def test_restatement_equals_reference_fixture(tag, case):
+    gold = np.load(GOLDEN)
+    assert list(gold[f"{tag}:meta"]) == [int(v) for v in case]
+    (r64, margin), _ = _fusion_runs(case)
+    assert abs(margin - float(gold[f"{tag}:kink_margin"])) <= 1e-9 * margin
+    for k in fr.OUT_KEYS:
+        assert mr.rel_err(r64[k], torch.from_numpy(gold[f"{tag}:{k}"])) <= 1e-12, k
+    probes = sorted({k.split(":")[2] for k in gold.files if k.startswith(f"{tag}:grad:")})
+    assert len(probes) >= 12 and {"pos_emb", "mambablocks.0.ln1.weight", "mambablocks.0.backward_mamba.x_proj.weight",
+                                  "mambablocks.0.fc2.bias", "dimage"} <= set(probes)
+    for k in probes:
+        g = r64[k].double()
+        for stat, mine in (("absmax", g.abs().max()), ("l2", g.norm())):
+            want = float(gold[f"{tag}:grad:{k}:{stat}"])
+            assert abs(float(mine) - want) <= 1e-12 * max(abs(want), 1e-300), (k, stat)
+        want_abs = float(gold[f"{tag}:grad:{k}:absmax"])
+        head = torch.from_numpy(gold[f"{tag}:grad:{k}:head"])
+        assert float((g.flatten()[:16] - head).abs().max()) <= 1e-12 * want_abs, k
+
+
+@pytest.mark.parametrize("case", fr.FUSION_CASES[:2])
+def test_restatement_fp32_tracks_fp64(case):
+    (r64, _), (r32, _) = _fusion_runs(case)
+    for k in r64:
+        assert mr.rel_err(r32[k], r64[k]) <= 1e-4, k
+
+
+def test_kink_condition_holds_for_every_gpu_case():
+    """min|fc2 output| >= 2e-6 * max|fc2 output| in every block, on the fp64 run (forward only)"""
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    with torch.no_grad():
+        for B, L, C, wide, seed in fr.BLOCK_CASES:
+            probe = []
+            fr.block_ref(fr.make_block_params(C, L, seed=seed, wide=wide), fr.make_block_input(C, B, L, seed=seed)[0], "", probe)
+            assert fr.kink_margin(probe) >= fr.KINK_MIN, (B, L, C, wide, seed)
+        for C, S, n_layer, B, spread, pseed, iseed in fr.FUSION_CASES:
+            probe = []
+            ins, _ = fr.make_fusion_inputs(C, B, S, seed=iseed)
+            fr.fusion_ref(fr.make_fusion_params(C, S, n_layer, seed=pseed, spread=spread), n_layer, S,
+                          *(ins[k] for k in fr.IN_KEYS), probe=probe)
+            assert len(probe) == n_layer and fr.kink_margin(probe) >= fr.KINK_MIN, (C, S, n_layer, B, spread, pseed)
+
+
+def test_restatement_swap_and_token_order():
+    """channel c of modality m's tokens comes from modality (m + seg(c)) % 3; rows are modality-major, gps last"""
+    C, S, B = 64, 2, 2
+    ins, _ = fr.make_fusion_inputs(C, B, S, seed=3)
+    tok = fr.swap_pack_ref(*(ins[k] for k in fr.IN_KEYS), S)
+    assert tuple(tok.shape) == (B, 192 * S + 2, C) and torch.equal(tok[:, -2:], ins["gps"])
+    maps = [ins[k] for k in fr.IN_KEYS[:3]]
+    for m, s, h, w, c in ((0, 0, 0, 0, 0), (0, 1, 3, 5, 21), (1, 0, 7, 7, 20), (1, 1, 2, 0, 41), (2, 1, 4, 4, 42), (2, 0, 1, 6, 63)):
+        seg = 0 if c < C // 3 else (1 if c < C // 3 * 2 else 2)
+        for b in range(B):
+            assert tok[b, (m * S + s) * 64 + h * 8 + w, c] == maps[(m + seg) % 3][b * S + s, c, h, w]
+    outs = fr.unpack_ref(tok, S)
+    assert torch.equal(outs[3], ins["gps"]) and outs[1][1 * S + 1, 5, 2, 3] == tok[1, (1 * S + 1) * 64 + 2 * 8 + 3, 5]
+
+
+def _cfg(n_views=1):
+    return types.SimpleNamespace(n_views=n_views)
+
+
+def _fusion(C=64, S=1, n_layer=1, **kw):
+    from deepsense6g_tii_amd.mamba_fusion import MambaFusion
+    args = dict(n_embd=C, ln_size=(192 * S + 2, C), d_state=16, d_conv=4, expand=2, n_layer=n_layer, vert_anchors=8,
+                horz_anchors=8, seq_len=S, embd_pdrop=0.0, config=_cfg())
+    args.update(kw)
+    return MambaFusion(**args)
+
+
+@pytest.mark.parametrize("n_layer", [1, 2])
+def test_module_contract(n_layer):
+    torch.manual_seed(0)
+    C, S = 64, 1
+    m = _fusion(C, S, n_layer)
+    sd = m.state_dict()
+    want = fr.fusion_shapes(C, S, n_layer)
+    assert len(sd) == 3 + 24 * n_layer and set(sd) == set(fr.fusion_names(n_layer)) == set(want)
+    assert {n for n, _ in m.named_parameters()} == set(want)
+    for k, shape in want.items():
+        assert tuple(sd[k].shape) == shape and sd[k].dtype == torch.float32, k
+    # the reference's self.apply(_init_weights): every Linear N(0, 0.02) with zero bias, LayerNorm (1, 0), pos_emb zeros
+    assert (sd["pos_emb"] == 0).all()
+    for i in range(n_layer):
+        b = f"mambablocks.{i}."
+        assert (sd[b + "ln1.weight"] == 1).all() and (sd[b + "ln1.bias"] == 0).all()
+        for fc in ("fc1", "fc2"):
+            assert (sd[b + fc + ".bias"] == 0).all() and abs(float(sd[b + fc + ".weight"].std()) - 0.02) < 2e-3
+        for br in fr.BRANCHES:
+            assert (sd[b + br + ".dt_proj.bias"] == 0).all()
+            for lin in ("in_proj", "x_proj", "dt_proj", "out_proj"):
+                assert abs(float(sd[b + br + f".{lin}.weight"].std()) - 0.02) < 3e-3, lin
+            assert torch.equal(sd[b + br + ".A_log"], torch.log(torch.arange(1, 17, dtype=torch.float32)).repeat(2 * C, 1))
+            assert (sd[b + br + ".D"] == 1).all()
+            assert float(sd[b + br + ".conv1d.weight"].abs().max()) <= 0.5 and float(sd[b + br + ".conv1d.weight"].std()) > 0.1
+    assert (sd["ln_f.weight"] == 1).all() and (sd["ln_f.bias"] == 0).all()
+    p = {k: v.float() for k, v in fr.make_fusion_params(C, S, n_layer, seed=2).items()}
+    m.load_state_dict(p, strict=True)
+    for k in want:
+        assert torch.equal(m.state_dict()[k], p[k]), k
+    assert m.get_block_size() == S
+
+
+def test_module_refusals():
+    from deepsense6g_tii_amd.mamba_fusion import MambaBlock
+    with pytest.raises(ValueError):
+        _fusion(config=_cfg(n_views=4))
+    with pytest.raises(ValueError):
+        _fusion(d_state=8)
+    with pytest.raises(ValueError):
+        _fusion(C=48)
+    with pytest.raises(ValueError):
+        MambaBlock(48, (10, 48), 16, 4, 2)
+    with pytest.raises(ValueError):
+        _fusion(ln_size=(962, 64))            # seq_len 1 has 194 tokens
+    with pytest.raises(ValueError):
+        _fusion(vert_anchors=4)
+    m = _fusion()
+    z = torch.zeros(1, 64, 8, 8)
+    with pytest.raises(RuntimeError):
+        m(z, z, z, torch.zeros(1, 2, 64))
+    blk = MambaBlock(64, (10, 64), 16, 4, 2)
+    assert len(blk.state_dict()) == 24 and set(blk.state_dict()) == set(fr.block_names())
+    with pytest.raises(RuntimeError):
+        blk(torch.zeros(1, 10, 64))
+    m.set_dropout_seed(5)
+    assert (m._seed, m._seed_off) == (5, 0)
+
+
+P = 0x1000   # a non-NULL, 16-byte aligned stand-in: every call below must be refused before anything is launched
+BIG = 1 << 24
+
+
+def _each_null(n):
+    for i in range(n):
+        yield tuple(0 if j == i else P for j in range(n))
+
+
+def _each_misaligned(n, skip=()):
+    for i in range(n):
+        if i not in skip:
+            yield tuple(P + 4 if j == i else P for j in range(n))
+
+
+def _each_short(lds):
+    for i, ld in enumerate(lds):
+        yield tuple(ld - 4 if j == i else v for j, v in enumerate(lds))
+        yield tuple(ld + 2 if j == i else v for j, v in enumerate(lds))   # not a multiple of 4
+
+
+def _sln_fwd(L, ptrs=(P,) * 6, B=2, n=4096, eps=1e-5, ws=P, ws_bytes=BIG):
+    x, g, b, y, mean, rstd = ptrs
+    return L.sample_layernorm_fwd(x, g, b, y, mean, rstd, B, n, eps, ws, ws_bytes, 0)
+
+
+def _sln_bwd(L, ptrs=(P,) * 8, B=2, n=4096, ws=P, ws_bytes=BIG):
+    dy, x, mean, rstd, g, dx, dg, db = ptrs
+    return L.sample_layernorm_bwd(dy, x, mean, rstd, g, dx, dg, db, B, n, 0, ws, ws_bytes, 0)
+
+
+def _gate_fwd(L, ptrs=(P,) * 4, lds=(64,) * 4, B=2, Lq=5, C=64):
+    fm, bm, f2, out = ptrs
+    return L.bimamba_gate_fwd(fm, lds[0], bm, lds[1], f2, lds[2], out, lds[3], B, Lq, C, 0)
+
+
+def _gate_bwd(L, ptrs=(P,) * 7, lds=(64,) * 7, B=2, Lq=5, C=64):
+    do, fm, bm, f2, dfm, dbm, df2 = ptrs
+    return L.bimamba_gate_bwd(do, lds[0], fm, lds[1], bm, lds[2], f2, lds[3], dfm, lds[4], dbm, lds[5], df2, lds[6], B, Lq, C, 0)
+
+
+def _pack_fwd(L, ptrs=(P,) * 6, B=2, S=1, C=64, p=0.0):
+    return L.swap_pack_fwd(*ptrs, B, S, C, p, 0, 0, 0)
+
+
+def _pack_bwd(L, ptrs=(P,) * 6, B=2, S=1, C=64, p=0.0):
+    return L.swap_pack_bwd(*ptrs, B, S, C, p, 0, 0, 0)
+
+
+def _unpack_fwd(L, ptrs=(P,) * 5, B=2, S=1, C=64):
+    return L.token_unpack_fwd(*ptrs, B, S, C, 0)
+
+
+def _unpack_bwd(L, ptrs=(P,) * 5, B=2, S=1, C=64):
+    return L.token_unpack_bwd(*ptrs, B, S, C, 0)
+
+
+def test_entry_points_reject_bad_arguments_without_launching():
+    L = _lib.lib()
+    E = _lib.Ds6gError
+
+    def refused(fn, **bad):
+        with pytest.raises(E, match="code 1$"):
+            fn(L, **bad)
+
+    need = int(L.sample_layernorm_workspace_bytes(2, 4096))
+    for fn, nptr, unaligned_ok in ((_sln_fwd, 6, (4, 5)), (_sln_bwd, 8, (2, 3))):   # mean / rstd: scalars per sample
+        for ptrs in _each_null(nptr):
+            refused(fn, ptrs=ptrs)
+        for ptrs in _each_misaligned(nptr, skip=unaligned_ok):
+            refused(fn, ptrs=ptrs)
+        for bad in (dict(B=0), dict(B=-1), dict(n=0), dict(n=-4), dict(n=4098), dict(ws=0), dict(ws=P + 4), dict(ws_bytes=need - 1),
+                    dict(ws_bytes=0)):
+            refused(fn, **bad)
+    refused(_sln_fwd, eps=0.0)
+    for fn, nptr in ((_gate_fwd, 4), (_gate_bwd, 7)):
+        for ptrs in _each_null(nptr):
+            refused(fn, ptrs=ptrs)
+        for ptrs in _each_misaligned(nptr):
+            refused(fn, ptrs=ptrs)
+        for lds in _each_short((64,) * nptr):
+            refused(fn, lds=lds)
+        for bad in (dict(B=0), dict(Lq=0), dict(Lq=-2), dict(C=0), dict(C=62)):
+            refused(fn, **bad)
+    for fn, nptr in ((_pack_fwd, 6), (_pack_bwd, 6), (_unpack_fwd, 5), (_unpack_bwd, 5)):
+        for ptrs in _each_null(nptr):
+            refused(fn, ptrs=ptrs)
+        for ptrs in _each_misaligned(nptr):
+            refused(fn, ptrs=ptrs)
+        for bad in (dict(B=0), dict(S=0), dict(S=-1), dict(C=0), dict(C=48), dict(C=96)):
+            refused(fn, **bad)
+    for fn in (_pack_fwd, _pack_bwd):
+        refused(fn, p=1.0)
+        refused(fn, p=-0.1)
+
+
+def test_size_query_is_host_only_and_monotone():
+    L = _lib.lib()
+    q = L.sample_layernorm_workspace_bytes
+    assert q(0, 4096) == 0 and q(2, 0) == 0 and q(-1, -1) == 0
+    base = q(2, 962 * 64)
+    assert base > 0 and q(3, 962 * 64) > base and q(2, 962 * 128) > base and q(2, 962 * 64 + 4) >= base
+    assert q(12, 962 * 512) < (1 << 20)     # partials only: two doubles per workgroup and sample
