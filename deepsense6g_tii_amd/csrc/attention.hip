@@ -1385,6 +1385,11 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
     const int cols4 = nh * hd / 4;
     const long n4 = (long)B * T * cols4;
     const size_t hand = handover_bytes(B, T, nh, hd);
+    // 16-bit storage runs the hand-over form only (the recomputing dQ kernel reads a fp32 o): it takes the size the query
+    // states, nothing less, so that the caller has one number to go by; fp32 takes any size (fewer splits, or recomputation)
+    if (o16 || in16) {
+        DS6G_CHECK_WS(ws && ws_bytes >= ds6g_attention_workspace_bytes(B, T, nh, hd, ld));
+    }
     if (g_ds6g_attn_handover && ws && ws_bytes >= hand + 2 * slab * sizeof(float)) {
         // ---- hand-over path: delta -> dK(/dV) kernel that also writes its dS (and P) tiles -> [dV from P] -> dQ from dS
         p.hs = (float*)ws;
@@ -1444,7 +1449,7 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
         return DS6G_OK;
     }
     // the recomputing form reads o inside its dQ kernel (fp32 only): the bf16-storage path needs the hand-over workspace
-    DS6G_CHECK_ARG(!o16 && !in16);
+    DS6G_CHECK_ARG(!o16 && !in16);   // reached by 16-bit storage only with the hand-over form switched off (debug flag)
     // ---- dQ (split over keys)
     {
         const size_t max_by_ws = ws ? ws_bytes / (slab * sizeof(float)) : 1;

@@ -787,6 +787,7 @@ int ds6g_h16_conv2d_fwd(int st16, const void* x, const void* w, void* y, int out
 // statistics updated in place when given) from per-tile column partials written by the conv's epilogue: the statistics are
 // those of the STORED bf16 tensor (what ds6g_h16_bn_stats would compute), without a pass over it.
 // ws: >= ds6g_h16_conv_bnstats_workspace_bytes(N * Ho * Wo, K).
+size_t ds6g_h16_conv_bnstats_workspace_bytes(long M, int K);
 extern "C++" template <typename T16>
 static int h16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
                                  int stride, int pad, float eps, float momentum, float* mean, float* invstd,
@@ -801,7 +802,8 @@ static int h16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, 
     p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
     const int tile = pick_tile(p.Mg, p.Ng, 1);
     const int nblk = cdiv(p.Mg, tile == 0 ? 128 : 64);
-    DS6G_CHECK_ARG(ws_bytes >= (size_t)nblk * 2 * K * sizeof(double));
+    // the size the query states (64-row tiles), also where 128-row tiles need half of it: one contract for the caller
+    DS6G_CHECK_WS(ws_bytes >= ds6g_h16_conv_bnstats_workspace_bytes(p.Mg, K));
     p.bn_partial = (double*)ws;
     const int rc = launch_bgemm<B_FWD, T16>(p, 1, 1, tile, (hipStream_t)stream);
     if (rc) return rc;

@@ -18,6 +18,15 @@
         }                                                                                      \
     } while (0)
 
+// a caller-owned workspace smaller than the entry point needs (its *_workspace_bytes query): refused before any launch
+#define DS6G_CHECK_WS(cond)                                                                    \
+    do {                                                                                       \
+        if (!(cond)) {                                                                         \
+            fprintf(stderr, "[ds6g] workspace too small: %s (%s:%d)\n", #cond, __FILE__, __LINE__); \
+            return DS6G_ERR_WORKSPACE;                                                         \
+        }                                                                                      \
+    } while (0)
+
 // Storage code `st16`, the first argument of every ds6g_h16_* / *_h16* entry point (include/ds6g.h): the values of in16 /
 // out16 / dp16 inside the library; 0 (fp32) has entry points of its own and is refused with every other value.
 #define DS6G_ST_BF16 1

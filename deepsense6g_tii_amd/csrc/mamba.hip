@@ -509,7 +509,7 @@ int ds6g_causal_conv1d_silu_bwd(const float* x, int ld_x, const float* w, const 
     DS6G_CHECK_ARG(x && w && bias && dy && dx && dw && dbias && ws && dims_ok(B, L, D));
     DS6G_CHECK_ARG(ld_ok(ld_x, D) && ld_ok(ld_dy, D) && ld_ok(ld_dx, D));
     DS6G_CHECK_ARG(al16(x) && al16(w) && al16(bias) && al16(dy) && al16(dx) && al16(ws));
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_causal_conv1d_workspace_bytes(B, L, D));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_causal_conv1d_workspace_bytes(B, L, D));
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (L + CONV_TT - 1) / CONV_TT;
     hipLaunchKernelGGL(conv1d_silu_bwd_kernel, dim3(D / CONV_CB, nblk, B), dim3(256), 0, st, x, ld_x, w, bias, dy, ld_dy, dx,
@@ -530,7 +530,7 @@ int ds6g_selective_scan_fwd(const float* u, int ld_u, const float* delta_raw, in
     DS6G_CHECK_ARG(ld_ok(ld_u, D) && ld_ok(ld_delta, D) && ld_ok(ld_z, D) && ld_ok(ld_y, D) && ld_ok(ld_b, NS) &&
                    ld_ok(ld_c, NS));
     DS6G_CHECK_ARG(al16(u) && al16(delta_raw) && al16(Bm) && al16(Cm) && al16(z) && al16(y) && al16(ws) && al16(saved));
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_selective_scan_workspace_bytes(B, L, D));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_selective_scan_workspace_bytes(B, L, D));
     hipStream_t st = (hipStream_t)stream;
     const ScanWs o = scan_ws(B, L, D);
     float* wsf = (float*)ws;
@@ -566,7 +566,7 @@ int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, in
                    ld_ok(ld_dcm, NS));
     DS6G_CHECK_ARG(al16(u) && al16(delta_raw) && al16(Bm) && al16(Cm) && al16(z) && al16(dy) && al16(saved) && al16(du) &&
                    al16(ddelta) && al16(dBm) && al16(dCm) && al16(dz) && al16(ws));
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_selective_scan_workspace_bytes(B, L, D));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_selective_scan_workspace_bytes(B, L, D));
     hipStream_t st = (hipStream_t)stream;
     const ScanWs o = scan_ws(B, L, D);
     float* wsf = (float*)ws;

@@ -405,7 +405,7 @@ int ds6g_sample_layernorm_fwd(const float* x, const float* gamma, const float* b
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && gamma && beta && y && mean && rstd && ws && sln_dims_ok(B, n) && eps > 0.f);
     DS6G_CHECK_ARG(al16(x) && al16(gamma) && al16(beta) && al16(y) && al16(ws));
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_sample_layernorm_workspace_bytes(B, n));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_sample_layernorm_workspace_bytes(B, n));
     hipStream_t st = (hipStream_t)stream;
     const int nchunk = sln_chunks(n);
     double* part = (double*)ws;
@@ -426,7 +426,7 @@ int ds6g_sample_layernorm_bwd(const float* dy, const float* x, const float* mean
     DS6G_ENTER();
     DS6G_CHECK_ARG(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && ws && sln_dims_ok(B, n));
     DS6G_CHECK_ARG(al16(dy) && al16(x) && al16(gamma) && al16(dx) && al16(dgamma) && al16(dbeta) && al16(ws));
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_sample_layernorm_workspace_bytes(B, n));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_sample_layernorm_workspace_bytes(B, n));
     hipStream_t st = (hipStream_t)stream;
     const int nblk = sln_colblocks(n);
     double* part = (double*)ws;

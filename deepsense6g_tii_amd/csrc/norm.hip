@@ -476,7 +476,7 @@ static int bn_stats_run(const TX* x, long M, int C, float eps, float momentum, f
     int rpb, nblk;
     DS6G_CHECK_ARG(x && mean && invstd && ws && M > 0);
     DS6G_CHECK_ARG(bn_geometry(M, C, &rpb, &nblk) == DS6G_OK);
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_bn_workspace_bytes(M, C));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_bn_workspace_bytes(M, C));
     double* partial = (double*)ws;
     const size_t lds = (size_t)(256 / (C / 4)) * 2 * C * sizeof(double);
     hipLaunchKernelGGL((bn_reduce_kernel<0, TX, TX>), dim3(nblk), dim3(256), lds, (hipStream_t)stream, x, (const TX*)nullptr,
@@ -513,7 +513,7 @@ static int bn_bwd_run(const TA* dy, const PoolGrad pg, const TA* y_mask, const T
     const float* mg = relu_beta ? gamma : nullptr;
     int rpb, nblk;
     DS6G_CHECK_ARG(bn_geometry(M, C, &rpb, &nblk) == DS6G_OK);
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_bn_workspace_bytes(M, C));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_bn_workspace_bytes(M, C));
     double* partial = (double*)ws;
     float* coef = (float*)((char*)ws + (size_t)nblk * 2 * C * sizeof(double));
     const size_t lds = (size_t)(256 / (C / 4)) * 2 * C * sizeof(double);
@@ -556,7 +556,7 @@ static int ln_bwd_launch(const TDY* dy, const float* x, const float* mean, const
     const uint32_t thr = ds6g_drop_threshold(drop_p);
     const float dscale = 1.f / (1.f - drop_p);
     DS6G_CHECK_ARG(C % 64 == 0 && C <= 512);
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_layernorm_bwd_workspace_bytes(M, C));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_layernorm_bwd_workspace_bytes(M, C));
     const int nblk = cdiv(M, LN_BWD_ROWS);
     float* partial = (float*)ws;
     dim3 grid(nblk), block(256);
@@ -783,7 +783,7 @@ size_t ds6g_colsum_workspace_bytes(long M, int C) { return (size_t)cdiv(M, COLSU
 int ds6g_colsum(const float* x, long M, int C, float* out, int accumulate, void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && out && ws && C % 4 == 0 && M > 0);
-    DS6G_CHECK_ARG(ws_bytes >= ds6g_colsum_workspace_bytes(M, C));
+    DS6G_CHECK_WS(ws_bytes >= ds6g_colsum_workspace_bytes(M, C));
     const int rpb = COLSUM_ROWS;
     const int nblk = cdiv(M, rpb);
     const int cols_per_pass = (C / 4) < 256 ? (C / 4) : 256;

@@ -364,9 +364,10 @@ static int h16_stem_fwd(const void* x, const float* w, int cin, void* y, int N, 
                        float* mean, float* invstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes,
                        void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_h16_stem_workspace_bytes());
+    DS6G_CHECK_ARG(x && w && y && ws && cin >= 1 && cin <= 4);
     StemParams p{};
     DS6G_CHECK_ARG(stem_geometry(p, N, H, W) == DS6G_OK);
+    DS6G_CHECK_WS(ws_bytes >= ds6g_h16_stem_workspace_bytes());
     T16* w16 = (T16*)ws;
     p.x = (const __bf16*)x; p.w16 = (const __bf16*)w16; p.y = (__bf16*)y;
     p.bn_partial = (double*)((char*)ws + (((size_t)KO * WROW * 2 + 1023) & ~(size_t)1023));
@@ -427,9 +428,10 @@ extern "C++" template <typename T16>
 static int h16_stem_wgrad(const void* x, const void* dy, float* dw, int cin, int N, int H, int W, int accumulate, void* ws,
                          size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && dy && dw && ws && cin >= 1 && cin <= 4 && ws_bytes >= ds6g_h16_stem_workspace_bytes());
+    DS6G_CHECK_ARG(x && dy && dw && ws && cin >= 1 && cin <= 4);
     StemParams p{};
     DS6G_CHECK_ARG(stem_geometry(p, N, H, W) == DS6G_OK);
+    DS6G_CHECK_WS(ws_bytes >= ds6g_h16_stem_workspace_bytes());
     p.x = (const __bf16*)x; p.dy = (const __bf16*)dy; p.slabs = (float*)ws;
     hipStream_t st = (hipStream_t)stream;
     const int grid = p.ntiles < STEM_GRID_WGRAD ? p.ntiles : STEM_GRID_WGRAD;

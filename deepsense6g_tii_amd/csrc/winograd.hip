@@ -1114,7 +1114,7 @@ int ds6g_conv3x3_winograd_wgrad(const float* x, const float* dy, float* dw, int 
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && dy && dw && ws && ds6g_winograd_wgrad_supported(N, H, W, C, K));
     const size_t slab = (size_t)16 * K * C * sizeof(float);
-    DS6G_CHECK_ARG(ws_bytes >= slab);
+    DS6G_CHECK_WS(ws_bytes >= slab);
     WinoWgradParams p{};
     p.x = x; p.dy = dy; p.du = ws; p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
     p.TH = H / 2; p.TW = W / 2;

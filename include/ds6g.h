@@ -9,7 +9,12 @@
  * conv weights OHWI (= torch channels_last storage of an OIHW parameter), Linear weights [N][K]
  * (torch layout); `stream` is a hipStream_t; every call is asynchronous on that stream, performs
  * no allocation and no synchronisation (hipGraph-capturable).  Return 0 on success, non-zero on
- * bad arguments / launch failure (message on stderr).  `ws` arguments are caller-owned scratch.
+ * bad arguments (1) / launch failure (2) (message on stderr).  `ws` arguments are caller-owned scratch.  Where an entry
+ * point states a minimum for it (its *_workspace_bytes query, or a size in its comment), a smaller ws_bytes is refused with 3
+ * (DS6G_ERR_WORKSPACE) after the argument checks and before anything is launched.  Exceptions: the fp32 ds6g_attention_fwd /
+ * _bwd and ds6g_attention_fwd_bf16out / _fwd_h16 take ANY size (their query is the size that allows every split; the 16-bit
+ * backwards need all of it); ds6g_grad_norm_clip refuses below the 8 + 8 * min(1024, ceil(n / 1024)) bytes that its n uses
+ * (8 KiB + 8 covers every n).
  * Dropout masks are a pure function of (seed, seed_off + element index): backward regenerates
  * them, nothing is stored.
  */
@@ -338,7 +343,8 @@ int ds6g_gru_head_bwd(const float* dpred, const float* h0, const float* saved, c
  *                        A = -exp(A_log) (D, 16); y_t = (<h_t, Cm_t> + Dp u_t) silu(z_t).  The sequence is cut into chunks
  *                        of ds6g_selective_scan_chunk() positions that run in parallel (state pass, carry over the chunks,
  *                        emitting pass).  saved (nullable): ds6g_selective_scan_saved_floats floats, the states at the chunk
- *                        starts (B, chunks, D, 16) - the only tape the backward needs beside the operands.
+ *                        starts (B, chunks, D, 16; chunk 0's slot, the zero state, is neither written nor read) - the only tape
+ *                        the backward needs beside the operands.
  *   selective_scan_bwd   du, d delta_raw, dz (D wide each), dBm / dCm (16 wide; summed over the channels), dA_log (D, 16)
  *                        and dD (D) (summed over the tokens), all written, not accumulated.  Recomputes the states of a chunk
  *                        from its checkpoint; never divides by exp(delta A).  Deterministic (partial slabs, fixed order).

@@ -115,9 +115,11 @@ def test_entry_points_reject_bad_arguments_without_launching():
     for lds in _each_short((128,) * 3):
         with pytest.raises(E, match="code 1$"):
             _conv_bwd(L, lds=lds)
-    for bad in (dict(Lq=0), dict(ws=0), dict(ws_bytes=int(L.causal_conv1d_workspace_bytes(2, 8, 128)) - 1)):
+    for bad in (dict(Lq=0), dict(ws=0)):
         with pytest.raises(E, match="code 1$"):
             _conv_bwd(L, **bad)
+    with pytest.raises(E, match="code 3$"):      # DS6G_ERR_WORKSPACE: one byte short of the size query
+        _conv_bwd(L, ws_bytes=int(L.causal_conv1d_workspace_bytes(2, 8, 128)) - 1)
     for ptrs in _each_null(9):
         with pytest.raises(E, match="code 1$"):
             _scan_fwd(L, ptrs=ptrs)
@@ -125,18 +127,22 @@ def test_entry_points_reject_bad_arguments_without_launching():
         with pytest.raises(E, match="code 1$"):
             _scan_fwd(L, lds=lds)
     need = int(L.selective_scan_workspace_bytes(2, 8, 128))
-    for bad in (dict(Lq=0), dict(Lq=-1), dict(B=0), dict(D=0), dict(D=144), dict(ws=0), dict(ws_bytes=need - 1)):
+    for bad in (dict(Lq=0), dict(Lq=-1), dict(B=0), dict(D=0), dict(D=144), dict(ws=0)):
         with pytest.raises(E, match="code 1$"):
             _scan_fwd(L, **bad)
+    with pytest.raises(E, match="code 3$"):
+        _scan_fwd(L, ws_bytes=need - 1)
     for ptrs in _each_null(17):
         with pytest.raises(E, match="code 1$"):
             _scan_bwd(L, ptrs=ptrs)
     for lds in _each_short((128, 128, 16, 16, 128, 128, 128, 128, 16, 16, 128)):
         with pytest.raises(E, match="code 1$"):
             _scan_bwd(L, lds=lds)
-    for bad in (dict(Lq=0), dict(ws=0), dict(ws_bytes=need - 1)):
+    for bad in (dict(Lq=0), dict(ws=0)):
         with pytest.raises(E, match="code 1$"):
             _scan_bwd(L, **bad)
+    with pytest.raises(E, match="code 3$"):
+        _scan_bwd(L, ws_bytes=need - 1)
     for args in ((0, 8, P, 8, 4, 4), (P, 8, 0, 8, 4, 4), (P, 8, P, 8, 0, 4), (P, 8, P, 8, 4, 6), (P, 4, P, 8, 4, 8),
                  (P, 8, P, 4, 4, 8), (P, 6, P, 8, 4, 4)):
         with pytest.raises(E, match="code 1$"):

@@ -227,9 +227,11 @@ def test_entry_points_reject_bad_arguments_without_launching():
             refused(fn, ptrs=ptrs)
         for ptrs in _each_misaligned(nptr, skip=unaligned_ok):
             refused(fn, ptrs=ptrs)
-        for bad in (dict(B=0), dict(B=-1), dict(n=0), dict(n=-4), dict(n=4098), dict(ws=0), dict(ws=P + 4), dict(ws_bytes=need - 1),
-                    dict(ws_bytes=0)):
+        for bad in (dict(B=0), dict(B=-1), dict(n=0), dict(n=-4), dict(n=4098), dict(ws=0), dict(ws=P + 4)):
             refused(fn, **bad)
+        for short in (need - 1, 0):
+            with pytest.raises(E, match="code 3$"):      # DS6G_ERR_WORKSPACE
+                fn(L, ws_bytes=short)
     refused(_sln_fwd, eps=0.0)
     for fn, nptr in ((_gate_fwd, 4), (_gate_bwd, 7)):
         for ptrs in _each_null(nptr):
