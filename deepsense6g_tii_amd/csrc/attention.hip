@@ -21,6 +21,8 @@
 
 int g_ds6g_attn_percu = 0;
 int g_ds6g_attn_handover = 1;  // 0: backward recomputes S / dP in every kernel (ds6g_set_debug_flags 0x01000000)
+int g_ds6g_attn_merged_sum = 1;  // 0 (ds6g_set_debug_flags 0x08000000): the hand-over backward sums dK/dV and dQ slabs in two launches
+thread_local int g_attn_bwd_slab_sums = 0;  // slab_sum_kernel launches of this thread's last backward (ds6g_last_attention_bwd_slab_sums)
 int g_ds6g_attn_fused128 = 1;  // 0 (ds6g_set_debug_flags 0x04000000): hd = 128 backward as dK kernel + dropped-P tiles + dV kernel
 
 // -DDS6G_ATTN_CLOCKS (tools/attn_clocks.py builds its own library): wave 0 of workgroup 0 of attn_bwd_dkv_kernel sums the
@@ -1157,15 +1159,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dv2_kernel(const AttnParams p
 }
 
 // out[row][0..cols) = sum_s part[s][row][0..cols)   (dq / dk / dv split slabs; rows of stride ld_in -> ld_out).
-// blockIdx.y picks the (part, out) pair, so dK and dV are reduced by one launch.
+// blockIdx.y picks the (part, out) pair, so dK and dV are reduced by one launch - and, in the hand-over backward, dQ with
+// them (pair 2, which has a split count of its own): every element is still the sum of its slabs in slab order.
 __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ part0, float* __restrict__ out0,
                                                        const float* __restrict__ part1, float* __restrict__ out1,
                                                        long n4, int cols4, int ld_in, int ld_out, int splits, size_t slab,
-                                                       int out16) {
+                                                       int out16, const float* __restrict__ part2 = nullptr,
+                                                       float* __restrict__ out2 = nullptr, int splits2 = 0) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
-    const float* part = blockIdx.y ? part1 : part0;
-    float* out = blockIdx.y ? out1 : out0;
+    const float* part = blockIdx.y == 2 ? part2 : (blockIdx.y ? part1 : part0);
+    float* out = blockIdx.y == 2 ? out2 : (blockIdx.y ? out1 : out0);
+    if (blockIdx.y == 2) splits = splits2;
     const long row = i / cols4;
     const int c = (int)(i - row * cols4) * 4;
     const float* src = part + row * ld_in + c;
@@ -1365,6 +1370,7 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
                               int nh, int hd, int ld_qkv, int ld, int ld_dqkv, float drop_p, uint64_t seed,
                               uint64_t seed_off, void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
+    g_attn_bwd_slab_sums = 0;
     DS6G_CHECK_ARG(q && k && v && o && d_o && lse && delta && dq && dk && dv && ld % 4 == 0 && ld >= nh * hd);
     DS6G_CHECK_ARG(ld_qkv % 4 == 0 && ld_qkv >= nh * hd && (size_t)B * T * ld_qkv * sizeof(float) < OOB_OFF);
     DS6G_CHECK_ARG(ld_dqkv % 4 == 0 && ld_dqkv >= nh * hd);
@@ -1421,9 +1427,32 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
         int rc = fused128 ? launch_hd<6>(p, hd, dim3(blocks128, nh * p.splits, B), st)
                           : launch_hd<3>(p, hd, dim3(blocks128, nh * p.splits, B), st);
         if (rc) return rc;
-        if (p.splits > 1) {
+        // The dK / dV sum feeds nothing before the projection gradients that follow the whole backward, so where the dQ
+        // kernel is split too and its slabs fit BEHIND the dK and dV slabs (at the split counts of the two-launch form, never fewer:
+        // the workspace query does not grow, and the result stays bit-identical to that form), the sum waits
+        // and one launch after attn_bwd_dq2 reduces all three: one launch less on the GPT stage's serial chain
+        const int splits_kv = p.splits;
+        bool merged = false;
+        if (!two_pass && splits_kv > 1 && g_ds6g_attn_merged_sum) {
+            plan(hd >= 64 ? 2 : 3, 1);
+            merged = p.splits > 1 && (size_t)(2 * splits_kv + p.splits) * slab * sizeof(float) <= wsb;
+        }
+        if (merged) {
+            float* wsq = wsf + (size_t)2 * splits_kv * slab;
+            p.dq = wsq;
+            rc = launch_hd<5>(p, hd, dim3(blocks128, nh * p.splits, B), st);
+            if (rc) return rc;
+            ++g_attn_bwd_slab_sums;
+            hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 3), dim3(256), 0, st, (const float*)wsf, dk,
+                               (const float*)(wsf + (size_t)splits_kv * slab), dv, n4, cols4, ld, ld_dqkv, splits_kv, slab, out16,
+                               (const float*)wsq, dq, p.splits);
+            DS6G_LAUNCH_CHECK();
+            return DS6G_OK;
+        }
+        if (splits_kv > 1) {
+            ++g_attn_bwd_slab_sums;
             hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), two_pass ? 1 : 2), dim3(256), 0, st, (const float*)wsf, dk,
-                               (const float*)(wsf + (size_t)p.splits * slab), dv, n4, cols4, ld, ld_dqkv, p.splits, slab, out16);
+                               (const float*)(wsf + (size_t)splits_kv * slab), dv, n4, cols4, ld, ld_dqkv, splits_kv, slab, out16);
             DS6G_LAUNCH_CHECK();
         }
         if (two_pass) {
@@ -1432,6 +1461,7 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
             rc = launch_hd<4>(p, hd, dim3(blocks128, nh * p.splits, B), st);
             if (rc) return rc;
             if (p.splits > 1) {
+                ++g_attn_bwd_slab_sums;
                 hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 1), dim3(256), 0, st, (const float*)wsf, dv,
                                    (const float*)nullptr, (float*)nullptr, n4, cols4, ld, ld_dqkv, p.splits, slab, out16);
                 DS6G_LAUNCH_CHECK();
@@ -1442,6 +1472,7 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
         rc = launch_hd<5>(p, hd, dim3(blocks128, nh * p.splits, B), st);
         if (rc) return rc;
         if (p.splits > 1) {
+            ++g_attn_bwd_slab_sums;
             hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 1), dim3(256), 0, st, (const float*)wsf, dq,
                                (const float*)nullptr, (float*)nullptr, n4, cols4, ld, ld_dqkv, p.splits, slab, out16);
             DS6G_LAUNCH_CHECK();
@@ -1462,6 +1493,7 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
         int rc = launch_hd<1>(p, hd, dim3(blocks128, nh * splits, B), st);
         if (rc) return rc;
         if (splits > 1) {
+            ++g_attn_bwd_slab_sums;
             hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 1), dim3(256), 0, st, (const float*)ws, dq,
                                (const float*)nullptr, (float*)nullptr, n4, cols4, ld, ld_dqkv, splits, slab, out16);
             DS6G_LAUNCH_CHECK();
@@ -1480,6 +1512,7 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
         int rc = launch_hd<2>(p, hd, dim3(blocks128, nh * splits, B), st);
         if (rc) return rc;
         if (splits > 1) {
+            ++g_attn_bwd_slab_sums;
             hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 2), dim3(256), 0, st, (const float*)wsf, dk,
                                (const float*)(wsf + (size_t)splits * slab), dv, n4, cols4, ld, ld_dqkv, splits, slab, out16);
             DS6G_LAUNCH_CHECK();
@@ -1487,6 +1520,10 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
     }
     return DS6G_OK;
 }
+
+// test instrumentation: how many slab_sum_kernel launches the calling thread's last attention backward made (0: nothing was
+// split; 1: dK, dV and dQ slabs in one launch; 2: the dK / dV sum and the dQ sum apart; 3 with the two-pass hd = 128 form)
+int ds6g_last_attention_bwd_slab_sums(void) { return g_attn_bwd_slab_sums; }
 
 int ds6g_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o,
                        const float* lse, float* delta, float* dq, float* dk, float* dv, int B, int T, int nh, int hd,

@@ -39,6 +39,9 @@
         return (st16) == DS6G_ST_BF16 ? fn<__bf16>(__VA_ARGS__) : fn<_Float16>(__VA_ARGS__);   \
     } while (0)
 
+// descriptors of the batched entry points: the one definition the public header uses too
+#include "../../include/ds6g_types.h"
+
 // hipGetLastError() is sticky per thread: a benign failure inside the caller's runtime (e.g. PyTorch probing a
 // host pointer) would otherwise be reported by our next launch check.  Every entry point clears it first.
 #define DS6G_ENTER() (void)hipGetLastError()

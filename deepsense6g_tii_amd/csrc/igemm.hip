@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 extern int g_ds6g_attn_fused128;  // attention.hip: hd = 128 backward with the fused dK + dV kernel (experiment)
+extern int g_ds6g_attn_merged_sum;  // attention.hip: hand-over backward reduces the dK, dV and dQ slabs in one launch
 extern int g_ds6g_attn_percu;  // attention.hip: split-heuristic override (timing experiments)
 extern int g_ds6g_attn_handover;
 extern int g_wino_kb64;         // winograd.hip: 64-channel workgroups (timing experiments)
@@ -1001,6 +1002,7 @@ int ds6g_set_debug_flags(int flags) {
     g_dbg = flags & 0xbf;  // 0x80: force the general (FAST 0) walk
     g_ds6g_attn_handover = (flags & 0x01000000) ? 0 : 1;
     g_ds6g_attn_fused128 = (flags & 0x04000000) ? 0 : 1;
+    g_ds6g_attn_merged_sum = (flags & 0x08000000) ? 0 : 1;
     g_ds6g_attn_percu = (flags >> 20) & 0xf;  // attention: resident-workgroups-per-CU assumption of the split heuristic
     g_wino_kb64 = (flags & 0x02000000) ? 1 : 0;
     g_bf16_bk32 = (flags & 0x10000000) ? 0 : 1;

@@ -396,7 +396,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy,
 __global__ __launch_bounds__(256) void col_finalize_kernel(const float* __restrict__ partial, int nblk, int ncol,
                                                            float* __restrict__ out0, float* __restrict__ out1,
                                                            int split_at, int accumulate) {
-    // 4 columns x 64 partial-groups per block (like the BatchNorm finalize kernels: latency-bound launches, 68 per step)
+    // 4 columns x 64 partial-groups per block (like the BatchNorm finalize kernels: latency-bound launches; the GPT stages batch theirs,
+    // ln_finalize_batched_kernel below)
     constexpr int CF_COLS = 4, CF_GROUPS = 64;
     __shared__ double red[4][CF_COLS];
     const int cl = threadIdx.x & (CF_COLS - 1), g = threadIdx.x / CF_COLS;
@@ -412,6 +413,34 @@ __global__ __launch_bounds__(256) void col_finalize_kernel(const float* __restri
     s = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
     float* dst = (c < split_at) ? (out0 + c) : (out1 + (c - split_at));
     *dst = accumulate ? (*dst + (float)s) : (float)s;
+}
+
+// col_finalize_kernel for up to DS6G_LN_FINALIZE_MAX LayerNorms in one launch (ds6g_layernorm_finalize_batched): blockIdx.y
+// picks the LayerNorm, whose descriptor travels in the kernel arguments; per column the same fp64 sums over the same 64
+// partial groups in the same order, so dgamma / dbeta are bit-identical to the per-LayerNorm launches
+struct LnFinalizeBatch {
+    ds6g_ln_finalize_desc d[DS6G_LN_FINALIZE_MAX];
+};
+__global__ __launch_bounds__(256) void ln_finalize_batched_kernel(const LnFinalizeBatch batch) {
+    constexpr int CF_COLS = 4, CF_GROUPS = 64;
+    __shared__ double red[4][CF_COLS];
+    const ds6g_ln_finalize_desc& d = batch.d[blockIdx.y];
+    const int ncol = 2 * d.C, nblk = d.nblk;
+    if ((int)blockIdx.x * CF_COLS >= ncol) return;  // the grid is as wide as the widest LayerNorm of the batch
+    const float* __restrict__ partial = d.partial;
+    const int cl = threadIdx.x & (CF_COLS - 1), g = threadIdx.x / CF_COLS;
+    const int c = blockIdx.x * CF_COLS + cl;
+    double s = 0.0;
+    if (c < ncol)
+        for (int b = g; b < nblk; b += CF_GROUPS) s += (double)partial[(size_t)b * ncol + c];
+#pragma unroll
+    for (int o = CF_COLS; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) < CF_COLS) red[threadIdx.x >> 6][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (g != 0 || c >= ncol) return;
+    s = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
+    float* dst = (c < d.C) ? (d.dgamma + c) : (d.dbeta + (c - d.C));
+    *dst = d.accumulate ? (*dst + (float)s) : (float)s;
 }
 
 // partial[blk][c] = sum over the block's rows of x[r][c]   (bias gradients, pos_emb gradient)
@@ -550,8 +579,10 @@ template <typename TDY, typename TDD>
 static int ln_bwd_launch(const TDY* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                          const float* add, float* dx, float* dgamma, float* dbeta, int M, int C, int accumulate_param_grads,
                          TDD* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws, size_t ws_bytes,
-                         hipStream_t st) {
-    DS6G_CHECK_ARG(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && ws);
+                         hipStream_t st, bool defer = false) {
+    // defer: ws is the caller's own [cdiv(M,16)][2C] partial buffer, which ds6g_layernorm_finalize_batched reduces later;
+    // dgamma / dbeta are not touched and no col_finalize_kernel is launched
+    DS6G_CHECK_ARG(dy && x && mean && rstd && gamma && dx && (defer || (dgamma && dbeta)) && ws && M > 0);
     DS6G_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
     const uint32_t thr = ds6g_drop_threshold(drop_p);
     const float dscale = 1.f / (1.f - drop_p);
@@ -568,6 +599,7 @@ static int ln_bwd_launch(const TDY* dy, const float* x, const float* mean, const
         default: DS6G_CHECK_ARG(!"LayerNorm width must be 64/128/256/512");
     }
     DS6G_LAUNCH_CHECK();
+    if (defer) return DS6G_OK;
     hipLaunchKernelGGL(col_finalize_kernel, dim3(cdiv(2 * C, 4)), dim3(256), 0, st, partial, nblk, 2 * C, dgamma,
                        dbeta, C, accumulate_param_grads);
     DS6G_LAUNCH_CHECK();
@@ -768,6 +800,53 @@ static int layernorm_bwd_h16(const void* dy, int dy16, const float* x, const flo
                                         accumulate_param_grads, (T16*)dx_drop, drop_p, seed, seed_off, ws, ws_bytes,
                                         (hipStream_t)stream);
 }
+// the deferred form of ds6g_layernorm_bwd / ds6g_layernorm_bwd_h16: `partial` (>= ds6g_layernorm_bwd_workspace_bytes(M, C), the caller's
+// own buffer, kept until the finalize) receives the row-block partials of dgamma / dbeta and nothing reduces them here
+int ds6g_layernorm_bwd_partial(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                               const float* add, float* dx, int M, int C, float* dx_drop, float drop_p, uint64_t seed,
+                               uint64_t seed_off, float* partial, size_t partial_bytes, void* stream) {
+    DS6G_ENTER();
+    return ln_bwd_launch<float, float>(dy, x, mean, rstd, gamma, add, dx, nullptr, nullptr, M, C, 0, dx_drop, drop_p, seed,
+                                       seed_off, partial, partial_bytes, (hipStream_t)stream, true);
+}
+extern "C++" template <typename T16>
+static int layernorm_bwd_h16_partial(const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
+                                     const float* gamma, const float* add, float* dx, int M, int C, void* dx_drop,
+                                     float drop_p, uint64_t seed, uint64_t seed_off, float* partial, size_t partial_bytes,
+                                     void* stream) {
+    DS6G_ENTER();
+    if (dy16)
+        return ln_bwd_launch<T16, T16>((const T16*)dy, x, mean, rstd, gamma, add, dx, nullptr, nullptr, M, C, 0,
+                                       (T16*)dx_drop, drop_p, seed, seed_off, partial, partial_bytes, (hipStream_t)stream,
+                                       true);
+    return ln_bwd_launch<float, T16>((const float*)dy, x, mean, rstd, gamma, add, dx, nullptr, nullptr, M, C, 0,
+                                     (T16*)dx_drop, drop_p, seed, seed_off, partial, partial_bytes, (hipStream_t)stream, true);
+}
+int ds6g_layernorm_bwd_h16_partial(int st16, const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
+                                   const float* gamma, const float* add, float* dx, int M, int C, void* dx_drop, float drop_p,
+                                   uint64_t seed, uint64_t seed_off, float* partial, size_t partial_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, layernorm_bwd_h16_partial, dy, dy16, x, mean, rstd, gamma, add, dx, M, C, dx_drop, drop_p, seed,
+                    seed_off, partial, partial_bytes, stream);
+}
+// dgamma / dbeta (+)= the column sums of `count` (1 .. DS6G_LN_FINALIZE_MAX) partial buffers, in one launch; descs is a host
+// array read during the call
+int ds6g_layernorm_finalize_batched(const ds6g_ln_finalize_desc* descs, int count, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(descs && count >= 1 && count <= DS6G_LN_FINALIZE_MAX);
+    LnFinalizeBatch batch{};
+    int cmax = 0;
+    for (int i = 0; i < count; ++i) {
+        const ds6g_ln_finalize_desc& d = descs[i];
+        DS6G_CHECK_ARG(d.partial && d.dgamma && d.dbeta && d.nblk > 0);
+        DS6G_CHECK_ARG(d.C == 64 || d.C == 128 || d.C == 256 || d.C == 512);  // the widths ln_bwd_launch has kernels for
+        batch.d[i] = d;
+        cmax = d.C > cmax ? d.C : cmax;
+    }
+    hipLaunchKernelGGL(ln_finalize_batched_kernel, dim3(cdiv(2 * cmax, 4), count), dim3(256), 0, (hipStream_t)stream, batch);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
 int ds6g_layernorm_bwd_h16(int st16, const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
                            const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
                            int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,

@@ -178,16 +178,21 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
 
 // ------------------------------------------------------------------------------------------------
 // tokens[row(f,ph,pw)][c] = dropout( mean_{k x k window} feat + pos_emb[tok][c] )
+// (the four token-glue kernels below exist as a body over an explicit block index `bx`, run by a single-map kernel and by a
+// grouped one that takes the three modality maps of a stage in one launch: blockIdx.z picks the map's descriptor, which
+// travels in the kernel arguments, and the blocks past a smaller map's range leave at the body's own bound check)
+struct MapGroup {
+    ds6g_map_desc d[3];
+};
 template <typename TF>
-__global__ __launch_bounds__(256) void avgpool_tokens_fwd_kernel(const TF* __restrict__ feat,
-                                                                 const float* __restrict__ pos_emb,
-                                                                 float* __restrict__ tokens, int N, int H, int C,
-                                                                 int fps, int mod_off, int T, uint32_t thr,
-                                                                 float scale, uint64_t seed, uint64_t seed_off_in,
-                                                                 const uint64_t* __restrict__ salt) {
+__device__ __forceinline__ void avgpool_tokens_fwd_body(const TF* __restrict__ feat, const float* __restrict__ pos_emb,
+                                                        float* __restrict__ tokens, int N, int H, int C, int fps,
+                                                        int mod_off, int T, uint32_t thr, float scale, uint64_t seed,
+                                                        uint64_t seed_off_in, const uint64_t* __restrict__ salt,
+                                                        unsigned bx) {
     const uint64_t seed_off = seed_off_in + ((salt && thr) ? *salt : (uint64_t)0);
     const int cg = C >> 2;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long i = (long)bx * blockDim.x + threadIdx.x;
     if (i >= (long)N * 64 * cg) return;
     const int c4 = (int)(i % cg) * 4;
     long t = i / cg;
@@ -209,6 +214,25 @@ __global__ __launch_bounds__(256) void avgpool_tokens_fwd_kernel(const TF* __res
         for (int j = 0; j < 4; ++j) s[j] = ds6g_keep(seed, seed_off + o + j, thr) ? s[j] * scale : 0.f;
     }
     *reinterpret_cast<f32x4*>(tokens + o) = s;
+}
+template <typename TF>
+__global__ __launch_bounds__(256) void avgpool_tokens_fwd_kernel(const TF* __restrict__ feat,
+                                                                 const float* __restrict__ pos_emb,
+                                                                 float* __restrict__ tokens, int N, int H, int C,
+                                                                 int fps, int mod_off, int T, uint32_t thr,
+                                                                 float scale, uint64_t seed, uint64_t seed_off_in,
+                                                                 const uint64_t* __restrict__ salt) {
+    avgpool_tokens_fwd_body<TF>(feat, pos_emb, tokens, N, H, C, fps, mod_off, T, thr, scale, seed, seed_off_in, salt,
+                                blockIdx.x);
+}
+template <typename TF>
+__global__ __launch_bounds__(256) void avgpool_tokens_fwd3_kernel(const MapGroup g, const float* __restrict__ pos_emb,
+                                                                  float* __restrict__ tokens, int B, int H, int C, int T,
+                                                                  uint32_t thr, float scale, uint64_t seed,
+                                                                  uint64_t seed_off_in, const uint64_t* __restrict__ salt) {
+    const ds6g_map_desc& d = g.d[blockIdx.z];
+    avgpool_tokens_fwd_body<TF>((const TF*)d.in, pos_emb, tokens, B * d.frames_per_sample, H, C, d.frames_per_sample,
+                                d.mod_off, T, thr, scale, seed, seed_off_in, salt, blockIdx.x);
 }
 
 // GPS rows: tokens[b][T-2+j][c] = dropout(emb[b][j][c] + pos_emb[T-2+j][c])
@@ -243,12 +267,11 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 
 // dfeat[f,h,w,c] = dfeat_in[f,h,w,c] + dtok[row(f,h/k,w/k)][c] / k^2
 template <typename TF>
-__global__ __launch_bounds__(256) void avgpool_tokens_bwd_kernel(const float* __restrict__ dtok,
-                                                                 const TF* __restrict__ dfeat_in,
-                                                                 TF* __restrict__ dfeat, int N, int H, int C,
-                                                                 int fps, int mod_off, int T) {
+__device__ __forceinline__ void avgpool_tokens_bwd_body(const float* __restrict__ dtok, const TF* __restrict__ dfeat_in,
+                                                        TF* __restrict__ dfeat, int N, int H, int C, int fps, int mod_off,
+                                                        int T, unsigned bx) {
     const int cg = C >> 2;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long i = (long)bx * blockDim.x + threadIdx.x;
     if (i >= (long)N * H * H * cg) return;
     const int c4 = (int)(i % cg) * 4;
     long t = i / cg;
@@ -260,6 +283,20 @@ __global__ __launch_bounds__(256) void avgpool_tokens_bwd_kernel(const float* __
     f32x4 g = *reinterpret_cast<const f32x4*>(dtok + row * C + c4) * (1.0f / (float)(k * k));
     if (dfeat_in) g += ld4(dfeat_in + i * 4);
     st4(dfeat + i * 4, g);
+}
+template <typename TF>
+__global__ __launch_bounds__(256) void avgpool_tokens_bwd_kernel(const float* __restrict__ dtok,
+                                                                 const TF* __restrict__ dfeat_in,
+                                                                 TF* __restrict__ dfeat, int N, int H, int C,
+                                                                 int fps, int mod_off, int T) {
+    avgpool_tokens_bwd_body<TF>(dtok, dfeat_in, dfeat, N, H, C, fps, mod_off, T, blockIdx.x);
+}
+template <typename TF>
+__global__ __launch_bounds__(256) void avgpool_tokens_bwd3_kernel(const MapGroup g, const float* __restrict__ dtok, int B,
+                                                                  int H, int C, int T) {
+    const ds6g_map_desc& d = g.d[blockIdx.z];
+    avgpool_tokens_bwd_body<TF>(dtok, (const TF*)d.in, (TF*)d.out, B * d.frames_per_sample, H, C, d.frames_per_sample,
+                                d.mod_off, T, blockIdx.x);
 }
 
 // PyTorch bilinear, align_corners=False, scale_factor given: src = max((dst+0.5)/scale - 0.5, 0)
@@ -273,12 +310,11 @@ __device__ __forceinline__ void bilin_src(int d, float inv_scale, int in_size, i
 
 // out[f,h,w,c] = feat[f,h,w,c] + bilinear_up(tokmap[f])[h,w,c]; tokmap rows live in the token buffer
 template <typename TF>
-__global__ __launch_bounds__(256) void upsample_add_fwd_kernel(const TF* __restrict__ feat,
-                                                               const float* __restrict__ tokens,
-                                                               TF* __restrict__ out, int N, int H, int C, int fps,
-                                                               int mod_off, int T) {
+__device__ __forceinline__ void upsample_add_fwd_body(const TF* __restrict__ feat, const float* __restrict__ tokens,
+                                                      TF* __restrict__ out, int N, int H, int C, int fps, int mod_off,
+                                                      int T, unsigned bx) {
     const int cg = C >> 2;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long i = (long)bx * blockDim.x + threadIdx.x;
     if (i >= (long)N * H * H * cg) return;
     const int c4 = (int)(i % cg) * 4;
     long t = i / cg;
@@ -298,21 +334,34 @@ __global__ __launch_bounds__(256) void upsample_add_fwd_kernel(const TF* __restr
     const f32x4 up = (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
     st4(out + i * 4, ld4(feat + i * 4) + up);
 }
+template <typename TF>
+__global__ __launch_bounds__(256) void upsample_add_fwd_kernel(const TF* __restrict__ feat,
+                                                               const float* __restrict__ tokens,
+                                                               TF* __restrict__ out, int N, int H, int C, int fps,
+                                                               int mod_off, int T) {
+    upsample_add_fwd_body<TF>(feat, tokens, out, N, H, C, fps, mod_off, T, blockIdx.x);
+}
+template <typename TF>
+__global__ __launch_bounds__(256) void upsample_add_fwd3_kernel(const MapGroup g, const float* __restrict__ tokens, int B,
+                                                                int H, int C, int T) {
+    const ds6g_map_desc& d = g.d[blockIdx.z];
+    upsample_add_fwd_body<TF>((const TF*)d.in, tokens, (TF*)d.out, B * d.frames_per_sample, H, C, d.frames_per_sample,
+                              d.mod_off, T, blockIdx.x);
+}
 
 // dtok[row(f,ph,pw)][c] = sum_{h,w} wh(h,ph) ww(w,pw) dout[f,h,w,c]   (adjoint of the upsample).
 // One workgroup per token cell (f, ph, pw): the <= 4k x 4k window of contributing pixels (k = H/8) is split over
 // 256 / (C/4) row slices, the 1-D bilinear weights are tabulated once per workgroup, partial sums meet in LDS.
 constexpr int UPB_MAXWIN = 64;  // window rows / columns per cell (4 * H/8, H <= 128)
 template <typename TF>
-__global__ __launch_bounds__(256) void upsample_add_bwd_kernel(const TF* __restrict__ dout,
-                                                               float* __restrict__ dtok, int N, int H, int C, int fps,
-                                                               int mod_off, int T) {
+__device__ __forceinline__ void upsample_add_bwd_body(const TF* __restrict__ dout, float* __restrict__ dtok, int N, int H,
+                                                      int C, int fps, int mod_off, int T, unsigned bx) {
     __shared__ float whs[UPB_MAXWIN], wws[UPB_MAXWIN];
     __shared__ f32x4 part[256];
     const int cg = C >> 2;                      // float4 channel groups
     const int lanes_c = cg < 256 ? cg : 256;    // threads along channels
     const int slices = 256 / lanes_c;           // row slices of the window
-    const int f = blockIdx.x >> 6, hw = blockIdx.x & 63;
+    const int f = bx >> 6, hw = bx & 63;
     const int ph = hw >> 3, pw = hw & 7;
     const int k = H >> 3;
     const float inv = 8.0f / (float)H;
@@ -358,6 +407,20 @@ __global__ __launch_bounds__(256) void upsample_add_bwd_kernel(const TF* __restr
         }
         __syncthreads();
     }
+}
+template <typename TF>
+__global__ __launch_bounds__(256) void upsample_add_bwd_kernel(const TF* __restrict__ dout,
+                                                               float* __restrict__ dtok, int N, int H, int C, int fps,
+                                                               int mod_off, int T) {
+    upsample_add_bwd_body<TF>(dout, dtok, N, H, C, fps, mod_off, T, blockIdx.x);
+}
+template <typename TF>
+__global__ __launch_bounds__(256) void upsample_add_bwd3_kernel(const MapGroup g, float* __restrict__ dtok, int B, int H,
+                                                                int C, int T) {
+    const ds6g_map_desc& d = g.d[blockIdx.z];
+    const int N = B * d.frames_per_sample;
+    if (blockIdx.x >= (unsigned)N * 64u) return;  // one workgroup per token cell of THIS map (the whole block leaves)
+    upsample_add_bwd_body<TF>((const TF*)d.in, dtok, N, H, C, d.frames_per_sample, d.mod_off, T, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -781,6 +844,80 @@ static int h16_upsample_add_bwd(const void* dout, float* dtok, int N, int H, int
 int ds6g_h16_upsample_add_bwd(int st16, const void* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
                               int T, void* stream) {
     DS6G_RETURN_H16(st16, h16_upsample_add_bwd, dout, dtok, N, H, C, frames_per_sample, mod_off, T, stream);
+}
+
+// ---- the three modality maps of a fusion stage in ONE launch each (the single-map entry points above, per-element
+// identical: same arithmetic, same dropout counters).  st: 0 fp32 maps, DS6G_ST_BF16 / DS6G_ST_F16 16-bit maps; maps: a
+// host array of 3 descriptors read during the call; map m holds B * frames_per_sample frames of H x H x C.
+extern "C++" {
+static int map_group(const ds6g_map_desc* maps, int B, bool need_in, bool need_out, MapGroup* g, int* nmax) {
+    DS6G_CHECK_ARG(maps && B > 0);
+    *nmax = 0;
+    for (int m = 0; m < 3; ++m) {
+        DS6G_CHECK_ARG((maps[m].in || !need_in) && (maps[m].out || !need_out) && maps[m].frames_per_sample > 0 &&
+                       maps[m].mod_off >= 0);
+        g->d[m] = maps[m];
+        const int n = B * maps[m].frames_per_sample;
+        *nmax = n > *nmax ? n : *nmax;
+    }
+    return DS6G_OK;
+}
+#define DS6G_ST_DISPATCH(st, kern, ...)                                                                 \
+    do {                                                                                                \
+        if ((st) == 0) hipLaunchKernelGGL((kern<float>), __VA_ARGS__);                                  \
+        else if ((st) == DS6G_ST_BF16) hipLaunchKernelGGL((kern<__bf16>), __VA_ARGS__);                 \
+        else hipLaunchKernelGGL((kern<_Float16>), __VA_ARGS__);                                         \
+    } while (0)
+}
+int ds6g_avgpool_tokens_fwd3(int st, const ds6g_map_desc* maps, const float* pos_emb, float* tokens, int B, int H, int C,
+                             int T, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(st == 0 || st == DS6G_ST_BF16 || st == DS6G_ST_F16);
+    DS6G_CHECK_ARG(pos_emb && tokens && C > 0 && C % 4 == 0 && H > 0 && H % 8 == 0 && drop_p >= 0.f && drop_p < 1.f);
+    MapGroup g{};
+    int nmax;
+    if (int rc = map_group(maps, B, true, false, &g, &nmax)) return rc;
+    DS6G_ST_DISPATCH(st, avgpool_tokens_fwd3_kernel, dim3(grid1((long)nmax * 64 * (C / 4)), 1, 3), dim3(256), 0,
+                     (hipStream_t)stream, g, pos_emb, tokens, B, H, C, T, ds6g_drop_threshold(drop_p), 1.f / (1.f - drop_p),
+                     seed, seed_off, g_ds6g_salt);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+int ds6g_avgpool_tokens_bwd3(int st, const ds6g_map_desc* maps, const float* dtok, int B, int H, int C, int T, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(st == 0 || st == DS6G_ST_BF16 || st == DS6G_ST_F16);
+    DS6G_CHECK_ARG(dtok && C > 0 && C % 4 == 0 && H > 0 && H % 8 == 0);
+    MapGroup g{};
+    int nmax;
+    if (int rc = map_group(maps, B, false, true, &g, &nmax)) return rc;
+    DS6G_ST_DISPATCH(st, avgpool_tokens_bwd3_kernel, dim3(grid1((long)nmax * H * H * (C / 4)), 1, 3), dim3(256), 0,
+                     (hipStream_t)stream, g, dtok, B, H, C, T);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+int ds6g_upsample_add_fwd3(int st, const ds6g_map_desc* maps, const float* tokens, int B, int H, int C, int T, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(st == 0 || st == DS6G_ST_BF16 || st == DS6G_ST_F16);
+    DS6G_CHECK_ARG(tokens && C > 0 && C % 4 == 0 && H > 0 && H % 8 == 0);
+    MapGroup g{};
+    int nmax;
+    if (int rc = map_group(maps, B, true, true, &g, &nmax)) return rc;
+    DS6G_ST_DISPATCH(st, upsample_add_fwd3_kernel, dim3(grid1((long)nmax * H * H * (C / 4)), 1, 3), dim3(256), 0,
+                     (hipStream_t)stream, g, tokens, B, H, C, T);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+int ds6g_upsample_add_bwd3(int st, const ds6g_map_desc* maps, float* dtok, int B, int H, int C, int T, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(st == 0 || st == DS6G_ST_BF16 || st == DS6G_ST_F16);
+    DS6G_CHECK_ARG(dtok && C > 0 && C % 4 == 0 && H > 0 && H % 8 == 0 && 5 * (H / 8) <= UPB_MAXWIN);
+    MapGroup g{};
+    int nmax;
+    if (int rc = map_group(maps, B, true, false, &g, &nmax)) return rc;
+    DS6G_ST_DISPATCH(st, upsample_add_bwd3_kernel, dim3(nmax * 64, 1, 3), dim3(256), 0, (hipStream_t)stream, g, dtok, B, H,
+                     C, T);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
 }
 
 extern "C++" template <typename T16>

@@ -257,51 +257,100 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
 }
 
 // y[m][n] = act( sum_k x[row(m)][k] w[n][k] + b[n] ), row(m) = (m / rpg) * gstride + (m % rpg) * K
-__global__ void small_linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                        const float* __restrict__ b, float* __restrict__ y, int M, int N, int K,
-                                        int rpg, long gstride, int relu) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M * N) return;
-    const int n = i % N, m = i / N;
+// One thread per output runs the fmaf chain over k in order, starting from the bias - the arithmetic and summation order these
+// layers have always had, so results do not move.  What the chain waits for does: a thread walking its own weight row reads
+// with a stride of K floats across the wave (up to 74 us for the 12 x 256 outputs of join[0], on the GPT stages' serial
+// chain), so the workgroup first copies the SLF_KC-column slice of its 256 weight rows into LDS with contiguous 128-B runs
+// per row, and the chains read LDS (row pitch SLF_KC + 1: conflict-free).  x rows are shared by the lanes of a wave.
+// The next slice travels from HBM into registers while the chains run over the current one: K / SLF_KC round trips in all.
+constexpr int SLF_KC = 32;
+__global__ __launch_bounds__(256) void small_linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                               const float* __restrict__ b, float* __restrict__ y, int M,
+                                                               int N, int K, int rpg, long gstride, int relu) {
+    __shared__ float wt[256][SLF_KC + 1];
+    const int base = blockIdx.x * 256;
+    const int total = M * N;
+    const int i = base + threadIdx.x;
+    const bool live = i < total;  // no early return: every thread copies and meets the barriers
+    const int n = live ? i % N : 0, m = live ? i / N : 0;
     const float* xr = x + (long)(m / rpg) * gstride + (long)(m % rpg) * K;
-    const float* wr = w + (long)n * K;
-    float s = b ? b[n] : 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf(xr[k], wr[k], s);
-    y[i] = relu ? fmaxf(s, 0.f) : s;
+    // copy duty of this thread: column ck of the rows o = 8 q + cr, q = 0 .. 31 (a quarter-wave reads 128 contiguous bytes)
+    const int ck = threadIdx.x & (SLF_KC - 1), cr = threadIdx.x / SLF_KC;
+    int wrow[SLF_KC];
+#pragma unroll
+    for (int q = 0; q < SLF_KC; ++q) {
+        const int o = base + q * 8 + cr;
+        wrow[q] = o < total ? o % N : -1;
+    }
+    float wreg[SLF_KC], xnext[SLF_KC], xcur[SLF_KC];
+    auto fetch = [&](int k0) {
+        const int kc = min(SLF_KC, K - k0);
+#pragma unroll
+        for (int q = 0; q < SLF_KC; ++q) {
+            wreg[q] = (wrow[q] >= 0 && ck < kc) ? w[(long)wrow[q] * K + k0 + ck] : 0.f;
+            xnext[q] = (live && q < kc) ? xr[k0 + q] : 0.f;
+        }
+    };
+    fetch(0);
+    float s = (live && b) ? b[n] : 0.f;
+    for (int k0 = 0; k0 < K; k0 += SLF_KC) {
+        const int kc = min(SLF_KC, K - k0);
+#pragma unroll
+        for (int q = 0; q < SLF_KC; ++q) {
+            wt[q * 8 + cr][ck] = wreg[q];
+            xcur[q] = xnext[q];
+        }
+        __syncthreads();
+        if (k0 + SLF_KC < K) fetch(k0 + SLF_KC);
+        if (kc == SLF_KC) {
+#pragma unroll
+            for (int kk = 0; kk < SLF_KC; ++kk) s = fmaf(xcur[kk], wt[threadIdx.x][kk], s);
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < SLF_KC; ++kk)
+                if (kk < kc) s = fmaf(xcur[kk], wt[threadIdx.x][kk], s);
+        }
+        __syncthreads();
+    }
+    if (live) y[i] = relu ? fmaxf(s, 0.f) : s;
 }
 
 // dyeff = dy * (y_mask > 0); dx[row(m)][k] (+)= sum_n dyeff[m][n] w[n][k]
-__global__ void small_linear_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ y_mask,
-                                          const float* __restrict__ w, float* __restrict__ dx, int M, int N, int K,
-                                          int rpg, long gstride, int accumulate) {  // rpg/gstride address dx
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M * K) return;
-    const int k = i % K, m = i / K;
-    // few threads (M*K) and a long reduction: four independent chains, eight loads each in flight
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+// The sum of an output has always been four interleaved fmaf chains (chain j over n = j, j + 4, ... below the last multiple of
+// four, the tail on chain 0) added as (s0 + s1) + (s2 + s3).  One thread ran all four: M * K threads with an N-long loop,
+// 17 us on average on the GPT stages' serial chain.  Four neighbouring lanes now run one chain each and meet by two
+// shuffles in that same order - four times the lanes in flight, the same bits.
+__global__ __launch_bounds__(256) void small_linear_dgrad_kernel(const float* __restrict__ dy,
+                                                                 const float* __restrict__ y_mask,
+                                                                 const float* __restrict__ w, float* __restrict__ dx, int M,
+                                                                 int N, int K, int rpg, long gstride,
+                                                                 int accumulate) {  // rpg/gstride address dx
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long i = t >> 2;
+    const int j = (int)(t & 3);
+    const bool live = i < (long)M * K;  // no early return: every lane takes part in the shuffles
+    const int k = live ? (int)(i % K) : 0, m = live ? (int)(i / K) : 0;
     const float* dyr = dy + (long)m * N;
     const float* mkr = y_mask ? y_mask + (long)m * N : nullptr;
-    int n = 0;
-#pragma unroll 2
-    for (; n + 4 <= N; n += 4) {
-        float g0 = dyr[n], g1 = dyr[n + 1], g2 = dyr[n + 2], g3 = dyr[n + 3];
-        if (mkr) {
-            if (!(mkr[n] > 0.f)) g0 = 0.f;
-            if (!(mkr[n + 1] > 0.f)) g1 = 0.f;
-            if (!(mkr[n + 2] > 0.f)) g2 = 0.f;
-            if (!(mkr[n + 3] > 0.f)) g3 = 0.f;
+    const int n4 = N & ~3;
+    float s = 0.f;
+    if (live) {
+#pragma unroll 8
+        for (int n = j; n < n4; n += 4) {  // the loads of eight steps in flight; the chain itself stays in order
+            float g = dyr[n];
+            if (mkr && !(mkr[n] > 0.f)) g = 0.f;
+            s = fmaf(g, w[(long)n * K + k], s);
         }
-        s0 = fmaf(g0, w[(long)n * K + k], s0);
-        s1 = fmaf(g1, w[(long)(n + 1) * K + k], s1);
-        s2 = fmaf(g2, w[(long)(n + 2) * K + k], s2);
-        s3 = fmaf(g3, w[(long)(n + 3) * K + k], s3);
+        if (j == 0)
+            for (int n = n4; n < N; ++n) {
+                float g = dyr[n];
+                if (mkr && !(mkr[n] > 0.f)) g = 0.f;
+                s = fmaf(g, w[(long)n * K + k], s);
+            }
     }
-    for (; n < N; ++n) {
-        float g = dyr[n];
-        if (mkr && !(mkr[n] > 0.f)) g = 0.f;
-        s0 = fmaf(g, w[(long)n * K + k], s0);
-    }
-    const float s = (s0 + s1) + (s2 + s3);
+    s += __shfl_xor(s, 1, 64);   // lanes 0 / 1: s0 + s1, lanes 2 / 3: s2 + s3
+    s += __shfl_xor(s, 2, 64);   // (s0 + s1) + (s2 + s3)
+    if (!live || j != 0) return;
     float* d = dx + (long)(m / rpg) * gstride + (long)(m % rpg) * K + k;
     *d = accumulate ? *d + s : s;
 }
@@ -471,7 +520,7 @@ int ds6g_grad_norm_clip(const float* g, long n, float max_norm, float pre_scale,
 int ds6g_small_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K,
                           int rows_per_group, long group_stride, int relu, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && rows_per_group > 0);
+    DS6G_CHECK_ARG(x && w && y && rows_per_group > 0 && M > 0 && N > 0 && K > 0);
     hipLaunchKernelGGL(small_linear_fwd_kernel, dim3(cdiv((long)M * N, 256)), dim3(256), 0, (hipStream_t)stream, x, w,
                        b, y, M, N, K, rows_per_group, group_stride, relu);
     DS6G_LAUNCH_CHECK();
@@ -487,7 +536,8 @@ int ds6g_small_linear_bwd(const float* dy, const float* y_mask, const float* x, 
     DS6G_CHECK_ARG(dy && x && w && dw && db && rows_per_group > 0);
     if (dx) {
         DS6G_CHECK_ARG(dx_rows_per_group > 0);
-        hipLaunchKernelGGL(small_linear_dgrad_kernel, dim3(cdiv((long)M * K, 256)), dim3(256), 0, (hipStream_t)stream,
+        DS6G_CHECK_ARG(M > 0 && K > 0);
+        hipLaunchKernelGGL(small_linear_dgrad_kernel, dim3(cdiv((long)M * K * 4, 256)), dim3(256), 0, (hipStream_t)stream,
                            dy, y_mask, w, dx, M, N, K, dx_rows_per_group, dx_group_stride, accumulate_dx);
         DS6G_LAUNCH_CHECK();
     }

@@ -326,6 +326,12 @@ class TransFuser(nn.Module):
         self.overlap_wgrad = True  # GPT-stage weight gradients on a second stream, overlapping the dgrad / attention chain
         self._wg_map, self._wg_used, self._wg_keep = {}, {}, []
         self.overlap_wgrad_trunks = False  # measured: no gain on top of the three concurrent trunk streams
+        # The GPT stages are one dependent chain on one stream, where every launch costs its own time plus a boundary and
+        # nothing else is resident to hide it.  Two kinds of launch leave that chain (each bit-identical to the form the
+        # flag's 0 keeps, for A/B with tools/ab_model_flags.py):
+        self.defer_ln_finalize = True  # dgamma / dbeta of a stage's 17 LayerNorms reduced by ONE launch at the stage's end
+        self.group_stage_glue = True   # token pooling / upsampling of the three modality maps in one launch, not three
+        self._ln_defer = None          # (partial buffer, descriptors) of the stage whose backward is running
         # bf16 configuration: train-mode BatchNorm statistics come out of the conv's epilogue (ds6g_h16_conv2d_fwd_bnstats)
         self.fuse_bn_stats16 = os.environ.get("DS6G_FUSE_BN_STATS16", "1") != "0"
         self.use_winograd = True  # 3x3 / stride-1 convs (forward and data gradient) as Winograd F(2x2, 3x3) in fp32 mode
@@ -948,7 +954,11 @@ class TransFuser(nn.Module):
         fdt = feats[0].dtype   # 16-bit storage: feature maps bf16 / f16, tokens fp32
         for m in range(3):
             assert feats[m].shape[0] == B * fps[m] and feats[m].shape[3] == C and feats[m].dtype == fdt
-            ops.avgpool_tokens_fwd(feats[m], pos, x0, fps[m], offs[m], T, pe, self._seed, off_e)
+        if self.group_stage_glue:
+            ops.avgpool_tokens_fwd3(feats, pos, x0, fps, offs, T, pe, self._seed, off_e)
+        else:
+            for m in range(3):
+                ops.avgpool_tokens_fwd(feats[m], pos, x0, fps[m], offs[m], T, pe, self._seed, off_e)
         _, gptr, rpg, gstride, K = gps_src
         gemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
         L.small_linear_fwd(gptr, wk.w(vel.weight), wk.w(vel.bias), gemb.data_ptr(), 2 * B, C, K, rpg, gstride, 0, st)
@@ -959,11 +969,12 @@ class TransFuser(nn.Module):
             x, c = self._gpt_block_fwd(wk, blk, x, B, T)
             blk_ctx.append(c)
         xo, mf, rf = ops.layernorm_fwd(x, wk.w(gpt.ln_f.weight), wk.w(gpt.ln_f.bias), gpt.ln_f.eps)
-        outs = []
-        for m in range(3):
-            o = torch.empty_like(feats[m])
-            ops.upsample_add_fwd(feats[m], xo, o, fps[m], offs[m], T)
-            outs.append(o)
+        outs = [torch.empty_like(feats[m]) for m in range(3)]
+        if self.group_stage_glue:
+            ops.upsample_add_fwd3(feats, xo, outs, fps, offs, T)
+        else:
+            for m in range(3):
+                ops.upsample_add_fwd(feats[m], xo, outs[m], fps[m], offs[m], T)
         return outs, xo, _StageRec(s, C, T, fps, offs, pe, off_e, gps_src, blk_ctx, x, mf, rf, [f.shape for f in feats])
 
     def _dp_check_fresh_grads(self):
@@ -1189,8 +1200,8 @@ class TransFuser(nn.Module):
         g2w, a2 = g(blk.ln2.weight)
         g2b, _ = g(blk.ln2.bias)
         # x1 = x + drop(proj(y)): the LayerNorm backward emits dx1 and dropout(dx1) together
-        dx1, dz1 = op.ln_bwd(dh2, r.x1, r.m2, r.r2, w32(blk.ln2.weight), g2w, g2b, self._ws, add=dx2,
-                             accumulate=bool(a2), drop=(r.pr, self._seed, r.off_p))
+        dx1, dz1 = self._ln_bwd(op, dh2, r.x1, r.m2, r.r2, w32(blk.ln2.weight), g2w, g2b, a2, add=dx2,
+                                drop=(r.pr, self._seed, r.off_p))
         wgrad(at.proj, r.y, dz1)
         dy = op.lin_dgrad(dz1, w(at.proj.weight), C)   # bf16 storage: the attention backward's dO
         # the fused [3C, C] weight-gradient block and its [3C] bias block start at key.*: only valid while the three
@@ -1218,12 +1229,27 @@ class TransFuser(nn.Module):
             op.lin_dgrad(dv, w(at.value.weight), C, out=dh, accumulate=True)
         g1w, a1 = g(blk.ln1.weight)
         g1b, _ = g(blk.ln1.bias)
-        ln1 = (dh, r.x, r.m1, r.r1, w32(blk.ln1.weight), g1w, g1b, self._ws)
+        ln1 = (op, dh, r.x, r.m1, r.r1, w32(blk.ln1.weight), g1w, g1b, a1)
         if next_drop is not None:   # also dropout(dx) on the mask of the block below
-            return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1), drop=next_drop)
+            return self._ln_bwd(*ln1, add=dx1, drop=next_drop)
         if f16:
-            return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1), want_drop=False)
-        return op.ln_bwd(*ln1, add=dx1, accumulate=bool(a1)), None
+            return self._ln_bwd(*ln1, add=dx1, want_drop=False)
+        return self._ln_bwd(*ln1, add=dx1), None
+
+    def _ln_bwd(self, op, dy, x, mean, rstd, gamma_ptr, gw, gb, acc, **kw):
+        """LayerNorm backward of a GPT stage.  While the stage defers its parameter gradients (_ln_defer, set by _stage_bwd),
+        dgamma / dbeta stay as row-block partials in this LayerNorm's slice of the stage's buffer and a descriptor is noted
+        for the stage's one batched finalize; otherwise they are reduced by a launch of their own right here."""
+        d = self._ln_defer
+        if d is None:
+            return op.ln_bwd(dy, x, mean, rstd, gamma_ptr, gw, gb, self._ws, accumulate=bool(acc), **kw)
+        buf, items = d
+        M, C = x.shape
+        nb = ops.layernorm_partial_bytes(M, C)
+        ptr = buf.data_ptr() + len(items) * nb
+        assert (len(items) + 1) * nb <= buf.numel() * 4
+        items.append((ptr, M, C, gw, gb, acc))
+        return op.ln_bwd(dy, x, mean, rstd, gamma_ptr, gw, gb, self._ws, partial=(ptr, nb), **kw)
 
     def _stage_bwd(self, wk, rec, dfeats_out, dgps_tok, B):
         """rec: the stage's _StageRec; dfeats_out: grads of the 3 post-fusion maps; dgps_tok: (tensor, bcast) grad of the
@@ -1236,7 +1262,11 @@ class TransFuser(nn.Module):
         dxo = torch.empty((B * T, C), dtype=F32, device=self.device)
         for m in range(3):
             assert dfeats_out[m].shape == tuple(fshapes[m])
-            ops.upsample_add_bwd(dfeats_out[m], dxo, fps[m], offs[m], T)
+        if self.group_stage_glue:
+            ops.upsample_add_bwd3(dfeats_out, dxo, fps, offs, T)
+        else:
+            for m in range(3):
+                ops.upsample_add_bwd(dfeats_out[m], dxo, fps[m], offs[m], T)
         gsrc, bcast = dgps_tok
         L.gps_rows(gsrc.data_ptr(), dxo.data_ptr(), B, C, T, 1, 0, int(bcast), st)
         gfw, af = wk.g(gpt.ln_f.weight)
@@ -1244,19 +1274,30 @@ class TransFuser(nn.Module):
         rev = list(zip(reversed(list(gpt.blocks)), reversed(rec.blocks)))
         # (resid_pdrop, seed, fc2-branch mask offset) of each block, in backward order; None below the last
         drops = [(bc.pr, self._seed, bc.off_m) for _, bc in rev] + [None]
-        dx, dz = _OPS[wk.dtype].ln_bwd(dxo, rec.x_last, rec.mf, rec.rf, wk.w(gpt.ln_f.weight), gfw, gfb, self._ws,
-                                       accumulate=bool(af), drop=drops[0])
-        for i, (blk, bc) in enumerate(rev):
-            dx, dz = self._gpt_block_bwd(wk, blk, bc, dx, B, T, dz2=dz, next_drop=drops[i + 1])
+        if self.defer_ln_finalize:   # one partial buffer for the stage's LayerNorms (ln_f and two per block), one finalize
+            n_ln = 2 * len(rev) + 1
+            self._ln_defer = (torch.empty(n_ln * ops.layernorm_partial_bytes(B * T, C) // 4, dtype=F32, device=self.device), [])
+        try:
+            dx, dz = self._ln_bwd(_OPS[wk.dtype], dxo, rec.x_last, rec.mf, rec.rf, wk.w(gpt.ln_f.weight), gfw, gfb, af,
+                                  drop=drops[0])
+            for i, (blk, bc) in enumerate(rev):
+                dx, dz = self._gpt_block_bwd(wk, blk, bc, dx, B, T, dz2=dz, next_drop=drops[i + 1])
+            if self._ln_defer is not None:   # before the join and the stage's milestone: the gradients are final there
+                items = self._ln_defer[1]
+                for i in range(0, len(items), ops.LN_FINALIZE_MAX):
+                    ops.layernorm_finalize_batched(items[i:i + ops.LN_FINALIZE_MAX])
+        finally:
+            self._ln_defer = None
         self._wg_join()
         dpre = ops.dropout(dx, rec.pe, self._seed, rec.off_e) if rec.pe > 0 else dx
         gpos, apos = wk.g(gpt.pos_emb)
         L.batch_sum(dpre.data_ptr(), gpos, T * C, B, T * C, apos, st)
-        dfeats = []
-        for m in range(3):
-            d = torch.empty(tuple(fshapes[m]), dtype=dfeats_out[m].dtype, device=self.device)
-            ops.avgpool_tokens_bwd(dpre, dfeats_out[m], d, fps[m], offs[m], T)
-            dfeats.append(d)
+        dfeats = [torch.empty(tuple(fshapes[m]), dtype=dfeats_out[m].dtype, device=self.device) for m in range(3)]
+        if self.group_stage_glue:
+            ops.avgpool_tokens_bwd3(dpre, dfeats_out, dfeats, fps, offs, T)
+        else:
+            for m in range(3):
+                ops.avgpool_tokens_bwd(dpre, dfeats_out[m], dfeats[m], fps[m], offs[m], T)
         dgemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
         L.gps_rows(dpre.data_ptr(), dgemb.data_ptr(), B, C, T, 0, 0, 0, st)
         _, gptr, rpg, gstride, K = rec.gps_src

@@ -6,6 +6,8 @@ on the host because an out-of-bounds kernel can take the whole GPU node down.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from ._lib import lib
@@ -309,8 +311,10 @@ def layernorm_fwd(x, gamma_ptr, beta_ptr, eps=1e-5):
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma_ptr, dgamma_ptr, dbeta_ptr, ws: Workspace, add=None, accumulate=False,
-                  out=None, drop=None):
-    """-> dx, or (dx, dropout(dx)) when drop = (p, seed, seed_off) with p > 0 (fused second output)"""
+                  out=None, drop=None, partial=None):
+    """-> dx, or (dx, dropout(dx)) when drop = (p, seed, seed_off) with p > 0 (fused second output).  partial = (ptr, nbytes)
+    of the caller's own buffer: the deferred form - dgamma / dbeta are left as row-block partials there for
+    layernorm_finalize_batched (dgamma_ptr, dbeta_ptr, accumulate and ws are not used)"""
     M, C = x.shape
     _chk(dy, M, C)
     _chk(x)
@@ -319,9 +323,41 @@ def layernorm_bwd(dy, x, mean, rstd, gamma_ptr, dgamma_ptr, dbeta_ptr, ws: Works
         _chk(add, M, C)
     dxd = torch.empty_like(x) if (drop is not None and drop[0] > 0) else None
     p, seed, off = drop if dxd is not None else (0.0, 0, 0)
+    if partial is not None:
+        lib().layernorm_bwd_partial(_p(dy), _p(x), _p(mean), _p(rstd), gamma_ptr, _p(add), _p(dx), M, C, _p(dxd), float(p),
+                                    seed, off, partial[0], partial[1], _stream())
+        return dx if drop is None else (dx, dxd if dxd is not None else dx)
     lib().layernorm_bwd(_p(dy), _p(x), _p(mean), _p(rstd), gamma_ptr, _p(add), _p(dx), dgamma_ptr, dbeta_ptr, M, C,
                         int(accumulate), _p(dxd), float(p), seed, off, ws.ptr, ws.nbytes, _stream())
     return dx if drop is None else (dx, dxd if dxd is not None else dx)
+
+
+LN_BWD_ROWS = 16          # rows per row-block partial of the LayerNorm backward (csrc/norm.hip)
+LN_FINALIZE_MAX = 24      # DS6G_LN_FINALIZE_MAX of include/ds6g.h
+
+
+class _LnFinalizeDesc(ctypes.Structure):   # ds6g_ln_finalize_desc
+    _fields_ = [("partial", ctypes.c_void_p), ("nblk", ctypes.c_int), ("C", ctypes.c_int), ("dgamma", ctypes.c_void_p),
+                ("dbeta", ctypes.c_void_p), ("accumulate", ctypes.c_int)]
+
+
+class _MapDesc(ctypes.Structure):          # ds6g_map_desc
+    _fields_ = [("inp", ctypes.c_void_p), ("out", ctypes.c_void_p), ("frames_per_sample", ctypes.c_int),
+                ("mod_off", ctypes.c_int)]
+
+
+def layernorm_partial_bytes(M, C):
+    return -(-M // LN_BWD_ROWS) * 2 * C * 4
+
+
+def layernorm_finalize_batched(items):
+    """items: (partial_ptr, M, C, dgamma_ptr, dbeta_ptr, accumulate) of 1 .. 24 deferred LayerNorm backwards (partial=...):
+    dgamma / dbeta (+)= in one launch, bit-identical to the undeferred layernorm_bwd"""
+    n = len(items)
+    descs = (_LnFinalizeDesc * max(n, 1))()
+    for d, (pp, M, C, gw, gb, acc) in zip(descs, items):
+        d.partial, d.nblk, d.C, d.dgamma, d.dbeta, d.accumulate = pp, -(-M // LN_BWD_ROWS), C, gw, gb, int(bool(acc))
+    lib().layernorm_finalize_batched(ctypes.addressof(descs), n, _stream())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -544,7 +580,7 @@ def layernorm_fwd_bf16(x, gamma_ptr, beta_ptr, eps=1e-5, dtype=BF16):
 
 
 def layernorm_bwd_bf16(dy, x, mean, rstd, gamma_ptr, dgamma_ptr, dbeta_ptr, ws: Workspace, add=None, accumulate=False,
-                       drop=None, want_drop=True, dtype=BF16):
+                       drop=None, want_drop=True, dtype=BF16, partial=None):
     """dy 16-bit (dtype: bf16 / f16) or fp32 -> (dx fp32, dropout(dx) as dtype); drop = (p, seed, seed_off) or None (= plain
     16-bit copy of dx); want_drop False: no second output (-> (dx, None))"""
     M, C = x.shape
@@ -555,6 +591,11 @@ def layernorm_bwd_bf16(dy, x, mean, rstd, gamma_ptr, dgamma_ptr, dbeta_ptr, ws: 
     dx = torch.empty_like(x)
     dxd = torch.empty((M, C), dtype=dtype, device=x.device) if want_drop else None
     p, seed, off = drop if drop is not None else (0.0, 0, 0)
+    if partial is not None:   # deferred dgamma / dbeta: see layernorm_bwd
+        lib().layernorm_bwd_h16_partial(_ST16[dtype], _p(dy), int(dy.dtype != F32), _p(x), _p(mean), _p(rstd), gamma_ptr,
+                                        _p(add), _p(dx), M, C, _p(dxd), float(p), seed, off, partial[0], partial[1],
+                                        _stream())
+        return dx, dxd
     lib().layernorm_bwd_h16(_ST16[dtype], _p(dy), int(dy.dtype != F32), _p(x), _p(mean), _p(rstd), gamma_ptr, _p(add), _p(dx), dgamma_ptr,
                             dbeta_ptr, M, C, int(accumulate), _p(dxd), float(p), seed, off, ws.ptr, ws.nbytes, _stream())
     return dx, dxd
@@ -823,6 +864,59 @@ def upsample_add_bwd(dout, dtok, frames_per_sample, mod_off, T):
     assert dtok.numel() == N // frames_per_sample * T * C, (tuple(dtok.shape), N, frames_per_sample, T, C)
     _launch(lib().upsample_add_bwd, lib().h16_upsample_add_bwd, dout.dtype, _p(dout), _p(dtok), N, H, C, frames_per_sample,
             mod_off, T)
+
+
+def _map_group(ins, outs, fps, offs, ntok, T, C, dtype):
+    """the descriptor array of a grouped glue launch over the three modality maps of a stage -> (descs, st, B, H)"""
+    assert len(ins) == len(fps) == len(offs) == 3 and (outs is None or len(outs) == 3)
+    ref = ins[0] if ins[0] is not None else outs[0]
+    _, H, _, _ = ref.shape
+    assert ref.shape[0] % fps[0] == 0 and ntok % (T * C) == 0
+    B = ref.shape[0] // fps[0]
+    assert ntok == B * T * C, (ntok, B, T, C)
+    descs = (_MapDesc * 3)()
+    for m in range(3):
+        for t in (ins[m], outs[m] if outs is not None else None):
+            if t is not None:
+                _chkmap(t, B * fps[m], H, H, C, dtype=dtype)
+        assert 0 <= offs[m] and offs[m] + fps[m] * 64 <= T, (offs[m], fps[m], T)
+        descs[m].inp, descs[m].out = _p(ins[m]), _p(outs[m]) if outs is not None else 0
+        descs[m].frames_per_sample, descs[m].mod_off = fps[m], offs[m]
+    return descs, (0 if dtype == F32 else _ST16[dtype]), B, H
+
+
+def avgpool_tokens_fwd3(feats, pos_emb_ptr, tokens, fps, offs, T, drop_p=0.0, seed=0, seed_off=0):
+    """avgpool_tokens_fwd of the three modality maps feats (frames per sample fps[m], first token row offs[m]) in one launch"""
+    C = feats[0].shape[3]
+    _chk(tokens)
+    descs, st, B, H = _map_group(feats, None, fps, offs, tokens.numel(), T, C, feats[0].dtype)
+    lib().avgpool_tokens_fwd3(st, ctypes.addressof(descs), pos_emb_ptr, _p(tokens), B, H, C, T, float(drop_p), seed, seed_off,
+                              _stream())
+
+
+def avgpool_tokens_bwd3(dtok, dfeats_in, dfeats, fps, offs, T):
+    """avgpool_tokens_bwd of the three modality maps in one launch"""
+    C = dfeats[0].shape[3]
+    _chk(dtok)
+    descs, st, B, H = _map_group(dfeats_in, dfeats, fps, offs, dtok.numel(), T, C, dfeats[0].dtype)
+    lib().avgpool_tokens_bwd3(st, ctypes.addressof(descs), _p(dtok), B, H, C, T, _stream())
+
+
+def upsample_add_fwd3(feats, tokens, outs, fps, offs, T):
+    """upsample_add_fwd of the three modality maps in one launch"""
+    C = feats[0].shape[3]
+    _chk(tokens)
+    descs, st, B, H = _map_group(feats, outs, fps, offs, tokens.numel(), T, C, feats[0].dtype)
+    lib().upsample_add_fwd3(st, ctypes.addressof(descs), _p(tokens), B, H, C, T, _stream())
+
+
+def upsample_add_bwd3(douts, dtok, fps, offs, T):
+    """upsample_add_bwd of the three modality maps in one launch"""
+    C = douts[0].shape[3]
+    _chk(dtok)
+    descs, st, B, H = _map_group(douts, None, fps, offs, dtok.numel(), T, C, douts[0].dtype)
+    assert 5 * (H // 8) <= 64, H
+    lib().upsample_add_bwd3(st, ctypes.addressof(descs), _p(dtok), B, H, C, T, _stream())
 
 
 def global_pool(feat, pooled):

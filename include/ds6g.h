@@ -22,6 +22,7 @@
 #define DS6G_H
 #include <stddef.h>
 #include <stdint.h>
+#include "ds6g_types.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -46,7 +47,11 @@ int ds6g_last_igemm_variant(void);
  * milliseconds).  Not thread-safe; bench.py only. */
 int ds6g_profile_begin(int max_records);
 int ds6g_profile_end(int* variants, double* flops, float* ms, int cap);
-/* ablation switches for kernel timing experiments (results become wrong); 0 = normal operation */
+/* test instrumentation: the number of slab-sum launches the calling thread's last attention backward made (0: no split; 1: the
+ * dK, dV and dQ slabs reduced by one launch; 2: dK / dV and dQ apart; 3: the two-pass hd = 128 form) */
+int ds6g_last_attention_bwd_slab_sums(void);
+/* ablation switches for kernel timing experiments (results become wrong); 0 = normal operation.  0x08000000 keeps results
+ * bit-identical: the hand-over attention backward reduces its dK / dV slabs and its dQ slabs in two launches, not one. */
 int ds6g_set_debug_flags(int flags);
 /* multi-GPU rehearsal on one GPU: keep `workgroups` (<= 256) workgroups of 256 threads with `lds_bytes` (<= 64 KiB) of LDS
  * each resident for `microseconds` (<= 2 s; every wave leaves on time) on `stream` - a stand-in for the channel workgroups an
@@ -249,6 +254,23 @@ int ds6g_layernorm_bwd_h16(int st16, const void* dy, int dy16, const float* x, c
                            const float* gamma, const float* add, float* dx, float* dgamma, float* dbeta, int M, int C,
                            int accumulate_param_grads, void* dx_drop, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,
                            size_t ws_bytes, void* stream);
+/* Deferred parameter gradients of LayerNorm: dgamma / dbeta feed nothing but the optimizer, so on a serial chain of
+ * LayerNorms (a GPT stage's backward) their reduction need not be launched once per layer.  The *_partial forms of the two
+ * backward entry points write dx (and dx_drop) as usual and leave the row-block partials of dgamma / dbeta in `partial`, the
+ * caller's own buffer of >= ds6g_layernorm_bwd_workspace_bytes(M, C) bytes (less is refused with DS6G_ERR_WORKSPACE);
+ * ds6g_layernorm_finalize_batched then reduces the buffers of 1 .. DS6G_LN_FINALIZE_MAX LayerNorms in ONE launch, with the
+ * arithmetic and summation order of the undeferred entry points (bit-identical dgamma / dbeta).  descs is a host array
+ * read during the call (the descriptors travel in the kernel's arguments: safe under stream capture); nblk =
+ * cdiv(M, 16), C as for ds6g_layernorm_bwd; a count outside 1 .. 24, a null pointer or another C is DS6G_ERR_ARG and
+ * launches nothing. */
+/* ds6g_ln_finalize_desc {partial, nblk, C, dgamma, dbeta, accumulate} and DS6G_LN_FINALIZE_MAX: ds6g_types.h */
+int ds6g_layernorm_bwd_partial(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                               const float* add, float* dx, int M, int C, float* dx_drop, float drop_p, uint64_t seed,
+                               uint64_t seed_off, float* partial, size_t partial_bytes, void* stream);
+int ds6g_layernorm_bwd_h16_partial(int st16, const void* dy, int dy16, const float* x, const float* mean, const float* rstd,
+                                   const float* gamma, const float* add, float* dx, int M, int C, void* dx_drop, float drop_p,
+                                   uint64_t seed, uint64_t seed_off, float* partial, size_t partial_bytes, void* stream);
+int ds6g_layernorm_finalize_batched(const ds6g_ln_finalize_desc* descs, int count, void* stream);
 /* bias gradients: out[c] (+)= sum_r x[r][c] */
 size_t ds6g_colsum_workspace_bytes(long M, int C);
 int ds6g_colsum(const float* x, long M, int C, float* out, int accumulate, void* ws, size_t ws_bytes, void* stream);
@@ -473,6 +495,17 @@ int ds6g_upsample_add_fwd(const float* feat, const float* tokens, float* out, in
                           int frames_per_sample, int mod_off, int T, void* stream);
 int ds6g_upsample_add_bwd(const float* dout, float* dtok, int N, int H, int C, int frames_per_sample, int mod_off,
                           int T, void* stream);
+/* The four kernels above for the THREE modality maps of a fusion stage in one launch each (per element the same
+ * arithmetic and dropout counters as three single-map calls).  st: 0 = fp32 maps, DS6G_ST_BF16 / DS6G_ST_F16 = 16-bit maps;
+ * maps: host array of 3 descriptors, read during the call; map m has B * frames_per_sample frames of H x H x C and its
+ * tokens start at row mod_off of each sample's T.  in / out: feat / - (avgpool_fwd3), dfeat_in (nullable) / dfeat
+ * (avgpool_bwd3), feat / out (upsample_add_fwd3), dout / - (upsample_add_bwd3). */
+/* ds6g_map_desc {in, out, frames_per_sample, mod_off}: ds6g_types.h */
+int ds6g_avgpool_tokens_fwd3(int st, const ds6g_map_desc* maps, const float* pos_emb, float* tokens, int B, int H, int C,
+                             int T, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
+int ds6g_avgpool_tokens_bwd3(int st, const ds6g_map_desc* maps, const float* dtok, int B, int H, int C, int T, void* stream);
+int ds6g_upsample_add_fwd3(int st, const ds6g_map_desc* maps, const float* tokens, int B, int H, int C, int T, void* stream);
+int ds6g_upsample_add_bwd3(int st, const ds6g_map_desc* maps, float* dtok, int B, int H, int C, int T, void* stream);
 /* features.avgpool + flatten + cat + sum(dim=1): model2_seq.py:581-595 */
 int ds6g_global_pool(const float* feat, float* pooled, int N, int C, void* stream);
 int ds6g_head_sum(const float* pooled_img, const float* pooled_lidar, const float* pooled_radar, const float* tokens,
