@@ -1187,116 +1187,288 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
     }
 }
 
+// ---- host: every call is PLANNED first (plan_fwd / plan_bwd: integer arithmetic on the shape, the workspace size and the
+// knobs - no HIP call, no pointer; ds6g_attention_plan shows it to tests), then the plan is RUN (attention_run).  DESIGN.md
+// 3.2 has the table of forms and what selects each.
+
+// everything outside the arguments that a plan depends on, read once per call
+struct AttnKnobs {
+    int percu, handover, fused128, merged_sum;  // ds6g_set_debug_flags (igemm.hip) bits 20-23, 0x01000000, 0x04000000, 0x08000000
+    int bf16;              // ds6g_set_compute_mode: operand mode of the fp32-storage kernels (their BF template value)
+    double split_penalty;  // DS6G_ATTN_SPLIT_PENALTY; < 0 (unset): 0.35 / 4 by operand width, see pick_splits
+    int fused128_h16;      // DS6G_ATTN_FUSED128_BF16 (default 1): 16-bit-stored hd = 128 backward with the fused dK / dV kernel
+};
+AttnKnobs attn_knobs() {
+    static const double pen_env = [] { const char* e = getenv("DS6G_ATTN_SPLIT_PENALTY"); return e ? atof(e) : -1.0; }();
+    static const int fused16 = [] { const char* e = getenv("DS6G_ATTN_FUSED128_BF16"); return e ? atoi(e) : 1; }();
+    return {g_ds6g_attn_percu, g_ds6g_attn_handover, g_ds6g_attn_fused128, g_ds6g_attn_merged_sum, g_ds6g_bf16, pen_env, fused16};
+}
+
 // number of loop splits: fills the chip evenly.  cap = workgroups resident at once (256 CUs x per-CU residency)
 // pen: what one more split costs in loop trips (its share of the merge / slab-sum kernel and of the prologue).  0.35 for the
 // fp32-storage kernels; 4 on the bf16-stored path, where a tile step is 3 - 4x shorter while the merge kernels cost the same
 // (measured: bf16 step 451.9 -> 460.3 samples/s at 4, 459.5 at 8; fp32 184.5 at 0.35, 183.4 at 4).  DS6G_ATTN_SPLIT_PENALTY overrides.
-int pick_splits(long base_blocks, int ntiles, int per_cu, int max_splits, double pen_default = 0.35) {
-    if (g_ds6g_attn_percu > 0) per_cu = g_ds6g_attn_percu;  // timing experiments (ds6g_set_debug_flags bits 20-23)
+int pick_splits(const AttnKnobs& kn, long base_blocks, int ntiles, int per_cu, int max_splits, double pen_default) {
+    if (kn.percu > 0) per_cu = kn.percu;  // timing experiments
     const long cap = 256L * per_cu;
+    const double pen = kn.split_penalty >= 0.0 ? kn.split_penalty : pen_default;
     int best = 1;
     double best_cost = 1e30;
     for (int s = 1; s <= max_splits && s <= ntiles; ++s) {
         const int tps = cdiv(ntiles, s);
         const int eff = cdiv(ntiles, tps);  // splits actually used
         const long rounds = cdiv(base_blocks * eff, cap);
-        static const double pen_env = [] { const char* e = getenv("DS6G_ATTN_SPLIT_PENALTY"); return e ? atof(e) : -1.0; }();
-        const double pen = pen_env >= 0.0 ? pen_env : pen_default;
         const double cost = (double)rounds * tps + pen * eff;  // loop trips per CU slot + a merge/prologue penalty
         if (cost < best_cost - 1e-9) { best_cost = cost; best = s; }
     }
     return best;
 }
 
-template <int KIND, int BF>
-int launch_hd_bf(const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
-#define ATTN_CASE(HDV)                                                                                        \
-    case HDV:                                                                                                 \
-        if (KIND == 0) hipLaunchKernelGGL((attn_fwd_kernel<HDV, BF>), grid, dim3(256), 0, st, p);             \
-        if (KIND == 1) hipLaunchKernelGGL((attn_bwd_dq_kernel<HDV, BF>), grid, dim3(256), 0, st, p);          \
-        if (KIND == 2) {                                                                                      \
-            if (HDV >= 128) {                                                                                 \
-                hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 1, BF>), grid, dim3(256), 0, st, p);             \
-                hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 2, BF>), grid, dim3(256), 0, st, p);             \
-            } else {                                                                                          \
-                hipLaunchKernelGGL((attn_bwd_dkv_kernel<(HDV >= 128 ? 64 : HDV), 0, BF>), grid, dim3(256), 0, st, p); \
-            }                                                                                                 \
-        }                                                                                                     \
-        if (KIND == 3) {                                                                                      \
-            if (HDV >= 128) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 2, BF, 1>), grid, dim3(256), 0, st, p); \
-            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<(HDV >= 128 ? 64 : HDV), 0, BF, 1>), grid, dim3(256), 0, st, p); \
-        }                                                                                                     \
-        if (KIND == 4) hipLaunchKernelGGL((attn_bwd_dv2_kernel<(HDV >= 128 ? HDV : 128), BF>), grid, dim3(256), 0, st, p); \
-        if (KIND == 5) hipLaunchKernelGGL((attn_bwd_dq2_kernel<HDV, BF>), grid, dim3(256), 0, st, p);         \
-        if (KIND == 6) hipLaunchKernelGGL((attn_bwd_dkv_kernel<(BF == 0 ? HDV : 16), 0, (BF == 0 ? 0 : BF), 1>), grid, dim3(256), 0, st, p); \
-        break;
-    switch (hd) {
-        ATTN_CASE(16)
-        ATTN_CASE(32)
-        ATTN_CASE(64)
-        ATTN_CASE(128)
-        default:
-            fprintf(stderr, "[ds6g] attention head dim %d not supported (16/32/64/128)\n", hd);
-            return DS6G_ERR_ARG;
+// the shape of one call and the sizes (bytes) that follow from it: a slab of B*T*ld floats, the hand-over tiles
+struct AttnShape {
+    int kind, B, T, nh, hd, ld;
+    size_t slab, hand;
+    AttnShape(int kind, int B, int T, int nh, int hd, int ld) : kind(kind), B(B), T(T), nh(nh), hd(hd), ld(ld) {
+        const size_t nkg = (size_t)cdiv(T, 128) * 4;
+        slab = (size_t)B * T * ld * sizeof(float);
+        hand = (size_t)B * nh * nkg * nkg * 1024 * sizeof(float) * (hd >= 128 ? 2 : 1);
     }
-#undef ATTN_CASE
-    DS6G_LAUNCH_CHECK();
+    size_t ml() const { return (size_t)B * nh * T * 2 * sizeof(float); }   // one split's (max, sum) pairs of the forward
+    size_t full_workspace() const { return 16 * slab + 8 * ml() + hand; }  // ds6g_attention_workspace_bytes
+};
+
+// one kernel step, its loop split as far as pick_splits likes and the room for `each` bytes per split allows (8 at the most)
+ds6g_attn_step kernel_step(const AttnKnobs& kn, const AttnShape& s, int family, int per_cu, size_t room, size_t each) {
+    const size_t cap = each ? room / each : 0;
+    const int ntiles = cdiv(s.T, 32);
+    const int splits = pick_splits(kn, (long)cdiv(s.T, 128) * s.nh * s.B, ntiles, per_cu, (int)(cap < 8 ? cap : 8),
+                                   s.kind == DS6G_ATTN_KIND_H16 ? 4.0 : 0.35);
+    ds6g_attn_step st{};
+    st.family = family;
+    st.tiles_per_split = cdiv(ntiles, splits);
+    st.splits = cdiv(ntiles, st.tiles_per_split);
+    return st;
+}
+ds6g_attn_step* push(ds6g_attn_plan* pl, const ds6g_attn_step& st) { return &(pl->steps[pl->nsteps++] = st); }
+// `tensor` of a kernel step: the caller's when the step is not split, else one slab of `each` bytes per split from ws + off
+void add_out(ds6g_attn_step* st, int tensor, size_t off, size_t each) {
+    ds6g_attn_out& o = st->out[st->nout++];
+    o.tensor = tensor;
+    if (st->splits > 1) { o.slabs = st->splits; o.off = off; o.bytes = st->splits * each; }
+}
+// the step that reduces the slabs kernel step `a` (and `b`) left in the workspace; none where nothing was split
+void add_reduce(ds6g_attn_plan* pl, int family, const ds6g_attn_step* a, const ds6g_attn_step* b = nullptr) {
+    ds6g_attn_step r{};
+    r.family = family;
+    for (const ds6g_attn_step* k : {a, b})
+        for (int i = 0; k && i < k->nout; ++i)
+            if (k->splits > 1 && k->out[i].tensor <= DS6G_ATTN_T_DV) r.out[r.nout++] = k->out[i];
+    if (!r.nout) return;
+    pl->slab_sums += family == DS6G_ATTN_SLAB_SUM;
+    push(pl, r);
+}
+
+void plan_fwd(const AttnShape& s, size_t ws_bytes, const AttnKnobs& kn, ds6g_attn_plan* pl) {
+    *pl = ds6g_attn_plan{};
+    pl->form = DS6G_ATTN_FORM_FWD;
+    // per_cu 3: measured (tools/bench_attn.py, debug-flag bits 20-23), best or tied for every head dim
+    ds6g_attn_step* f = push(pl, kernel_step(kn, s, DS6G_ATTN_FWD, 3, ws_bytes, s.slab + s.ml()));
+    add_out(f, DS6G_ATTN_T_O, 0, s.slab);
+    if (f->splits > 1) add_out(f, DS6G_ATTN_T_ML, f->splits * s.slab, s.ml());
+    add_reduce(pl, DS6G_ATTN_FWD_MERGE, f);
+}
+
+// -> DS6G_OK and the plan, or the refusal of the entry point
+int plan_bwd(const AttnShape& s, size_t ws_bytes, const AttnKnobs& kn, ds6g_attn_plan* pl) {
+    *pl = ds6g_attn_plan{};
+    const bool out16 = s.kind != DS6G_ATTN_KIND_F32, st16 = s.kind == DS6G_ATTN_KIND_H16;
+    const int hd = s.hd;
+    // workgroups resident per CU (register budget of each instantiation): hd 128 -> 1, 64 -> 2, <= 32 -> 3
+    const int cu_kv = hd >= 128 ? 1 : (hd >= 64 ? 2 : 3), cu_q = hd >= 64 ? 2 : 3;
+    // 16-bit storage has the hand-over forms only (the recomputing dQ kernel reads a fp32 o) and takes the size the query
+    // states, nothing less: one number for the caller to go by; fp32 takes any size (fewer splits, or recomputation)
+    if (out16 && ws_bytes < s.full_workspace()) return DS6G_ERR_WORKSPACE;
+    if (!kn.handover || ws_bytes < s.hand + 2 * s.slab) {
+        if (out16) return DS6G_ERR_ARG;
+        pl->form = DS6G_ATTN_FORM_RECOMPUTE;   // dQ split over keys, then dK / dV split over queries; slabs from ws + 0 each time
+        ds6g_attn_step* q = push(pl, kernel_step(kn, s, DS6G_ATTN_DQ_RECOMPUTE, cu_kv, ws_bytes, s.slab));
+        add_out(q, DS6G_ATTN_T_DQ, 0, s.slab);
+        add_reduce(pl, DS6G_ATTN_SLAB_SUM, q);
+        ds6g_attn_step* kv = push(pl, kernel_step(kn, s, DS6G_ATTN_DKV_RECOMPUTE, cu_kv, ws_bytes, 2 * s.slab));
+        add_out(kv, DS6G_ATTN_T_DK, 0, s.slab);
+        add_out(kv, DS6G_ATTN_T_DV, kv->splits * s.slab, s.slab);
+        add_reduce(pl, DS6G_ATTN_SLAB_SUM, kv);
+        return DS6G_OK;
+    }
+    // hand-over: delta -> dK(/dV) kernel that also writes its dS (and P) tiles -> [dV from P] -> dQ from dS
+    const size_t hand = pl->handover_bytes = s.hand, room = ws_bytes - hand;
+    const bool fused128 = hd >= 128 && kn.fused128 && (st16 ? kn.fused128_h16 != 0 : !kn.bf16);
+    const bool two_pass = hd >= 128 && !fused128;
+    pl->form = fused128 ? DS6G_ATTN_FORM_HANDOVER_FUSED128 : (two_pass ? DS6G_ATTN_FORM_HANDOVER_TWO_PASS : DS6G_ATTN_FORM_HANDOVER);
+    add_out(push(pl, {DS6G_ATTN_DELTA}), DS6G_ATTN_T_DELTA, 0, 0);
+    const int kv_family = fused128 ? DS6G_ATTN_DKV_FUSED128 : (two_pass ? DS6G_ATTN_DK_TWO_PASS : DS6G_ATTN_DKV_HANDOVER);
+    ds6g_attn_step* kv = push(pl, kernel_step(kn, s, kv_family, cu_kv, room, (two_pass ? 1 : 2) * s.slab));
+    add_out(kv, DS6G_ATTN_T_DK, hand, s.slab);
+    if (!two_pass) add_out(kv, DS6G_ATTN_T_DV, hand + kv->splits * s.slab, s.slab);
+    kv->out[kv->nout++] = {DS6G_ATTN_T_HS, 1, 0, hd >= 128 ? hand / 2 : hand};
+    if (two_pass) kv->out[kv->nout++] = {DS6G_ATTN_T_HP, 1, hand / 2, hand / 2};
+    // one sum after the dQ kernel where both kernels are split and the dQ slabs fit BEHIND the dK and dV slabs
+    ds6g_attn_step q = kernel_step(kn, s, DS6G_ATTN_DQ_FROM_DS, cu_q, room, s.slab);
+    pl->merged_sum = !two_pass && kn.merged_sum && kv->splits > 1 && q.splits > 1 && (2 * kv->splits + q.splits) * s.slab <= room;
+    if (!pl->merged_sum) add_reduce(pl, DS6G_ATTN_SLAB_SUM, kv);
+    if (two_pass) {
+        ds6g_attn_step* v = push(pl, kernel_step(kn, s, DS6G_ATTN_DV_FROM_P, 2, room, s.slab));
+        add_out(v, DS6G_ATTN_T_DV, hand, s.slab);
+        add_reduce(pl, DS6G_ATTN_SLAB_SUM, v);
+    }
+    add_out(&q, DS6G_ATTN_T_DQ, hand + (pl->merged_sum ? 2 * kv->splits * s.slab : 0), s.slab);
+    const ds6g_attn_step* qs = push(pl, q);
+    add_reduce(pl, DS6G_ATTN_SLAB_SUM, pl->merged_sum ? kv : qs, pl->merged_sum ? qs : nullptr);
     return DS6G_OK;
 }
 
-// 16-bit stored q / k / v / dO (BF >= 4): forward, dK/dV with hand-over, dV from P (HD = 128), dQ from dS
-template <int KIND, int BF>
-int launch_hd_st(const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
-#define ATTN_CASE16(HDV)                                                                                      \
-    case HDV:                                                                                                 \
-        if constexpr (KIND == 0) hipLaunchKernelGGL((attn_fwd_kernel<HDV, BF>), grid, dim3(256), 0, st, p);    \
-        if constexpr (KIND == 3) {                                                                            \
-            if constexpr (HDV >= 128) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 2, BF, 1>), grid, dim3(256), 0, st, p); \
-            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 0, BF, 1>), grid, dim3(256), 0, st, p);          \
-        }                                                                                                     \
-        if constexpr (KIND == 4 && HDV >= 128) hipLaunchKernelGGL((attn_bwd_dv2_kernel<HDV, BF>), grid, dim3(256), 0, st, p); \
-        if constexpr (KIND == 5) hipLaunchKernelGGL((attn_bwd_dq2_kernel<HDV, BF>), grid, dim3(256), 0, st, p); \
-        if constexpr (KIND == 6 && HDV >= 128) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 0, BF, 1>), grid, dim3(256), 0, st, p); \
-        break;
-    switch (hd) {
-        ATTN_CASE16(16)
-        ATTN_CASE16(32)
-        ATTN_CASE16(64)
-        ATTN_CASE16(128)
-        default:
-            fprintf(stderr, "[ds6g] attention head dim %d not supported (16/32/64/128)\n", hd);
-            return DS6G_ERR_ARG;
+// the launch table: family KIND at head dim HD with operand mode BF (0 exact fp32, 1 - 3 the operand-rounding modes of
+// ds6g_set_compute_mode, 4 / 5 bf16 / f16 STORED q / k / v / dO).  What the planner never asks for - a recomputing kernel on
+// 16-bit storage, a hd = 128 kernel at another head dim, the fused kernel in a rounding mode - is DS6G_ERR_ARG and
+// instantiates nothing.
+template <int KIND, int BF, int HD>
+int launch_one(const AttnParams& p, dim3 grid, hipStream_t st) {
+    constexpr bool F32_STORED = BF < 4;
+    if constexpr (KIND == DS6G_ATTN_FWD) {
+        hipLaunchKernelGGL((attn_fwd_kernel<HD, BF>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DQ_RECOMPUTE && F32_STORED) {
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, BF>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DKV_RECOMPUTE && F32_STORED && HD < 128) {
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 0, BF>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DKV_RECOMPUTE && F32_STORED) {   // hd = 128: dK and dV apart
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 1, BF>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 2, BF>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DKV_HANDOVER && HD < 128) {
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 0, BF, 1>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DK_TWO_PASS && HD == 128) {
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 2, BF, 1>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DKV_FUSED128 && HD == 128 && (BF == 0 || BF >= 4)) {
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 0, BF, 1>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DV_FROM_P && HD == 128) {
+        hipLaunchKernelGGL((attn_bwd_dv2_kernel<HD, BF>), grid, dim3(256), 0, st, p);
+    } else if constexpr (KIND == DS6G_ATTN_DQ_FROM_DS) {
+        hipLaunchKernelGGL((attn_bwd_dq2_kernel<HD, BF>), grid, dim3(256), 0, st, p);
+    } else {
+        return DS6G_ERR_ARG;
     }
-#undef ATTN_CASE16
-    DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-
-template <int KIND>
+template <int KIND, int BF>
 int launch_hd(const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
-    if (p.in16) {
-        if constexpr (KIND == 0 || KIND == 3 || KIND == 4 || KIND == 5 || KIND == 6) return p.in16 == 2 ? launch_hd_st<KIND, 5>(p, hd, grid, st) : launch_hd_st<KIND, 4>(p, hd, grid, st);
-        else return DS6G_ERR_ARG;
+    switch (hd) {
+        case 16: return launch_one<KIND, BF, 16>(p, grid, st);
+        case 32: return launch_one<KIND, BF, 32>(p, grid, st);
+        case 64: return launch_one<KIND, BF, 64>(p, grid, st);
+        case 128: return launch_one<KIND, BF, 128>(p, grid, st);
     }
-    if (g_ds6g_bf16 == 3) return launch_hd_bf<KIND, 3>(p, hd, grid, st);
-    if (g_ds6g_bf16 == 2) return launch_hd_bf<KIND, 2>(p, hd, grid, st);
-    return g_ds6g_bf16 ? launch_hd_bf<KIND, 1>(p, hd, grid, st) : launch_hd_bf<KIND, 0>(p, hd, grid, st);
+    fprintf(stderr, "[ds6g] attention head dim %d not supported (16/32/64/128)\n", hd);
+    return DS6G_ERR_ARG;
+}
+template <int KIND>
+int launch(int bf, const AttnParams& p, int hd, dim3 grid, hipStream_t st) {
+    static int (*const by_bf[6])(const AttnParams&, int, dim3, hipStream_t) = {launch_hd<KIND, 0>, launch_hd<KIND, 1>, launch_hd<KIND, 2>,
+                                                                               launch_hd<KIND, 3>, launch_hd<KIND, 4>, launch_hd<KIND, 5>};
+    return bf >= 0 && bf < 6 ? by_bf[bf](p, hd, grid, st) : DS6G_ERR_ARG;
+}
+
+// the parameters every kernel of one call shares; the tensors a call writes (and the backward's o / d_o / delta) are the
+// entry point's to add
+AttnParams attn_params(const float* q, const float* k, const float* v, int in16, float* lse, int out16, int B, int T, int nh, int hd,
+                       int ld_qkv, int ld, int ld_out, float drop_p, uint64_t seed, uint64_t seed_off) {
+    AttnParams p{};
+    p.q = q; p.k = k; p.v = v; p.lse = lse; p.T = T; p.nh = nh; p.B = B; p.ld = ld; p.ldq = ld_qkv; p.ldd = ld_out;
+    p.in16 = in16; p.out16 = out16;
+    const size_t esz = in16 ? 2 : 4;
+    p.slab = (size_t)B * T * ld; p.bytes = (unsigned)(p.slab * esz);
+    p.bytes_q = (unsigned)((((size_t)B * T - 1) * ld_qkv + nh * hd) * esz);
+    p.scale = 1.0f / sqrtf((float)hd);
+    ds6g_attn_drop_params(drop_p, &p.thr, &p.dscale); p.seed = seed; p.seed_off = seed_off; p.salt = g_ds6g_salt;
+    p.nkg = cdiv(T, 128) * 4;
+    return p;
+}
+
+// plans the call whose operands `c` holds (o, dq, dk, dv, delta: the CALLER's tensors), then launches the plan's steps in order
+int attention_run(bool backward, const AttnParams& c, int hd, void* ws, size_t ws_bytes, void* stream) {
+    const AttnKnobs kn = attn_knobs();
+    const AttnShape s(c.in16 ? DS6G_ATTN_KIND_H16 : (c.out16 ? DS6G_ATTN_KIND_OUT16 : DS6G_ATTN_KIND_F32), c.B, c.T, c.nh, hd, c.ld);
+    ds6g_attn_plan plan;
+    int rc = DS6G_OK;
+    if (backward) rc = plan_bwd(s, ws ? ws_bytes : 0, kn, &plan);
+    else plan_fwd(s, ws ? ws_bytes : 0, kn, &plan);
+    DS6G_CHECK_WS(rc != DS6G_ERR_WORKSPACE);   // a 16-bit backward below ds6g_attention_workspace_bytes
+    DS6G_CHECK_ARG(rc == DS6G_OK);             // a 16-bit backward with the hand-over forms switched off
+    if (backward) g_attn_bwd_slab_sums = plan.slab_sums;
+
+    static float* AttnParams::* const field[DS6G_ATTN_T_COUNT] = {&AttnParams::o, &AttnParams::ml, &AttnParams::dq, &AttnParams::dk,
+                                                                   &AttnParams::dv, &AttnParams::delta, &AttnParams::hs, &AttnParams::hp};
+    hipStream_t st = (hipStream_t)stream;
+    AttnParams p = c;
+    const int bf = c.in16 ? 3 + c.in16 : kn.bf16;
+    const int cols4 = c.nh * hd / 4;
+    const long n4 = (long)c.B * c.T * cols4;
+    for (int i = 0; i < plan.nsteps; ++i) {
+        const ds6g_attn_step& step = plan.steps[i];
+        const ds6g_attn_out* o = step.out;
+        float *at[3] = {}, *mine[3] = {};   // per out: where its workspace range starts, the caller's tensor
+        for (int j = 0; j < step.nout; ++j) { at[j] = (float*)((char*)ws + o[j].off); mine[j] = c.*field[o[j].tensor]; }
+        if (step.splits) {   // a split kernel: its loop bounds and where it writes
+            p.splits = step.splits; p.tiles_per_split = step.tiles_per_split;
+            for (int j = 0; j < step.nout; ++j) p.*field[o[j].tensor] = o[j].slabs ? at[j] : mine[j];
+        }
+        const dim3 grid(cdiv(c.T, 128), c.nh * step.splits, c.B);
+        switch (step.family) {
+            case DS6G_ATTN_FWD: rc = launch<DS6G_ATTN_FWD>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DQ_RECOMPUTE: rc = launch<DS6G_ATTN_DQ_RECOMPUTE>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DKV_RECOMPUTE: rc = launch<DS6G_ATTN_DKV_RECOMPUTE>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DKV_HANDOVER: rc = launch<DS6G_ATTN_DKV_HANDOVER>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DKV_FUSED128: rc = launch<DS6G_ATTN_DKV_FUSED128>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DK_TWO_PASS: rc = launch<DS6G_ATTN_DK_TWO_PASS>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DV_FROM_P: rc = launch<DS6G_ATTN_DV_FROM_P>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DQ_FROM_DS: rc = launch<DS6G_ATTN_DQ_FROM_DS>(bf, p, hd, grid, st); break;
+            case DS6G_ATTN_DELTA:
+                hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv((long)c.B * c.T * c.nh, 256)), dim3(256), 0, st, c.o, c.d_o, c.delta,
+                                   c.B, c.T, c.nh, hd, c.ld, c.o16 | (c.in16 << 1));
+                break;
+            case DS6G_ATTN_FWD_MERGE:   // out 0: the partial outputs, out 1: their (max, sum) pairs
+                hipLaunchKernelGGL(attn_fwd_merge_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, st, at[0], at[1], c.o, c.lse, c.B, c.T,
+                                   c.nh, hd, c.ld, o[0].slabs, c.slab, c.out16);
+                break;
+            case DS6G_ATTN_SLAB_SUM:    // pairs 0 and 1 (dK and dV) share a split count, pair 2 (dQ behind them) has its own
+                hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), step.nout), dim3(256), 0, st, at[0], mine[0], at[1], mine[1],
+                                   n4, cols4, c.ld, c.ldd, o[0].slabs, c.slab, c.out16, at[2], mine[2], o[2].slabs);
+                break;
+        }
+        if (rc) return rc;
+        DS6G_LAUNCH_CHECK();
+    }
+    return DS6G_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
-// scratch that lets the split paths use up to 8 splits (forward: partial outputs + (m,l); backward: dk + dv slabs)
-static size_t handover_bytes(int B, int T, int nh, int hd) {
-    const size_t nkg = (size_t)cdiv(T, 128) * 4;
-    return (size_t)B * nh * nkg * nkg * 1024 * sizeof(float) * (hd >= 128 ? 2 : 1);
-}
-// ... plus, for the backward, the dS (and at hd = 128 the dropped-P) tiles handed from the dK/dV kernel to the dQ / dV
-// kernels; with less than this the backward falls back to recomputing the scores in every kernel
+// what lets every split path use its 8 splits (forward: partial outputs + (max, sum) pairs; backward: dK + dV slabs) behind
+// the dS (and, hd = 128, dropped-P) tiles of the backward's hand-over forms; with less the fp32 backward recomputes the scores
 size_t ds6g_attention_workspace_bytes(int B, int T, int nh, int hd, int ld) {
-    const size_t slab = (size_t)B * T * ld * sizeof(float);
-    return 2 * 8 * slab + (size_t)8 * B * nh * T * 2 * sizeof(float) + handover_bytes(B, T, nh, hd);
+    return AttnShape(DS6G_ATTN_KIND_F32, B, T, nh, hd, ld).full_workspace();
+}
+
+// test instrumentation: the plan a call with these arguments would run under the process's current compute mode, debug flags
+// and environment, or that call's refusal.  No HIP call is made.
+int ds6g_attention_plan(int backward, int kind, int B, int T, int nh, int hd, int ld, size_t ws_bytes, ds6g_attn_plan* plan) {
+    DS6G_CHECK_ARG(plan && kind >= DS6G_ATTN_KIND_F32 && kind <= DS6G_ATTN_KIND_H16 && B > 0 && T > 0 && nh > 0);
+    DS6G_CHECK_ARG((hd == 16 || hd == 32 || hd == 64 || hd == 128) && ld % 4 == 0 && ld >= nh * hd);
+    DS6G_CHECK_ARG((size_t)B * T * ld * sizeof(float) < OOB_OFF);
+    const AttnShape s(kind, B, T, nh, hd, ld);
+    if (backward) return plan_bwd(s, ws_bytes, attn_knobs(), plan);
+    plan_fwd(s, ws_bytes, attn_knobs(), plan);
+    return DS6G_OK;
 }
 
 // o = dropout(softmax(q k^T / sqrt(hd))) v ; lse[b][h][t] = logsumexp of the scaled scores
@@ -1307,37 +1479,10 @@ static int attention_fwd_impl(const float* q, const float* k, const float* v, in
     DS6G_CHECK_ARG(q && k && v && o && lse && B > 0 && T > 0 && ld % 4 == 0 && ld >= nh * hd);
     DS6G_CHECK_ARG(ld_qkv % 4 == 0 && ld_qkv >= nh * hd && (size_t)B * T * ld_qkv * sizeof(float) < OOB_OFF);
     DS6G_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
-    const size_t slab = (size_t)B * T * ld;
-    DS6G_CHECK_ARG(slab * sizeof(float) < OOB_OFF);
-    hipStream_t st = (hipStream_t)stream;
-    AttnParams p{};
-    p.q = q; p.k = k; p.v = v; p.lse = lse; p.T = T; p.nh = nh; p.B = B; p.ld = ld; p.ldq = ld_qkv; p.ldd = ld;
-    const size_t esz = in16 ? 2 : 4;
-    p.in16 = in16;
-    p.bytes = (unsigned)(slab * esz); p.slab = slab;
-    p.bytes_q = (unsigned)((((size_t)B * T - 1) * ld_qkv + nh * hd) * esz);
-    p.scale = 1.0f / sqrtf((float)hd);
-    ds6g_attn_drop_params(drop_p, &p.thr, &p.dscale); p.seed = seed; p.seed_off = seed_off; p.salt = g_ds6g_salt;
-    const int ntiles = cdiv(T, 32);
-    const int qblocks = cdiv(T, 128);
-    const int per_cu = 3;  // measured (tools/bench_attn.py, DBG bits 20-23): 3 is best or tied for every head dim
-    const size_t max_by_ws = ws ? ws_bytes / (slab * sizeof(float) + (size_t)B * nh * T * 2 * sizeof(float)) : 1;
-    int splits = pick_splits((long)qblocks * nh * B, ntiles, per_cu, (int)(max_by_ws < 8 ? max_by_ws : 8), in16 ? 4.0 : 0.35);
-    if (splits < 1) splits = 1;
-    p.tiles_per_split = cdiv(ntiles, splits);
-    splits = cdiv(ntiles, p.tiles_per_split);
-    p.splits = splits;
-    float* part = (float*)ws;
-    p.out16 = out16;
-    p.o = splits == 1 ? o : part;
-    p.ml = splits == 1 ? nullptr : part + (size_t)splits * slab;
-    int rc = launch_hd<0>(p, hd, dim3(qblocks, nh * splits, B), st);
-    if (rc || splits == 1) return rc;
-    const long n = (long)B * T * (nh * hd / 4);
-    hipLaunchKernelGGL(attn_fwd_merge_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, part, p.ml, o, lse, B, T, nh, hd, ld,
-                       splits, slab, out16);
-    DS6G_LAUNCH_CHECK();
-    return DS6G_OK;
+    DS6G_CHECK_ARG((size_t)B * T * ld * sizeof(float) < OOB_OFF);
+    AttnParams c = attn_params(q, k, v, in16, lse, out16, B, T, nh, hd, ld_qkv, ld, ld, drop_p, seed, seed_off);
+    c.o = o;
+    return attention_run(false, c, hd, ws, ws_bytes, stream);
 }
 
 int ds6g_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int T, int nh,
@@ -1374,151 +1519,10 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
     DS6G_CHECK_ARG(q && k && v && o && d_o && lse && delta && dq && dk && dv && ld % 4 == 0 && ld >= nh * hd);
     DS6G_CHECK_ARG(ld_qkv % 4 == 0 && ld_qkv >= nh * hd && (size_t)B * T * ld_qkv * sizeof(float) < OOB_OFF);
     DS6G_CHECK_ARG(ld_dqkv % 4 == 0 && ld_dqkv >= nh * hd);
-    const size_t slab = (size_t)B * T * ld;
-    DS6G_CHECK_ARG(slab * sizeof(float) < OOB_OFF);
-    hipStream_t st = (hipStream_t)stream;
-    AttnParams p{};
-    p.q = q; p.k = k; p.v = v; p.o = const_cast<float*>(o); p.lse = const_cast<float*>(lse); p.d_o = d_o;
-    p.delta = delta; p.T = T; p.nh = nh; p.B = B; p.ld = ld; p.ldq = ld_qkv; p.ldd = ld_dqkv;
-    p.out16 = out16; p.o16 = o16; p.in16 = in16;
-    const size_t esz = in16 ? 2 : 4;
-    p.bytes = (unsigned)(slab * esz); p.slab = slab;
-    p.bytes_q = (unsigned)((((size_t)B * T - 1) * ld_qkv + nh * hd) * esz);
-    p.scale = 1.0f / sqrtf((float)hd);
-    ds6g_attn_drop_params(drop_p, &p.thr, &p.dscale); p.seed = seed; p.seed_off = seed_off; p.salt = g_ds6g_salt;
-    const int ntiles = cdiv(T, 32);
-    const int blocks128 = cdiv(T, 128);
-    const int cols4 = nh * hd / 4;
-    const long n4 = (long)B * T * cols4;
-    const size_t hand = handover_bytes(B, T, nh, hd);
-    // 16-bit storage runs the hand-over form only (the recomputing dQ kernel reads a fp32 o): it takes the size the query
-    // states, nothing less, so that the caller has one number to go by; fp32 takes any size (fewer splits, or recomputation)
-    if (o16 || in16) {
-        DS6G_CHECK_WS(ws && ws_bytes >= ds6g_attention_workspace_bytes(B, T, nh, hd, ld));
-    }
-    if (g_ds6g_attn_handover && ws && ws_bytes >= hand + 2 * slab * sizeof(float)) {
-        // ---- hand-over path: delta -> dK(/dV) kernel that also writes its dS (and P) tiles -> [dV from P] -> dQ from dS
-        p.hs = (float*)ws;
-        p.hp = hd >= 128 ? p.hs + hand / sizeof(float) / 2 : nullptr;
-        p.nkg = blocks128 * 4;
-        float* wsf = (float*)((char*)ws + hand);
-        const size_t wsb = ws_bytes - hand;
-        hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv((long)B * T * nh, 256)), dim3(256), 0, st, o, d_o, delta, B, T, nh,
-                           hd, ld, o16 | (in16 << 1));
-        DS6G_LAUNCH_CHECK();
-        auto plan = [&](int per_cu, size_t slabs_per_split) {
-            const size_t cap = wsb / (slabs_per_split * slab * sizeof(float));
-            int splits = pick_splits((long)blocks128 * nh * B, ntiles, per_cu, (int)(cap < 8 ? cap : 8), in16 ? 4.0 : 0.35);
-            if (splits < 1) splits = 1;
-            p.tiles_per_split = cdiv(ntiles, splits);
-            p.splits = cdiv(ntiles, p.tiles_per_split);
-        };
-        // hd = 128, exact fp32: dK and dV in ONE kernel (one wave per SIMD, 512 registers, 37 of them spilled) instead of the
-        // dK kernel + dropped-P tiles through HBM (201 MB per layer) + attn_bwd_dv2_kernel: measured 690 -> 669 us per
-        // backward at B = 12 (ds6g_set_debug_flags 0x04000000 restores the two-kernel form; the operand-rounding bf16 modes keep
-        // it).  bf16-STORED tiles (round 4): K / V fragments are packed bf16, the fused kernel needs 484 registers and no spill -
-        // bf16 step 431 -> 439 samples/s (DS6G_ATTN_FUSED128_BF16=0: the two-kernel form)
-        static const int fused16 = [] { const char* e = getenv("DS6G_ATTN_FUSED128_BF16"); return e ? atoi(e) : 1; }();
-        const bool fused128 = hd >= 128 && g_ds6g_attn_fused128 && (in16 ? fused16 != 0 : !g_ds6g_bf16);
-        const bool two_pass = hd >= 128 && !fused128;
-        plan(hd >= 128 ? 1 : (hd >= 64 ? 2 : 3), two_pass ? 1 : 2);
-        p.dk = p.splits == 1 ? dk : wsf;
-        p.dv = p.splits == 1 ? dv : wsf + (size_t)p.splits * slab;
-        int rc = fused128 ? launch_hd<6>(p, hd, dim3(blocks128, nh * p.splits, B), st)
-                          : launch_hd<3>(p, hd, dim3(blocks128, nh * p.splits, B), st);
-        if (rc) return rc;
-        // The dK / dV sum feeds nothing before the projection gradients that follow the whole backward, so where the dQ
-        // kernel is split too and its slabs fit BEHIND the dK and dV slabs (at the split counts of the two-launch form, never fewer:
-        // the workspace query does not grow, and the result stays bit-identical to that form), the sum waits
-        // and one launch after attn_bwd_dq2 reduces all three: one launch less on the GPT stage's serial chain
-        const int splits_kv = p.splits;
-        bool merged = false;
-        if (!two_pass && splits_kv > 1 && g_ds6g_attn_merged_sum) {
-            plan(hd >= 64 ? 2 : 3, 1);
-            merged = p.splits > 1 && (size_t)(2 * splits_kv + p.splits) * slab * sizeof(float) <= wsb;
-        }
-        if (merged) {
-            float* wsq = wsf + (size_t)2 * splits_kv * slab;
-            p.dq = wsq;
-            rc = launch_hd<5>(p, hd, dim3(blocks128, nh * p.splits, B), st);
-            if (rc) return rc;
-            ++g_attn_bwd_slab_sums;
-            hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 3), dim3(256), 0, st, (const float*)wsf, dk,
-                               (const float*)(wsf + (size_t)splits_kv * slab), dv, n4, cols4, ld, ld_dqkv, splits_kv, slab, out16,
-                               (const float*)wsq, dq, p.splits);
-            DS6G_LAUNCH_CHECK();
-            return DS6G_OK;
-        }
-        if (splits_kv > 1) {
-            ++g_attn_bwd_slab_sums;
-            hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), two_pass ? 1 : 2), dim3(256), 0, st, (const float*)wsf, dk,
-                               (const float*)(wsf + (size_t)splits_kv * slab), dv, n4, cols4, ld, ld_dqkv, splits_kv, slab, out16);
-            DS6G_LAUNCH_CHECK();
-        }
-        if (two_pass) {
-            plan(2, 1);
-            p.dv = p.splits == 1 ? dv : wsf;
-            rc = launch_hd<4>(p, hd, dim3(blocks128, nh * p.splits, B), st);
-            if (rc) return rc;
-            if (p.splits > 1) {
-                ++g_attn_bwd_slab_sums;
-                hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 1), dim3(256), 0, st, (const float*)wsf, dv,
-                                   (const float*)nullptr, (float*)nullptr, n4, cols4, ld, ld_dqkv, p.splits, slab, out16);
-                DS6G_LAUNCH_CHECK();
-            }
-        }
-        plan(hd >= 64 ? 2 : 3, 1);
-        p.dq = p.splits == 1 ? dq : wsf;
-        rc = launch_hd<5>(p, hd, dim3(blocks128, nh * p.splits, B), st);
-        if (rc) return rc;
-        if (p.splits > 1) {
-            ++g_attn_bwd_slab_sums;
-            hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 1), dim3(256), 0, st, (const float*)wsf, dq,
-                               (const float*)nullptr, (float*)nullptr, n4, cols4, ld, ld_dqkv, p.splits, slab, out16);
-            DS6G_LAUNCH_CHECK();
-        }
-        return DS6G_OK;
-    }
-    // the recomputing form reads o inside its dQ kernel (fp32 only): the bf16-storage path needs the hand-over workspace
-    DS6G_CHECK_ARG(!o16 && !in16);   // reached by 16-bit storage only with the hand-over form switched off (debug flag)
-    // ---- dQ (split over keys)
-    {
-        const size_t max_by_ws = ws ? ws_bytes / (slab * sizeof(float)) : 1;
-        // workgroups resident per CU (register budget of each instantiation): hd 128 -> 1, 64 -> 2, <= 32 -> 3
-        int splits = pick_splits((long)blocks128 * nh * B, ntiles, hd >= 128 ? 1 : (hd >= 64 ? 2 : 3), (int)(max_by_ws < 8 ? max_by_ws : 8));
-        p.tiles_per_split = cdiv(ntiles, splits);
-        splits = cdiv(ntiles, p.tiles_per_split);
-        p.splits = splits;
-        p.dq = splits == 1 ? dq : (float*)ws;
-        int rc = launch_hd<1>(p, hd, dim3(blocks128, nh * splits, B), st);
-        if (rc) return rc;
-        if (splits > 1) {
-            ++g_attn_bwd_slab_sums;
-            hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 1), dim3(256), 0, st, (const float*)ws, dq,
-                               (const float*)nullptr, (float*)nullptr, n4, cols4, ld, ld_dqkv, splits, slab, out16);
-            DS6G_LAUNCH_CHECK();
-        }
-    }
-    // ---- dK, dV (split over queries)
-    {
-        const size_t max_by_ws = ws ? ws_bytes / (2 * slab * sizeof(float)) : 1;
-        int splits = pick_splits((long)blocks128 * nh * B, ntiles, hd >= 128 ? 1 : (hd >= 64 ? 2 : 3), (int)(max_by_ws < 8 ? max_by_ws : 8));
-        p.tiles_per_split = cdiv(ntiles, splits);
-        splits = cdiv(ntiles, p.tiles_per_split);
-        p.splits = splits;
-        float* wsf = (float*)ws;
-        p.dk = splits == 1 ? dk : wsf;
-        p.dv = splits == 1 ? dv : wsf + (size_t)splits * slab;
-        int rc = launch_hd<2>(p, hd, dim3(blocks128, nh * splits, B), st);
-        if (rc) return rc;
-        if (splits > 1) {
-            ++g_attn_bwd_slab_sums;
-            hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n4, 256), 2), dim3(256), 0, st, (const float*)wsf, dk,
-                               (const float*)(wsf + (size_t)splits * slab), dv, n4, cols4, ld, ld_dqkv, splits, slab, out16);
-            DS6G_LAUNCH_CHECK();
-        }
-    }
-    return DS6G_OK;
+    DS6G_CHECK_ARG((size_t)B * T * ld * sizeof(float) < OOB_OFF);
+    AttnParams c = attn_params(q, k, v, in16, const_cast<float*>(lse), out16, B, T, nh, hd, ld_qkv, ld, ld_dqkv, drop_p, seed, seed_off);
+    c.o = const_cast<float*>(o); c.o16 = o16; c.d_o = d_o; c.delta = delta; c.dq = dq; c.dk = dk; c.dv = dv;
+    return attention_run(true, c, hd, ws, ws_bytes, stream);
 }
 
 // test instrumentation: how many slab_sum_kernel launches the calling thread's last attention backward made (0: nothing was

@@ -50,6 +50,12 @@ int ds6g_profile_end(int* variants, double* flops, float* ms, int cap);
 /* test instrumentation: the number of slab-sum launches the calling thread's last attention backward made (0: no split; 1: the
  * dK, dV and dQ slabs reduced by one launch; 2: dK / dV and dQ apart; 3: the two-pass hd = 128 form) */
 int ds6g_last_attention_bwd_slab_sums(void);
+/* test instrumentation, host arithmetic only (no GPU needed): the launch plan that the attention forward (backward = 0) or
+ * backward of storage `kind` (DS6G_ATTN_KIND_*, ds6g_types.h) would run for this shape and workspace size (0 for a null ws)
+ * under the process's current compute mode, debug flags and environment - the entry points run what this very planner
+ * returns - or the refusal of that call: DS6G_ERR_WORKSPACE where a 16-bit backward gets less than
+ * ds6g_attention_workspace_bytes, DS6G_ERR_ARG where it meets the switched-off hand-over form (or for a bad shape). */
+int ds6g_attention_plan(int backward, int kind, int B, int T, int nh, int hd, int ld, size_t ws_bytes, ds6g_attn_plan* plan);
 /* ablation switches for kernel timing experiments (results become wrong); 0 = normal operation.  0x08000000 keeps results
  * bit-identical: the hand-over attention backward reduces its dK / dV slabs and its dQ slabs in two launches, not one. */
 int ds6g_set_debug_flags(int flags);
@@ -282,7 +288,14 @@ int ds6g_colsum(const float* x, long M, int C, float* out, int accumulate, void*
  * ws: scratch for the split-loop partial results (any size; more allows more splits, see *_workspace_bytes).  With the
  * full *_workspace_bytes the backward hands its dS (and, hd = 128, dropped-P) tiles from the dK/dV kernel to the dQ / dV
  * kernels through ws (5 matrix products); with less it recomputes the scores in every kernel (7-8 products, same results
- * up to summation order). */
+ * up to summation order).
+ * ds6g_attention_workspace_bytes = hand-over tiles + 16 slabs of B*T*ld floats + 8 (max, sum) arrays of the split forward.
+ * It is the size at which every FORM of the backward is available (and the one size the 16-bit backwards accept as a
+ * minimum) - NOT the size at which every split count is: the launch plan goes on depending on ws_bytes beyond it.  The
+ * hand-over backward reduces its dK, dV and dQ slabs in one launch only where all three sets fit side by side behind the
+ * tiles, and at 6 or more splits each those are more than 16 slabs: B = 12, T = 642 takes 7 + 7 + 7, so that call makes
+ * two slab-sum launches at the queried size and one on a larger scratch (the model passes its whole arena).
+ * The split counts of the kernels, and with them the bits of the results, are the same either way. */
 size_t ds6g_attention_workspace_bytes(int B, int T, int nh, int hd, int ld);
 int ds6g_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int T, int nh,
                        int hd, int ld_qkv, int ld, float drop_p, uint64_t seed, uint64_t seed_off, void* ws,

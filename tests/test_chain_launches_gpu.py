@@ -203,6 +203,10 @@ def _attn_bwd(ops, B, T, nh, hd, kind, flags):
     try:
         bwd(q, k, v, o, d_o, lse, B, T, nh, ws, 0.1, 5, 0, out=out)
         sums = int(L.last_attention_bwd_slab_sums())
+        # the planner, asked without a launch (under the same flags), predicts what the call then did
+        from tests.test_attention_plan_cpu import KIND_OF, query_plan
+        rc, plan = query_plan(1, KIND_OF[kind], B, T, nh, hd, need)
+        assert rc == 0 and plan.slab_sums == sums, (rc, plan and plan.slab_sums, sums)
         mo.check()
     finally:
         L.set_debug_flags(0)
