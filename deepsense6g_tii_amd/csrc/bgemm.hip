@@ -19,10 +19,10 @@
 //     segment index is XOR-swizzled by the k row so that the four rows of one transposed read hit different banks;
 //   * a bf16 output tile is rounded once from the fp32 accumulators and leaves through LDS, so that rows are stored as
 //     16-byte pieces instead of 2-byte elements.
-// Only the wave-uniform k walk of igemm.hip exists here (channel counts multiples of 64; wgrad: see bgemm_wgrad_walk):
+// Only the wave-uniform k walk of igemm.hip exists here (channel counts multiples of 64; wgrad: see gemm_wgrad_rows in gemm_plan.h):
 // every layer of the model but the 4-channel stems qualifies, and the stems keep the fp32-storage kernel.
 #include "common.h"
-#include <cstdlib>
+#include "gemm_plan.h"
 
 void* ds6g_prof_open(int variant, double flops, hipStream_t st);
 void ds6g_prof_close(void* rec, hipStream_t st);
@@ -638,128 +638,46 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgemmParams pin) {
     GCLK_END(g_bgemm_clk, g_bgemm_wg);
 }
 
-// ------------------------------------------------------------------------------------------------
-// 128 x 128 tiles once they give this many workgroups, else 64 x 64 (tools/bench_bgemm.py with DS6G_BG_TILE forced: the large
-// tile wins from ~240 workgroups up - 32x32 x 128 ch and 16x16 x 256 ch convs at N = 60 633-677 vs 536-562 TFLOP/s, stage-4 GPT
-// linears +15-20 % - and loses on the 64-wide and the 8x8 x 512 layers, 120 workgroups)
-int g_bg_min_blocks = 200;
-// wgrad split-K: workgroups aimed at (measured sweep 128 .. 4096, tools/bench_bgemm.py with DS6G_BG_WTARGET: few, long splits
-// win - convs peak at ~384, the GPT linears at ~512; 1024 costs 15-25 %, 2048+ up to 2x through the slab reduction)
-int g_bg_wgrad_target = 0;
-int g_bg_force_tile = -1;   // tuning experiments (env DS6G_BG_TILE / DS6G_BG_MINBLOCKS, read once)
-// wgrad (split, tile) -> XCD mapping (env DS6G_BG_WXCD): 0 plain (tiles of each split dealt XCD-contiguously), 1 (default)
-// contiguous (split, tile) runs where they measured faster (tools/bench_bwgrad.py, N = 60: convs with <= 24 output tiles -
-// 64x64x64 75 -> 57 us / 499 -> 72 MB read, 32x32x128 45 -> 35 us / 247 -> 37 MB, the stride-2 layers 31 -> 25 us; the
-// 36 .. 144-tile layers lose 1 - 2 us although their traffic falls 2 - 4x - and the large linears whose workgroup count is a
-// multiple of 8, i.e. whole splits per XCD: fc1 / fc2 / proj of stage 4 44.8 -> 40.2 us, 142 - 213 -> 59 MB), 2 every conv,
-// 3 everything
-int g_bg_wxcd = 1;
-void bg_env() {
-    static bool done = false;
-    if (done) return;
-    done = true;
-    if (const char* e = getenv("DS6G_BG_TILE")) g_bg_force_tile = atoi(e);
-    if (const char* e = getenv("DS6G_BG_MINBLOCKS")) g_bg_min_blocks = atoi(e);
-    if (const char* e = getenv("DS6G_BG_WTARGET")) g_bg_wgrad_target = atoi(e);
-    if (const char* e = getenv("DS6G_BG_WXCD")) g_bg_wxcd = atoi(e);
+// ---- host: every call is planned by gemm_plan.h (shared with igemm.hip; DESIGN.md 3.1 has the rules), then run_bgemm runs the plan
+
+// The instantiation table.  CODE = ((mode * 2 + out16) * 3 + epilogue) * 2 + tile; epilogue 2 exists for the bf16-output forward only
+template <typename T16, int CODE>
+void launch_bgemm(const BgemmParams& p, const GemmPlan& pl, hipStream_t st) {
+    constexpr int TILE = CODE % 2, EPI = CODE / 2 % 3, OUT16 = CODE / 6 % 2, MODE = CODE / 12;
+    constexpr int BT = TILE == 0 ? 128 : 64;
+    if constexpr (EPI < 2 || (MODE == B_FWD && OUT16))
+        hipLaunchKernelGGL((bgemm_kernel<MODE, BT, BT, OUT16, EPI, T16>), dim3(pl.grid_x, pl.grid_y, pl.grid_z), dim3(256), 0, st, p);
 }
 
-void fill_conv(BgemmParams& p, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    p = BgemmParams{};
-    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K; p.R = R; p.S = S; p.stride = stride; p.pad = pad;
-    p.Ho = (H + 2 * pad - R) / stride + 1;
-    p.Wo = (W + 2 * pad - S) / stride + 1;
-    p.drop_scale = 1.f;
-    p.h0 = 0; p.hstep = 1; p.Hs = H; p.w0 = 0; p.wstep = 1; p.Ws = W;
-    p.r0 = 0; p.rstep = 1; p.nr = R; p.s0 = 0; p.sstep = 1; p.ns = S;
-}
-
-// wgrad: the 64 pixels of a k-tile share one (image, output row), or cover whole output rows of one image
-bool bgemm_wgrad_walk(BgemmParams& p) {
-    if (p.Wo % BK == 0 || p.N * p.Ho == 1) { p.wg_rows = 0; return true; }
-    if (BK % p.Wo == 0 && p.Ho % (BK / p.Wo) == 0) { p.wg_rows = BK / p.Wo; return true; }
-    return false;
-}
-
-template <int MODE, int OUT16, int EPI, typename T16>
-int launch_tiles(BgemmParams& p, int splits, int tile, hipStream_t st) {
-    dim3 block(256);
-    const int ny = p.nclass > 1 ? p.nclass : 1;
-    if (tile == 0) {
-        p.tiles_n = cdiv(p.Ng, 128);
-        dim3 grid(cdiv(p.Mg, 128) * p.tiles_n, ny, splits);
-        hipLaunchKernelGGL((bgemm_kernel<MODE, 128, 128, OUT16, EPI, T16>), grid, block, 0, st, p);
-    } else {
-        p.tiles_n = cdiv(p.Ng, 64);
-        dim3 grid(cdiv(p.Mg, 64) * p.tiles_n, ny, splits);
-        hipLaunchKernelGGL((bgemm_kernel<MODE, 64, 64, OUT16, EPI, T16>), grid, block, 0, st, p);
-    }
-    DS6G_LAUNCH_CHECK();
-    return DS6G_OK;
-}
-
-template <int MODE, typename T16>
-int launch_bgemm(BgemmParams& p, int out16, int splits, int tile, hipStream_t st) {
-    if ((size_t)p.Mg * p.Ng * 4 >= OOB_OFF) return DS6G_ERR_ARG;
-    const bool epi = p.bias || p.relu || p.mask_src || p.drop_thr || p.residual;
-    void* rec = ds6g_prof_open(30000 + 100 * out16 + 10 * MODE + tile, 2.0 * p.Mg * p.Ng * p.Kg, st);
-    int rc;
-    if (MODE == B_WGRAD) rc = launch_tiles<MODE, 0, 0, T16>(p, splits, tile, st);
-    else if (out16) rc = epi ? launch_tiles<MODE, 1, 1, T16>(p, splits, tile, st) : launch_tiles<MODE, 1, 0, T16>(p, splits, tile, st);
-    else rc = epi ? launch_tiles<MODE, 0, 1, T16>(p, splits, tile, st) : launch_tiles<MODE, 0, 0, T16>(p, splits, tile, st);
-    ds6g_prof_close(rec, st);
-    return rc;
-}
-
-int pick_tile(int Mg, int Ng, long splits) {
-    bg_env();
-    if (g_bg_force_tile >= 0) return g_bg_force_tile;
-    return ((long)cdiv(Mg, 128) * cdiv(Ng, 128) * splits >= g_bg_min_blocks && Mg > 64 && Ng > 64) ? 0 : 1;
-}
-
+// step 5 of every entry point: launches what the plan says, and the slab reduction into dw (/ dbias) where it says so
 template <typename T16>
-int run_wgrad(BgemmParams& p, float* dw, int accumulate, float* dbias, float* ws, size_t ws_bytes, hipStream_t st) {
-    const long out_elems = (long)p.Mg * p.Ng;
-    DS6G_CHECK_ARG(out_elems % 4 == 0 && p.Mg % 4 == 0);
-    const long slab_elems = out_elems + (dbias ? p.Mg : 0);
-    const int tile = (p.Mg >= 128 && p.Ng >= 128) ? 0 : 1;
-    const long tiles = (long)cdiv(p.Mg, tile == 0 ? 128 : 64) * cdiv(p.Ng, tile == 0 ? 128 : 64);
-    bg_env();
-    const long target = g_bg_wgrad_target > 0 ? g_bg_wgrad_target : (p.N * p.Ho == 1 ? 512 : 384);
-    long splits = (target + tiles - 1) / tiles;
-    const long max_by_k = (p.Kg + 4 * BK - 1) / (4 * BK);   // >= 4 k-tiles per split
-    if (splits > max_by_k) splits = max_by_k;
-    const long max_by_ws = (long)(ws_bytes / (slab_elems * sizeof(float)));
-    if (splits > max_by_ws) splits = max_by_ws;
-    if (splits < 1) splits = 1;
-    const int kps = cdiv(cdiv(p.Kg, splits), BK) * BK;
-    splits = cdiv(p.Kg, kps);
-    p.k_per_split = kps;
-    p.split_stride = (size_t)slab_elems;
-    p.want_colsum = dbias != nullptr;
-    {
-        const bool linear = p.N * p.Ho == 1;
-        const bool pays = linear ? ((tiles * splits) % 8 == 0 && (long)p.Mg * p.Ng >= 512L * 512) : tiles <= 24;
-        p.xcd_splits = (splits >= 2 && ((g_bg_wxcd == 1 && pays) || (g_bg_wxcd == 2 && (!linear || pays)) || g_bg_wxcd >= 3)) ? 1 : 0;
-    }
-    if (splits == 1 && !accumulate && !dbias) {
-        p.out = dw;
-        return launch_bgemm<B_WGRAD, T16>(p, 0, 1, tile, st);
-    }
-    DS6G_CHECK_ARG(ws != nullptr && (size_t)splits * slab_elems * sizeof(float) <= ws_bytes);
-    p.out = ws;
-    const int rc = launch_bgemm<B_WGRAD, T16>(p, 0, (int)splits, tile, st);
-    if (rc) return rc;
-    return ds6g_internal_splitk_reduce(ws, dw, out_elems / 4, dbias, dbias ? p.Mg / 4 : 0, (int)splits, (size_t)slab_elems,
-                                       accumulate, accumulate, st);
+int run_bgemm(const BgemmParams& p, const GemmPlan& pl, float* dw, float* dbias, int accumulate, hipStream_t st) {
+    void* rec = ds6g_prof_open(pl.variant, 2.0 * p.Mg * p.Ng * p.Kg, st);
+    const int code = ((pl.mode * 2 + pl.out16) * 3 + pl.epilogue) * 2 + pl.tile;
+    gemm_dispatch(code, [&](auto c) { launch_bgemm<T16, decltype(c)::value>(p, pl, st); }, std::make_integer_sequence<int, 3 * 2 * 3 * 2>{});
+    ds6g_prof_close(rec, st);
+    DS6G_LAUNCH_CHECK();
+    if (!pl.reduce) return DS6G_OK;
+    return ds6g_internal_splitk_reduce((const float*)p.out, dw, (long)pl.Mg * pl.Ng / 4, dbias, pl.want_colsum ? pl.Mg / 4 : 0,
+                                       pl.splits, pl.slab_elems, accumulate, accumulate, st);
 }
 
-bool sizes_ok(const BgemmParams& p) {
-    const size_t x = (size_t)p.N * p.H * p.W * p.C * 2, y = (size_t)p.N * p.Ho * p.Wo * p.K * 2, w = (size_t)p.K * p.R * p.S * p.C * 2;
-    return x < OOB_OFF && y < OOB_OFF && w < OOB_OFF;
-}
+constexpr int H16F = DS6G_GEMM_H16;
 
 }  // namespace
+
+// the knobs of this family: four environment variables for tuning experiments, read once (also for ds6g_gemm_plan, igemm.hip)
+GemmKnobs ds6g_internal_bgemm_knobs() {
+    static const GemmKnobs knobs = [] {
+        GemmKnobs kn;
+        gemm_env("DS6G_BG_TILE", &kn.h16_tile);
+        gemm_env("DS6G_BG_MINBLOCKS", &kn.h16_min_blocks);
+        gemm_env("DS6G_BG_WTARGET", &kn.h16_wgrad_target);
+        gemm_env("DS6G_BG_WXCD", &kn.h16_wgrad_xcd);
+        return kn;
+    }();
+    return knobs;
+}
 
 extern "C" {
 
@@ -769,14 +687,12 @@ extern "C++" template <typename T16>
 static int h16_conv2d_fwd(const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R, int S,
                          int stride, int pad, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && C % BK == 0 && K % 8 == 0 && N > 0);
-    BgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
-    DS6G_CHECK_ARG(sizes_ok(p));
+    DS6G_CHECK_ARG(x && w && y);
+    const GemmProblem q = {H16F, DS6G_GEMM_CONV_FWD, N, H, W, C, K, R, S, stride, pad, 0, out16 != 0, 0, 0, 0};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
     p.a_src = (const __bf16*)x; p.b_src = (const __bf16*)w; p.out = y;
-    p.a_bytes = (unsigned)((size_t)N * H * W * C * 2); p.b_bytes = (unsigned)((size_t)K * R * S * C * 2);
-    p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
-    return launch_bgemm<B_FWD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
+    return run_bgemm<T16>(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 int ds6g_h16_conv2d_fwd(int st16, const void* x, const void* w, void* y, int out16, int N, int H, int W, int C, int K, int R,
                         int S, int stride, int pad, void* stream) {
@@ -787,27 +703,19 @@ int ds6g_h16_conv2d_fwd(int st16, const void* x, const void* w, void* y, int out
 // statistics updated in place when given) from per-tile column partials written by the conv's epilogue: the statistics are
 // those of the STORED bf16 tensor (what ds6g_h16_bn_stats would compute), without a pass over it.
 // ws: >= ds6g_h16_conv_bnstats_workspace_bytes(N * Ho * Wo, K).
-size_t ds6g_h16_conv_bnstats_workspace_bytes(long M, int K);
 extern "C++" template <typename T16>
 static int h16_conv2d_fwd_bnstats(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R, int S,
                                  int stride, int pad, float eps, float momentum, float* mean, float* invstd,
                                  float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && mean && invstd && ws && C % BK == 0 && K % 8 == 0 && N > 0);
-    BgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
-    DS6G_CHECK_ARG(sizes_ok(p));
+    DS6G_CHECK_ARG(x && w && y && mean && invstd && ws);
+    const GemmProblem q = {H16F, DS6G_GEMM_CONV_FWD_BNSTATS, N, H, W, C, K, R, S, stride, pad, 0, 1, 0, 0, ws_bytes};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
     p.a_src = (const __bf16*)x; p.b_src = (const __bf16*)w; p.out = y;
-    p.a_bytes = (unsigned)((size_t)N * H * W * C * 2); p.b_bytes = (unsigned)((size_t)K * R * S * C * 2);
-    p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
-    const int tile = pick_tile(p.Mg, p.Ng, 1);
-    const int nblk = cdiv(p.Mg, tile == 0 ? 128 : 64);
-    // the size the query states (64-row tiles), also where 128-row tiles need half of it: one contract for the caller
-    DS6G_CHECK_WS(ws_bytes >= ds6g_h16_conv_bnstats_workspace_bytes(p.Mg, K));
     p.bn_partial = (double*)ws;
-    const int rc = launch_bgemm<B_FWD, T16>(p, 1, 1, tile, (hipStream_t)stream);
-    if (rc) return rc;
-    return ds6g_internal_bn_stats_finalize(p.bn_partial, nblk, (long)p.Mg, K, eps, momentum, mean, invstd, running_mean,
+    if (const int rc = run_bgemm<T16>(p, pl, nullptr, nullptr, 0, (hipStream_t)stream)) return rc;
+    return ds6g_internal_bn_stats_finalize(p.bn_partial, cdiv(p.Mg, pl.BM), (long)p.Mg, K, eps, momentum, mean, invstd, running_mean,
                                            running_var, (hipStream_t)stream);
 }
 int ds6g_h16_conv2d_fwd_bnstats(int st16, const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int R,
@@ -825,26 +733,20 @@ extern "C++" template <typename T16>
 static int h16_conv2d_bias_act_fwd(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H,
                                    int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && bias && y && C % BK == 0 && K % 8 == 0 && N > 0 && relu >= 0 && relu <= 2);
-    BgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
-    DS6G_CHECK_ARG(p.Ho > 0 && p.Wo > 0 && sizes_ok(p));
+    DS6G_CHECK_ARG(x && w && bias && y && relu >= 0 && relu <= 2);
+    const GemmProblem q = {H16F, DS6G_GEMM_CONV_BIAS_ACT_FWD, N, H, W, C, K, R, S, stride, pad, 1, 1, 0, 0, 0};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
     p.a_src = (const __bf16*)x; p.b_src = (const __bf16*)w; p.out = y;
     p.bias = bias; p.residual16 = residual; p.relu = relu;
-    p.a_bytes = (unsigned)((size_t)N * H * W * C * 2); p.b_bytes = (unsigned)((size_t)K * R * S * C * 2);
-    p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
-    DS6G_CHECK_ARG((size_t)p.Mg * p.Ng * 4 < OOB_OFF);
-    const int tile = pick_tile(p.Mg, p.Ng, 1);
-    void* rec = ds6g_prof_open(30200 + tile, 2.0 * p.Mg * p.Ng * p.Kg, (hipStream_t)stream);
-    const int rc = launch_tiles<B_FWD, 1, 2, T16>(p, 1, tile, (hipStream_t)stream);
-    ds6g_prof_close(rec, (hipStream_t)stream);
-    return rc;
+    return run_bgemm<T16>(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 int ds6g_h16_conv2d_bias_act_fwd(int st16, const void* x, const void* w, const float* bias, const void* residual, void* y,
                                  int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
     DS6G_RETURN_H16(st16, h16_conv2d_bias_act_fwd, x, w, bias, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream);
 }
 
+// the size the caller provides for every tile choice (64-row tiles), also where 128-row tiles need half of it
 size_t ds6g_h16_conv_bnstats_workspace_bytes(long M, int K) { return (size_t)cdiv(M, 64) * 2 * K * sizeof(double); }
 
 // dx (+)= conv^T(dy, w): dy bf16, w bf16, dx bf16 / fp32.  K % 64 == 0, C % 8 == 0; stride 1, or 2 with even H, W (the four
@@ -853,21 +755,12 @@ extern "C++" template <typename T16>
 static int h16_conv2d_dgrad(const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K, int R,
                            int S, int stride, int pad, int accumulate, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(dy && w && dx && K % BK == 0 && C % 8 == 0 && (stride == 1 || (stride == 2 && H % 2 == 0 && W % 2 == 0)));
-    BgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
-    DS6G_CHECK_ARG(sizes_ok(p));
-    p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)w; p.out = dx; p.accumulate = accumulate;
-    p.a_bytes = (unsigned)((size_t)N * p.Ho * p.Wo * K * 2); p.b_bytes = (unsigned)((size_t)K * R * S * C * 2);
-    if (stride == 2) {
-        p.nclass = 4;
-        p.hstep = 2; p.Hs = H / 2; p.wstep = 2; p.Ws = W / 2; p.rstep = 2; p.sstep = 2;
-        p.nr = (R + 1) / 2; p.ns = (S + 1) / 2;
-        p.Mg = N * p.Hs * p.Ws; p.Ng = C; p.Kg = p.nr * p.ns * K;   // the largest class (tile choice); classes derive their own
-        return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 4), (hipStream_t)stream);
-    }
-    p.Mg = N * H * W; p.Ng = C; p.Kg = R * S * K;
-    return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(p.Mg, p.Ng, 1), (hipStream_t)stream);
+    DS6G_CHECK_ARG(dy && w && dx);
+    const GemmProblem q = {H16F, DS6G_GEMM_CONV_DGRAD, N, H, W, C, K, R, S, stride, pad, 0, out16 != 0, accumulate, 0, 0};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
+    p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)w; p.out = dx;
+    return run_bgemm<T16>(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 int ds6g_h16_conv2d_dgrad(int st16, const void* dy, const void* w, void* dx, int out16, int N, int H, int W, int C, int K,
                           int R, int S, int stride, int pad, int accumulate, void* stream) {
@@ -879,14 +772,13 @@ extern "C++" template <typename T16>
 static int h16_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
                            int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && dy && dw && C % 8 == 0 && K % 8 == 0);
-    BgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
-    DS6G_CHECK_ARG(sizes_ok(p) && bgemm_wgrad_walk(p));
-    p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)x;
-    p.a_bytes = (unsigned)((size_t)N * p.Ho * p.Wo * K * 2); p.b_bytes = (unsigned)((size_t)N * H * W * C * 2);
-    p.Mg = K; p.Ng = R * S * C; p.Kg = N * p.Ho * p.Wo;
-    return run_wgrad<T16>(p, dw, accumulate, nullptr, ws, ws_bytes, (hipStream_t)stream);
+    DS6G_CHECK_ARG(x && dy && dw);
+    const GemmProblem q = {H16F, DS6G_GEMM_CONV_WGRAD, N, H, W, C, K, R, S, stride, pad, 0, 0, accumulate, 0, ws_bytes};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
+    DS6G_CHECK_ARG(ws || !pl.reduce);
+    p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)x; p.out = pl.reduce ? ws : dw;
+    return run_bgemm<T16>(p, pl, dw, nullptr, accumulate, (hipStream_t)stream);
 }
 int ds6g_h16_conv2d_wgrad(int st16, const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
                           int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
@@ -899,18 +791,17 @@ extern "C++" template <typename T16>
 static int h16_linear_fwd(const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K, int relu,
                          const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && K % BK == 0 && N % 8 == 0 && M > 0 && drop_p >= 0.f && drop_p < 1.f);
+    DS6G_CHECK_ARG(x && w && y && drop_p >= 0.f && drop_p < 1.f);
     DS6G_CHECK_ARG(!(out16 && residual));   // the residual stream is fp32: a fused residual add writes fp32
-    BgemmParams p;
-    fill_conv(p, 1, 1, M, K, N, 1, 1, 1, 0);
-    DS6G_CHECK_ARG(sizes_ok(p));
+    const uint32_t drop_thr = ds6g_drop_threshold(drop_p);
+    const GemmProblem q = {H16F, DS6G_GEMM_LINEAR_FWD, 1, 1, M, K, N, 1, 1, 1, 0, bias || relu || drop_thr || residual, out16 != 0, 0, 0, 0};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
     p.a_src = (const __bf16*)x; p.b_src = (const __bf16*)w; p.out = y; p.bias = bias; p.relu = relu; p.residual = residual;
-    p.drop_thr = ds6g_drop_threshold(drop_p);
+    p.drop_thr = drop_thr;
     p.drop_scale = 1.f / (1.f - drop_p);
     p.seed = seed; p.seed_off = seed_off; p.salt = g_ds6g_salt;
-    p.a_bytes = (unsigned)((size_t)M * K * 2); p.b_bytes = (unsigned)((size_t)N * K * 2);
-    p.Mg = M; p.Ng = N; p.Kg = K;
-    return launch_bgemm<B_FWD, T16>(p, out16, 1, pick_tile(M, N, 1), (hipStream_t)stream);
+    return run_bgemm<T16>(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 int ds6g_h16_linear_fwd(int st16, const void* x, const void* w, const float* bias, void* y, int out16, int M, int N, int K,
                         int relu, const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
@@ -923,16 +814,13 @@ extern "C++" template <typename T16>
 static int h16_linear_dgrad(const void* dy, const void* w, void* dx, int out16, int M, int N, int K, const void* mask_src,
                            int mask16, int accumulate, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(dy && w && dx && N % BK == 0 && K % 8 == 0);
+    DS6G_CHECK_ARG(dy && w && dx);
     DS6G_CHECK_ARG(!(mask_src && !out16));
-    BgemmParams p;
-    fill_conv(p, 1, 1, M, K, N, 1, 1, 1, 0);
-    DS6G_CHECK_ARG(sizes_ok(p));
+    const GemmProblem q = {H16F, DS6G_GEMM_LINEAR_DGRAD, 1, 1, M, K, N, 1, 1, 1, 0, mask_src != nullptr, out16 != 0, accumulate, 0, 0};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
     p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)w; p.out = dx; p.mask_src = mask_src; p.mask16 = mask16;
-    p.accumulate = accumulate;
-    p.a_bytes = (unsigned)((size_t)M * N * 2); p.b_bytes = (unsigned)((size_t)N * K * 2);
-    p.Mg = M; p.Ng = K; p.Kg = N;
-    return launch_bgemm<B_DGRAD, T16>(p, out16, 1, pick_tile(M, K, 1), (hipStream_t)stream);
+    return run_bgemm<T16>(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 int ds6g_h16_linear_dgrad(int st16, const void* dy, const void* w, void* dx, int out16, int M, int N, int K,
                           const void* mask_src, int mask16, int accumulate, void* stream) {
@@ -944,14 +832,13 @@ extern "C++" template <typename T16>
 static int h16_linear_wgrad(const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
                            float* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && dy && dw && K % 8 == 0 && N % 8 == 0);
-    BgemmParams p;
-    fill_conv(p, 1, 1, M, K, N, 1, 1, 1, 0);
-    DS6G_CHECK_ARG(sizes_ok(p) && bgemm_wgrad_walk(p));
-    p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)x;
-    p.a_bytes = (unsigned)((size_t)M * N * 2); p.b_bytes = (unsigned)((size_t)M * K * 2);
-    p.Mg = N; p.Ng = K; p.Kg = M;
-    return run_wgrad<T16>(p, dw, accumulate, dbias, ws, ws_bytes, (hipStream_t)stream);
+    DS6G_CHECK_ARG(x && dy && dw);
+    const GemmProblem q = {H16F, DS6G_GEMM_LINEAR_WGRAD, 1, 1, M, K, N, 1, 1, 1, 0, 0, 0, accumulate, dbias != nullptr, ws_bytes};
+    GemmPlan pl; BgemmParams p;
+    if (const int rc = gemm_plan_params(q, ds6g_internal_bgemm_knobs(), pl, p)) return rc;
+    DS6G_CHECK_ARG(ws || !pl.reduce);
+    p.a_src = (const __bf16*)dy; p.b_src = (const __bf16*)x; p.out = pl.reduce ? ws : dw;
+    return run_bgemm<T16>(p, pl, dw, dbias, accumulate, (hipStream_t)stream);
 }
 int ds6g_h16_linear_wgrad(int st16, const void* x, const void* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
                           float* ws, size_t ws_bytes, void* stream) {
@@ -959,3 +846,4 @@ int ds6g_h16_linear_wgrad(int st16, const void* x, const void* dy, float* dw, fl
 }
 
 }  // extern "C"
+

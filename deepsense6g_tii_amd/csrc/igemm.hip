@@ -20,8 +20,8 @@
 // ds_read_b128.  Row-contiguous sources (both wgrad operands, dgrad weights) use a k-major [16][rows]
 // image: whole 256/512-B rows per wave-instruction and 8 conflict-free ds_read_b32 per fragment.
 #include "common.h"
+#include "gemm_plan.h"
 #include <vector>
-#include <cstdlib>
 
 extern int g_ds6g_attn_fused128;  // attention.hip: hd = 128 backward with the fused dK + dV kernel (experiment)
 extern int g_ds6g_attn_merged_sum;  // attention.hip: hand-over backward reduces the dK, dV and dQ slabs in one launch
@@ -92,7 +92,7 @@ struct IgemmParams {
 // BF 3: three-way split (hi, mid, lo = 24 significand bits), the six products above 2^-24: fp32-grade results
 // for 6/16 of the exact path's matrix-core cycles.
 // FAST 1: the k walk is wave-uniform - a k-tile never straddles a filter tap (FWD: C % BK == 0, DGRAD: K % BK == 0) or
-// an image row group (WGRAD: see wgrad_fast_ok) - so the per-lane byte offsets are constants of the current tap / of
+// an image row group (WGRAD: gemm_wgrad_rows, gemm_plan.h) - so the per-lane byte offsets are constants of the current tap / of
 // the lane, and the per-k-tile advance lives in SGPRs and rides in the buffer instruction's scalar offset: the loop
 // spends ~2 (FWD/DGRAD) to ~8 (WGRAD) VALU instructions per DMA piece instead of ~25.  FAST 0 is the general walk
 // (any channel count, any image size), kept for the stem (C = 4) and odd shapes.
@@ -755,6 +755,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     *o = s;
 }
 
+// ---- host: every call is PLANNED first (gemm_plan.h: integer arithmetic on the shape, the workspace size and the knobs - no
+// HIP call, no pointer; ds6g_gemm_plan shows it to tests), then the plan is RUN (run_igemm).  DESIGN.md 3.1 has the rules.
+static_assert(GEMM_ERR_ARG == DS6G_ERR_ARG && GEMM_ERR_WORKSPACE == DS6G_ERR_WORKSPACE && GEMM_OOB == OOB_OFF, "gemm_plan.h");
+
 // last launched variant, for the bench's live per-kernel timing (see ds6g_last_igemm_variant in the header)
 int g_last_variant = -1;
 
@@ -762,181 +766,91 @@ int g_last_variant = -1;
 struct ProfRec { int variant; double flops; hipEvent_t e0, e1; };
 std::vector<ProfRec>* g_prof = nullptr;
 size_t g_prof_cap = 0;
-int g_dbg = 0;
 
-// tile choice: 0 = 128x128, 1 = 128x64, 2 = 64x64 - the largest tile that still yields >= 384 workgroups
-int g_min_blocks = 2560;  // measured: many small (64x64, 8 waves/SIMD) workgroups beat larger tiles up to here
-int g_wgrad_tile = 1;
-int g_bf16_bk32 = 1;
-int g_f32_bk32 = 2;  // 0 never, 1 wherever the walk allows it (experiment), 2 small-spatial convs only
-int pick_tile(int Mg, int Ng, long splits) {
-    const long t128 = (long)cdiv(Mg, 128) * cdiv(Ng, 128) * splits;
-    const long t12864 = (long)cdiv(Mg, 128) * cdiv(Ng, 64) * splits;
-    if (Ng > 64 && Mg > 64 && t128 >= g_min_blocks) return 0;
-    if (Mg > 64 && t12864 >= g_min_blocks) return 1;
-    return 2;
+// the knobs of this family: ds6g_set_debug_flags stores its fields here, the environment is read once, the mode per call
+GemmKnobs g_knobs;
+GemmKnobs igemm_knobs() {
+    static const bool env_read = [] {   // overrides for tuning sweeps
+        gemm_env("DS6G_WGRAD_TARGET_LIN", &g_knobs.wgrad_target_lin);
+        gemm_env("DS6G_WGRAD_TARGET_CONV", &g_knobs.wgrad_target_conv);
+        gemm_env("DS6G_WGRAD_XCD", &g_knobs.wgrad_xcd);
+        return true;
+    }();
+    (void)env_read;
+    GemmKnobs kn = g_knobs;
+    kn.operand_mode = g_ds6g_bf16;
+    return kn;
 }
 
-template <int MODE, int EPI, int BKV, int BF, int FAST>
-void launch_tile(IgemmParams& p, int splits, int tile, hipStream_t st) {
-    dim3 block(256);
-    const int ny = p.nclass > 1 ? p.nclass : 1;
-    if (tile == 0) {
-        p.tiles_n = cdiv(p.Ng, 128);
-        dim3 grid(cdiv(p.Mg, 128) * p.tiles_n, ny, splits);
-        hipLaunchKernelGGL((igemm_kernel<MODE, 128, 128, EPI, BKV, BF, FAST>), grid, block, 0, st, p);
-    } else if (tile == 1) {
-        p.tiles_n = cdiv(p.Ng, 64);
-        dim3 grid(cdiv(p.Mg, 128) * p.tiles_n, ny, splits);
-        hipLaunchKernelGGL((igemm_kernel<MODE, 128, 64, EPI, BKV, BF, FAST>), grid, block, 0, st, p);
-    } else {
-        p.tiles_n = cdiv(p.Ng, 64);
-        dim3 grid(cdiv(p.Mg, 64) * p.tiles_n, ny, splits);
-        hipLaunchKernelGGL((igemm_kernel<MODE, 64, 64, EPI, BKV, BF, FAST>), grid, block, 0, st, p);
-    }
+}  // namespace
+
+// shared with bgemm.hip and winograd.hip: open / close one profiler record around a kernel launch (no-ops unless profiling is on)
+void* ds6g_prof_open(int variant, double flops, hipStream_t st) {
+    if (!g_prof || g_prof->size() >= g_prof_cap) return nullptr;
+    g_prof->push_back(ProfRec{});
+    ProfRec* rec = &g_prof->back();
+    rec->variant = variant;
+    rec->flops = flops;
+    (void)hipEventCreate(&rec->e0);
+    (void)hipEventCreate(&rec->e1);
+    (void)hipEventRecord(rec->e0, st);
+    return rec;
+}
+void ds6g_prof_close(void* rec, hipStream_t st) {
+    if (rec) (void)hipEventRecord(static_cast<ProfRec*>(rec)->e1, st);
 }
 
-// FAST walk eligibility (see igemm_kernel); also fills wg_rows for WGRAD
-template <int MODE>
-bool fast_walk_ok(IgemmParams& p, int bk = 16) {
-    if (MODE == MODE_FWD) return p.C % bk == 0;
-    if (MODE == MODE_DGRAD) return p.K % bk == 0;
-    // WGRAD: the bk pixels of a k-tile share one (image, output row) - or cover whole rows of one image
-    if (p.Wo % bk == 0 || p.N * p.Ho == 1) { p.wg_rows = 0; return true; }
-    if (bk % p.Wo == 0 && p.Ho % (bk / p.Wo) == 0) { p.wg_rows = bk / p.Wo; return true; }
-    return false;
-}
-
-template <int MODE>
-int launch_igemm(IgemmParams& p, int splits, int tile, hipStream_t st) {
-    p.dbg = g_dbg;
-    const bool full = p.bias || p.relu || p.mask_src || p.drop_thr || p.residual || (MODE == MODE_DGRAD && p.hstep != 1);
-    if ((size_t)p.Mg * p.Ng * sizeof(float) >= OOB_OFF) return DS6G_ERR_ARG;
-    // BK = 32 was measured (tools/bench_igemm.py): within +-5 % on fwd/dgrad, 10-30 % slower on wgrad -> BK = 16
-    const bool fast = fast_walk_ok<MODE>(p) && !(g_dbg & 0x80);
-    const bool epi = MODE != MODE_WGRAD && full;
-    // 32-column k-tiles: bf16 mode - one MFMA per 16 columns makes the k-tile bookkeeping (DMA issue, barrier) the
-    // bottleneck, so fwd / dgrad use two MFMAs per barrier wherever the uniform walk allows it (wgrad was measured with
-    // 32-pixel k-tiles too: no gain, its k-major fragments are LDS-read bound); fp32 - pays on the small-spatial conv
-    // layers (16x16, 8x8: few workgroups per CU, +4-15 %), not on the large ones, the GPT linears or any wgrad
-    // (measured, tools/bench_igemm.py)
-    const bool can32 = MODE != MODE_WGRAD && fast && fast_walk_ok<MODE>(p, 32);
-    const bool bk32 = can32 && (g_ds6g_bf16 ? g_bf16_bk32 != 0
-                                            : (g_f32_bk32 == 1 || (g_f32_bk32 == 2 && !p.is_linear && p.R * p.S > 1 &&
-                                                                   (long)cdiv(p.Mg, 64) * cdiv(p.Ng, 64) <= 1024)));
-    const int variant = 10000 * (int)bk32 + 1000 * (int)epi + 100 * (int)fast + 10 * MODE + tile;
-    ProfRec* rec = nullptr;
-    if (g_prof && g_prof->size() < g_prof_cap) {
-        g_prof->push_back(ProfRec{});
-        rec = &g_prof->back();
-        rec->variant = variant;
-        rec->flops = p.prof_flops > 0 ? p.prof_flops : 2.0 * p.Mg * p.Ng * p.Kg;
-        (void)hipEventCreate(&rec->e0);
-        (void)hipEventCreate(&rec->e1);
-        (void)hipEventRecord(rec->e0, st);
-    }
-    const int bfm = g_ds6g_bf16;
-#define DS6G_TILE(EPI_, BK_, FAST_)                                               \
-    do {                                                                          \
-        if (bfm == 3) launch_tile<MODE, EPI_, BK_, 3, FAST_>(p, splits, tile, st); \
-        else if (bfm == 2) launch_tile<MODE, EPI_, BK_, 2, FAST_>(p, splits, tile, st); \
-        else if (bfm == 1) launch_tile<MODE, EPI_, BK_, 1, FAST_>(p, splits, tile, st); \
-        else launch_tile<MODE, EPI_, BK_, 0, FAST_>(p, splits, tile, st);         \
-    } while (0)
-    if (bk32) {
-        if constexpr (MODE != MODE_WGRAD) {
-            if (epi) DS6G_TILE(1, 32, 1); else DS6G_TILE(0, 32, 1);
-        }
-    } else if (fast) {
-        if (epi) DS6G_TILE(1, 16, 1); else DS6G_TILE(0, 16, 1);
-    } else {
-        if (epi) DS6G_TILE(1, 16, 0); else DS6G_TILE(0, 16, 0);
-    }
-#undef DS6G_TILE
-    if (rec) (void)hipEventRecord(rec->e1, st);
-    g_last_variant = variant;
+// shared with bgemm.hip: the split-K slab reduction (weight gradient + optional bias-gradient tail)
+int ds6g_internal_splitk_reduce(const float* ws, float* dw, long n4, float* dbias, long m4, int splits, size_t stride,
+                                int accumulate, int accumulate_b, hipStream_t st) {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(n4 + m4, RED_COLS)), dim3(256), 0, st, ws, dw, n4, dbias, m4, splits,
+                       stride, accumulate, accumulate_b);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
 
-template <int MODE>
-int launch_igemm(IgemmParams& p, hipStream_t st) {
-    return launch_igemm<MODE>(p, 1, pick_tile(p.Mg, p.Ng, 1), st);
-}
+GemmKnobs ds6g_internal_bgemm_knobs();  // bgemm.hip
 
-int run_wgrad(IgemmParams& p, float* dw, int accumulate, float* dbias, int accumulate_b, float* ws, size_t ws_bytes,
-              hipStream_t st) {
-    const long out_elems = (long)p.Mg * p.Ng;
-    DS6G_CHECK_ARG(out_elems % 4 == 0 && p.Mg % 4 == 0);
-    const long slab_elems = out_elems + (dbias ? p.Mg : 0);
-    // the output (a weight tensor) has few tiles and the reduction (pixels) is long: split K until the grid
-    // holds enough workgroups for latency hiding, bounded by the workspace and by >= 4 k-tiles per split
-    const int tile = (p.Mg >= 128 && g_wgrad_tile == 1) ? 1 : 2;
-    const long tiles = (long)cdiv(p.Mg, tile == 1 ? 128 : 64) * cdiv(p.Ng, 64);
-    // measured on gfx950 (tools/bench_igemm.py): convs are fastest with ~2048 workgroups in flight, the GPT
-    // linears (large outputs, costlier slab reduction) with ~1024
-    static long t_lin = -1, t_conv = -1;   // env overrides for tuning sweeps
-    if (t_lin < 0) { const char* e = getenv("DS6G_WGRAD_TARGET_LIN"); t_lin = e ? atol(e) : 1024; }
-    if (t_conv < 0) { const char* e = getenv("DS6G_WGRAD_TARGET_CONV"); t_conv = e ? atol(e) : 2048; }
-    const long target_blocks = p.is_linear ? t_lin : t_conv;
-    long splits = (target_blocks + tiles - 1) / tiles;
-    const long max_by_k = (p.Kg + 64 - 1) / 64;
-    if (splits > max_by_k) splits = max_by_k;
-    const long max_by_ws = (long)(ws_bytes / (slab_elems * sizeof(float)));
-    if (splits > max_by_ws) splits = max_by_ws;
-    if (splits < 1) splits = 1;
-    int kps = cdiv(cdiv(p.Kg, splits), 32) * 32;
-    splits = cdiv(p.Kg, kps);
-    p.k_per_split = kps;
-    p.split_stride = (size_t)slab_elems;
-    p.want_colsum = dbias != nullptr;
-    {
-        static int xcd_mode = -1;   // env DS6G_WGRAD_XCD: 0 off, 1 (default) few-tile convs, 2 every conv wgrad (experiment)
-        if (xcd_mode < 0) { const char* e = getenv("DS6G_WGRAD_XCD"); xcd_mode = e ? atoi(e) : 1; }
-        p.xcd_splits = (!p.is_linear && splits >= 8 && ((xcd_mode == 1 && tiles <= 12) || xcd_mode == 2)) ? 1 : 0;
-    }
-    if (splits == 1 && !accumulate && !dbias) {
-        p.out = dw;
-        return launch_igemm<MODE_WGRAD>(p, 1, tile, st);
-    }
-    DS6G_CHECK_ARG(ws != nullptr && (size_t)splits * slab_elems * sizeof(float) <= ws_bytes);
-    p.out = ws;
-    int rc = launch_igemm<MODE_WGRAD>(p, (int)splits, tile, st);
-    if (rc) return rc;
-    const long n4 = out_elems / 4, m4 = dbias ? p.Mg / 4 : 0;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(n4 + m4, RED_COLS)), dim3(256), 0, st, ws, dw, n4, dbias, m4,
-                       (int)splits, (size_t)slab_elems, accumulate, accumulate_b);
-    DS6G_LAUNCH_CHECK();
+namespace {
+
+// steps 3 and 4 of every entry point: plan the problem, then the kernel parameters that the problem and the plan determine
+int plan_params(const GemmProblem& q, GemmPlan& pl, IgemmParams& p) {
+    if (const int rc = gemm_plan_params(q, igemm_knobs(), pl, p)) return rc;
+    p.is_linear = q.op >= DS6G_GEMM_LINEAR_FWD && q.op <= DS6G_GEMM_LINEAR_WGRAD;
+    if (pl.nclass > 1) p.prof_flops = 2.0 * p.Mg * p.Ng * (double)(p.R * p.S) * p.K;  // all taps are visited exactly once over the classes
+    p.dbg = g_knobs.dbg;
     return DS6G_OK;
 }
 
-void fill_conv(IgemmParams& p, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    p = IgemmParams{};
-    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K; p.R = R; p.S = S; p.stride = stride; p.pad = pad;
-    p.Ho = (H + 2 * pad - R) / stride + 1;
-    p.Wo = (W + 2 * pad - S) / stride + 1;
-    p.drop_scale = 1.f;
-    p.h0 = 0; p.hstep = 1; p.Hs = H; p.w0 = 0; p.wstep = 1; p.Ws = W;
-    p.r0 = 0; p.rstep = 1; p.nr = R; p.s0 = 0; p.sstep = 1; p.ns = S;
+// The instantiation table.  CODE = ((tile * 2 + epilogue) * 3 + k walk) * 4 + operand mode; k walk 0 general, 1 uniform, 2 uniform
+// with 32-column k-tiles.  BK = 32 was measured on wgrad too (tools/bench_igemm.py): 10-30 % slower, its k-major fragments are
+// LDS-read bound - not instantiated.
+template <int MODE, int CODE>
+void launch_igemm(const IgemmParams& p, const GemmPlan& pl, hipStream_t st) {
+    constexpr int BF = CODE % 4, KW = CODE / 4 % 3, EPI = CODE / 12 % 2, TILE = CODE / 24;
+    constexpr int BM = TILE == 2 ? 64 : 128, BN = TILE == 0 ? 128 : 64;
+    if constexpr (!(MODE == MODE_WGRAD && KW == 2))
+        hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, EPI, KW == 2 ? 32 : 16, BF, KW != 0>), dim3(pl.grid_x, pl.grid_y, pl.grid_z),
+                           dim3(256), 0, st, p);
 }
 
-// A Linear over M rows is the 1x1 convolution of ONE 1 x M image (not M 1x1 images): the per-k-tile pixel walk of the
-// kernels then never wraps (a wrap costs a VALU loop iteration per crossed image row).
-void fill_linear(IgemmParams& p, int M, int N, int K) {
-    fill_conv(p, 1, 1, M, K, N, 1, 1, 1, 0);
-    p.is_linear = 1;
+// step 5: launches what the plan says, and the slab reduction into dw (/ dbias) where it says so
+int run_igemm(const IgemmParams& p, const GemmPlan& pl, float* dw, float* dbias, int accumulate, hipStream_t st) {
+    void* rec = ds6g_prof_open(pl.variant, p.prof_flops > 0 ? p.prof_flops : 2.0 * p.Mg * p.Ng * p.Kg, st);
+    const int code = ((pl.tile * 2 + pl.epilogue) * 3 + (pl.bk == 32 ? 2 : pl.walk)) * 4 + pl.operand_mode;
+    const auto codes = std::make_integer_sequence<int, 3 * 2 * 3 * 4>{};
+    if (pl.mode == MODE_FWD) gemm_dispatch(code, [&](auto c) { launch_igemm<MODE_FWD, decltype(c)::value>(p, pl, st); }, codes);
+    else if (pl.mode == MODE_DGRAD) gemm_dispatch(code, [&](auto c) { launch_igemm<MODE_DGRAD, decltype(c)::value>(p, pl, st); }, codes);
+    else gemm_dispatch(code, [&](auto c) { launch_igemm<MODE_WGRAD, decltype(c)::value>(p, pl, st); }, codes);
+    ds6g_prof_close(rec, st);
+    g_last_variant = pl.variant;
+    DS6G_LAUNCH_CHECK();
+    if (!pl.reduce) return DS6G_OK;
+    return ds6g_internal_splitk_reduce(p.out, dw, (long)pl.Mg * pl.Ng / 4, dbias, pl.want_colsum ? pl.Mg / 4 : 0, pl.splits,
+                                       pl.slab_elems, accumulate, accumulate, st);
 }
 
-// byte sizes of the three tensors of a conv (for the buffer descriptors); all must stay below the OOB sentinel
-struct ConvBytes { size_t x, y, w; bool ok; };
-ConvBytes conv_bytes(const IgemmParams& p) {
-    ConvBytes b;
-    b.x = (size_t)p.N * p.H * p.W * p.C * sizeof(float);
-    b.y = (size_t)p.N * p.Ho * p.Wo * p.K * sizeof(float);
-    b.w = (size_t)p.K * p.R * p.S * p.C * sizeof(float);
-    b.ok = b.x < OOB_OFF && b.y < OOB_OFF && b.w < OOB_OFF;
-    return b;
-}
+constexpr int F32 = DS6G_GEMM_F32;
 
 }  // namespace
 
@@ -970,99 +884,61 @@ int ds6g_profile_end(int* variants, double* flops, float* ms, int cap) {
     return n;
 }
 
-}  // extern "C"
-
-// shared with bgemm.hip: the split-K slab reduction (weight gradient + optional bias-gradient tail)
-int ds6g_internal_splitk_reduce(const float* ws, float* dw, long n4, float* dbias, long m4, int splits, size_t stride,
-                                int accumulate, int accumulate_b, hipStream_t st) {
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(n4 + m4, RED_COLS)), dim3(256), 0, st, ws, dw, n4, dbias, m4, splits,
-                       stride, accumulate, accumulate_b);
-    DS6G_LAUNCH_CHECK();
-    return DS6G_OK;
-}
-
-// shared with winograd.hip: open / close one profiler record around a kernel launch (no-ops unless profiling is on)
-void* ds6g_prof_open(int variant, double flops, hipStream_t st) {
-    if (!g_prof || g_prof->size() >= g_prof_cap) return nullptr;
-    g_prof->push_back(ProfRec{});
-    ProfRec* rec = &g_prof->back();
-    rec->variant = variant;
-    rec->flops = flops;
-    (void)hipEventCreate(&rec->e0);
-    (void)hipEventCreate(&rec->e1);
-    (void)hipEventRecord(rec->e0, st);
-    return rec;
-}
-void ds6g_prof_close(void* rec, hipStream_t st) {
-    if (rec) (void)hipEventRecord(static_cast<ProfRec*>(rec)->e1, st);
-}
-
-extern "C" {
 int ds6g_set_debug_flags(int flags) {
-    g_dbg = flags & 0xbf;  // 0x80: force the general (FAST 0) walk
+    g_knobs.dbg = flags & 0xbf;  // 0x80: force the general (FAST 0) walk
     g_ds6g_attn_handover = (flags & 0x01000000) ? 0 : 1;
     g_ds6g_attn_fused128 = (flags & 0x04000000) ? 0 : 1;
     g_ds6g_attn_merged_sum = (flags & 0x08000000) ? 0 : 1;
     g_ds6g_attn_percu = (flags >> 20) & 0xf;  // attention: resident-workgroups-per-CU assumption of the split heuristic
     g_wino_kb64 = (flags & 0x02000000) ? 1 : 0;
-    g_bf16_bk32 = (flags & 0x10000000) ? 0 : 1;
-    g_f32_bk32 = (flags & 0x20000000) ? 1 : ((flags & 0x40000000) ? 0 : 2);   // fp32 32-column k-tiles: everywhere / never
-    g_wgrad_tile = (flags & 0x40) ? 2 : 1;
-    if ((flags >> 8) & 0xfff) g_min_blocks = (flags >> 8) & 0xfff;
+    g_knobs.bf16_bk32 = (flags & 0x10000000) ? 0 : 1;
+    g_knobs.f32_bk32 = (flags & 0x20000000) ? 1 : ((flags & 0x40000000) ? 0 : 2);   // fp32 32-column k-tiles: everywhere / never
+    g_knobs.wgrad_tile = (flags & 0x40) ? 2 : 1;
+    if ((flags >> 8) & 0xfff) g_knobs.min_blocks = (flags >> 8) & 0xfff;
     return 0;
+}
+
+// test instrumentation: the plan the entry point `op` of `family` would run for this shape, these flags (DS6G_GEMM_EPILOGUE ...)
+// and this workspace size under the process's current compute mode, debug flags and environment, or its refusal.  No HIP call.
+int ds6g_gemm_plan(int family, int op, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int flags,
+                   size_t ws_bytes, struct ds6g_gemm_plan* plan) {
+    const GemmProblem q = {family, op, N, H, W, C, K, R, S, stride, pad, (flags & DS6G_GEMM_EPILOGUE) != 0,
+                           (flags & DS6G_GEMM_OUT16) != 0, (flags & DS6G_GEMM_ACCUMULATE) != 0, (flags & DS6G_GEMM_DBIAS) != 0, ws_bytes};
+    return gemm_plan(q, family == DS6G_GEMM_H16 ? ds6g_internal_bgemm_knobs() : igemm_knobs(), plan);
 }
 
 int ds6g_conv2d_fwd(const float* x, const float* w, float* y, int N, int H, int W, int C, int K, int R,
                     int S, int stride, int pad, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && C % 4 == 0 && N > 0);
-    IgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
+    DS6G_CHECK_ARG(x && w && y);
+    const GemmProblem q = {F32, DS6G_GEMM_CONV_FWD, N, H, W, C, K, R, S, stride, pad, 0, 0, 0, 0, 0};
+    GemmPlan pl; IgemmParams p;
+    if (const int rc = plan_params(q, pl, p)) return rc;
     p.a_src = x; p.b_src = w; p.out = y;
-    const ConvBytes cb = conv_bytes(p);
-    DS6G_CHECK_ARG(cb.ok);
-    p.a_bytes = (unsigned)cb.x; p.b_bytes = (unsigned)cb.w;
-    p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
-    return launch_igemm<MODE_FWD>(p, (hipStream_t)stream);
+    return run_igemm(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 int ds6g_conv2d_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int R,
                       int S, int stride, int pad, int accumulate, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(dy && w && dx && C % 4 == 0 && K % 4 == 0);
-    IgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
-    p.a_src = dy; p.b_src = w; p.out = dx; p.accumulate = accumulate;
-    const ConvBytes cb = conv_bytes(p);
-    DS6G_CHECK_ARG(cb.ok);
-    p.a_bytes = (unsigned)cb.y; p.b_bytes = (unsigned)cb.w;
-    if (stride == 2 && H % 2 == 0 && W % 2 == 0) {
-        // four input-pixel parity classes in blockIdx.y of ONE launch (class parameters are derived in the kernel);
-        // host-side values describe the largest class (tile choice, eligibility of the uniform walk)
-        IgemmParams q = p;
-        q.nclass = 4;
-        q.hstep = 2; q.Hs = H / 2; q.wstep = 2; q.Ws = W / 2; q.rstep = 2; q.sstep = 2;
-        q.h0 = 0; q.w0 = 0; q.r0 = 0; q.s0 = 0; q.nr = (R + 1) / 2; q.ns = (S + 1) / 2;
-        q.Mg = N * q.Hs * q.Ws; q.Ng = C; q.Kg = q.nr * q.ns * K;
-        q.prof_flops = 2.0 * q.Mg * q.Ng * (double)(R * S) * K;   // all taps are visited exactly once over the classes
-        return launch_igemm<MODE_DGRAD>(q, (hipStream_t)stream);
-    }
-    p.Mg = N * H * W; p.Ng = C; p.Kg = R * S * K;
-    return launch_igemm<MODE_DGRAD>(p, (hipStream_t)stream);
+    DS6G_CHECK_ARG(dy && w && dx);
+    const GemmProblem q = {F32, DS6G_GEMM_CONV_DGRAD, N, H, W, C, K, R, S, stride, pad, 0, 0, accumulate, 0, 0};
+    GemmPlan pl; IgemmParams p;
+    if (const int rc = plan_params(q, pl, p)) return rc;
+    p.a_src = dy; p.b_src = w; p.out = dx;
+    return run_igemm(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 int ds6g_conv2d_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R,
                       int S, int stride, int pad, int accumulate, float* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && dy && dw && C % 4 == 0 && K % 4 == 0);
-    IgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
-    p.a_src = dy; p.b_src = x;
-    const ConvBytes cb = conv_bytes(p);
-    DS6G_CHECK_ARG(cb.ok);
-    p.a_bytes = (unsigned)cb.y; p.b_bytes = (unsigned)cb.x;
-    p.Mg = K; p.Ng = R * S * C; p.Kg = N * p.Ho * p.Wo;
-    return run_wgrad(p, dw, accumulate, nullptr, 0, ws, ws_bytes, (hipStream_t)stream);
+    DS6G_CHECK_ARG(x && dy && dw);
+    const GemmProblem q = {F32, DS6G_GEMM_CONV_WGRAD, N, H, W, C, K, R, S, stride, pad, 0, 0, accumulate, 0, ws_bytes};
+    GemmPlan pl; IgemmParams p;
+    if (const int rc = plan_params(q, pl, p)) return rc;
+    DS6G_CHECK_ARG(ws || !pl.reduce);
+    p.a_src = dy; p.b_src = x; p.out = pl.reduce ? ws : dw;
+    return run_igemm(p, pl, dw, nullptr, accumulate, (hipStream_t)stream);
 }
 
 // inference form of Conv2d + eval-mode BatchNorm2d (+ residual) (+ ReLU) with the BN folded into w / bias
@@ -1070,63 +946,54 @@ int ds6g_conv2d_wgrad(const float* x, const float* dy, float* dw, int N, int H, 
 int ds6g_conv2d_bias_act_fwd(const float* x, const float* w, const float* bias, const float* residual, float* y, int N,
                              int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && C % 4 == 0 && N > 0 && relu >= 0 && relu <= 2);
-    IgemmParams p;
-    fill_conv(p, N, H, W, C, K, R, S, stride, pad);
+    DS6G_CHECK_ARG(x && w && y && relu >= 0 && relu <= 2);
+    const GemmProblem q = {F32, DS6G_GEMM_CONV_BIAS_ACT_FWD, N, H, W, C, K, R, S, stride, pad, bias || relu || residual, 0, 0, 0, 0};
+    GemmPlan pl; IgemmParams p;
+    if (const int rc = plan_params(q, pl, p)) return rc;
     p.a_src = x; p.b_src = w; p.out = y; p.bias = bias; p.residual = residual; p.relu = relu;
-    const ConvBytes cb = conv_bytes(p);
-    DS6G_CHECK_ARG(cb.ok);
-    p.a_bytes = (unsigned)cb.x; p.b_bytes = (unsigned)cb.w;
-    p.Mg = N * p.Ho * p.Wo; p.Ng = K; p.Kg = R * S * C;
-    return launch_igemm<MODE_FWD>(p, (hipStream_t)stream);
+    return run_igemm(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // y[M][N] = residual + dropout( act( x[M][K] @ w[N][K]^T + bias ) )
 int ds6g_linear_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int relu,
                     const float* residual, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && w && y && K % 4 == 0 && M > 0 && drop_p >= 0.f && drop_p < 1.f);
-    IgemmParams p;
-    fill_linear(p, M, N, K);
+    DS6G_CHECK_ARG(x && w && y && drop_p >= 0.f && drop_p < 1.f);
+    const uint32_t drop_thr = ds6g_drop_threshold(drop_p);
+    const GemmProblem q = {F32, DS6G_GEMM_LINEAR_FWD, 1, 1, M, K, N, 1, 1, 1, 0, bias || relu || drop_thr || residual, 0, 0, 0, 0};
+    GemmPlan pl; IgemmParams p;
+    if (const int rc = plan_params(q, pl, p)) return rc;
     p.a_src = x; p.b_src = w; p.out = y; p.bias = bias; p.relu = relu; p.residual = residual;
-    p.drop_thr = ds6g_drop_threshold(drop_p);
+    p.drop_thr = drop_thr;
     p.drop_scale = 1.f / (1.f - drop_p);
     p.seed = seed; p.seed_off = seed_off; p.salt = g_ds6g_salt;
-    const ConvBytes cb = conv_bytes(p);
-    DS6G_CHECK_ARG(cb.ok);
-    p.a_bytes = (unsigned)cb.x; p.b_bytes = (unsigned)cb.w;
-    p.Mg = M; p.Ng = N; p.Kg = K;
-    return launch_igemm<MODE_FWD>(p, (hipStream_t)stream);
+    return run_igemm(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // dx[M][K] (+)= (dy[M][N] @ w[N][K]) * (mask_src > 0)
 int ds6g_linear_dgrad(const float* dy, const float* w, float* dx, int M, int N, int K, const float* mask_src,
                       int accumulate, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(dy && w && dx && K % 4 == 0 && N % 4 == 0);
-    IgemmParams p;
-    fill_linear(p, M, N, K);
-    p.a_src = dy; p.b_src = w; p.out = dx; p.mask_src = mask_src; p.accumulate = accumulate;
-    const ConvBytes cb = conv_bytes(p);
-    DS6G_CHECK_ARG(cb.ok);
-    p.a_bytes = (unsigned)cb.y; p.b_bytes = (unsigned)cb.w;
-    p.Mg = M; p.Ng = K; p.Kg = N;
-    return launch_igemm<MODE_DGRAD>(p, (hipStream_t)stream);
+    DS6G_CHECK_ARG(dy && w && dx);
+    const GemmProblem q = {F32, DS6G_GEMM_LINEAR_DGRAD, 1, 1, M, K, N, 1, 1, 1, 0, mask_src != nullptr, 0, accumulate, 0, 0};
+    GemmPlan pl; IgemmParams p;
+    if (const int rc = plan_params(q, pl, p)) return rc;
+    p.a_src = dy; p.b_src = w; p.out = dx; p.mask_src = mask_src;
+    return run_igemm(p, pl, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // dw[N][K] (+)= dy[M][N]^T @ x[M][K];  dbias[N] (+)= column sums of dy (nullable; fused into the same kernel)
 int ds6g_linear_wgrad(const float* x, const float* dy, float* dw, float* dbias, int M, int N, int K, int accumulate,
                       float* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && dy && dw && K % 4 == 0 && N % 4 == 0);
-    IgemmParams p;
-    fill_linear(p, M, N, K);
-    p.a_src = dy; p.b_src = x;
-    const ConvBytes cb = conv_bytes(p);
-    DS6G_CHECK_ARG(cb.ok);
-    p.a_bytes = (unsigned)cb.y; p.b_bytes = (unsigned)cb.x;
-    p.Mg = N; p.Ng = K; p.Kg = M;
-    return run_wgrad(p, dw, accumulate, dbias, accumulate, ws, ws_bytes, (hipStream_t)stream);
+    DS6G_CHECK_ARG(x && dy && dw);
+    const GemmProblem q = {F32, DS6G_GEMM_LINEAR_WGRAD, 1, 1, M, K, N, 1, 1, 1, 0, 0, 0, accumulate, dbias != nullptr, ws_bytes};
+    GemmPlan pl; IgemmParams p;
+    if (const int rc = plan_params(q, pl, p)) return rc;
+    DS6G_CHECK_ARG(ws || !pl.reduce);
+    p.a_src = dy; p.b_src = x; p.out = pl.reduce ? ws : dw;
+    return run_igemm(p, pl, dw, dbias, accumulate, (hipStream_t)stream);
 }
 
 }  // extern "C"
+

@@ -56,6 +56,16 @@ int ds6g_last_attention_bwd_slab_sums(void);
  * returns - or the refusal of that call: DS6G_ERR_WORKSPACE where a 16-bit backward gets less than
  * ds6g_attention_workspace_bytes, DS6G_ERR_ARG where it meets the switched-off hand-over form (or for a bad shape). */
 int ds6g_attention_plan(int backward, int kind, int B, int T, int nh, int hd, int ld, size_t ws_bytes, ds6g_attn_plan* plan);
+/* test instrumentation, host arithmetic only (no GPU needed): the launch that the conv / linear entry point `op` (DS6G_GEMM_CONV_FWD
+ * ..., ds6g_types.h) of storage `family` (DS6G_GEMM_F32: ds6g_conv2d_* / ds6g_linear_*; DS6G_GEMM_H16: ds6g_h16_*) would make for
+ * this shape - a linear over M rows as N = H = 1, W = M, C = in features, K = out features, R = S = stride = 1, pad = 0 - these
+ * `flags` (DS6G_GEMM_EPILOGUE | _OUT16 | _ACCUMULATE | _DBIAS) and this workspace size under the process's current compute mode,
+ * debug flags and environment - the entry points run what this very planner (csrc/gemm_plan.h) returns - or the refusal of
+ * that call: DS6G_ERR_ARG for a shape the entry point does not take, a size beyond the 2 GiB buffer limit, a 16-bit weight
+ * gradient without a uniform k walk, or a split-K reduction whose slabs do not fit ws_bytes; DS6G_ERR_WORKSPACE for
+ * ds6g_h16_conv2d_fwd_bnstats below its workspace query.  The type is named with its tag: the function has the same name. */
+int ds6g_gemm_plan(int family, int op, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int flags,
+                   size_t ws_bytes, struct ds6g_gemm_plan* plan);
 /* ablation switches for kernel timing experiments (results become wrong); 0 = normal operation.  0x08000000 keeps results
  * bit-identical: the hand-over attention backward reduces its dK / dV slabs and its dQ slabs in two launches, not one. */
 int ds6g_set_debug_flags(int flags);

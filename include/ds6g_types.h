@@ -1,4 +1,4 @@
-/* Descriptor structs of the batched entry points of ds6g.h and the attention launch plan, in a header of their own so that
+/* Descriptor structs of the batched entry points of ds6g.h and the attention and GEMM launch plans, in a header of their own so that
  * the public header and the kernel sources (csrc/common.h) share ONE definition.  The host reads a caller's descriptor
  * array during the call and hands the descriptors to the kernel by value, in its arguments. */
 #ifndef DS6G_TYPES_H
@@ -58,5 +58,38 @@ typedef struct {
     size_t handover_bytes;       /* the hand-over forms keep ws[0, handover_bytes) for the tiles; slabs start behind it */
     ds6g_attn_step steps[DS6G_ATTN_MAX_STEPS];
 } ds6g_attn_plan;
+
+/* ---- the launch of one conv / linear GEMM call, fully decided (ds6g_gemm_plan; csrc/gemm_plan.h plans every call of
+ * csrc/igemm.hip and csrc/bgemm.hip with it, then the entry point runs it).  DESIGN.md 3.1 has the table of the rules. */
+enum { DS6G_GEMM_F32 = 0,  /* fp32 storage: ds6g_conv2d_* / ds6g_linear_* */
+       DS6G_GEMM_H16 = 1 }; /* 16-bit storage: ds6g_h16_conv2d_* / ds6g_h16_linear_* */
+/* the entry point; a linear over M rows is the 1x1 conv of ONE 1 x M image: N = H = 1, W = M, C = in, K = out features */
+enum { DS6G_GEMM_CONV_FWD = 0, DS6G_GEMM_CONV_DGRAD, DS6G_GEMM_CONV_WGRAD, DS6G_GEMM_LINEAR_FWD, DS6G_GEMM_LINEAR_DGRAD,
+       DS6G_GEMM_LINEAR_WGRAD, DS6G_GEMM_CONV_BIAS_ACT_FWD, DS6G_GEMM_CONV_FWD_BNSTATS /* 16-bit storage only */ };
+/* what of a call's arguments besides the shape decides its launch (the `flags` of the query).  EPILOGUE: a fused epilogue
+ * is needed (any of bias, ReLU, ReLU mask, dropout, residual; the 16-bit inference conv always has its own) */
+enum { DS6G_GEMM_EPILOGUE = 1, DS6G_GEMM_OUT16 = 2, DS6G_GEMM_ACCUMULATE = 4, DS6G_GEMM_DBIAS = 8 };
+struct ds6g_gemm_plan {
+    int family;                  /* DS6G_GEMM_F32 / _H16 */
+    int mode;                    /* the kernel's product: 0 fwd, 1 dgrad, 2 wgrad */
+    int operand_mode;            /* fp32 storage: ds6g_set_compute_mode's matrix-core mode 0 .. 3 (the BF template value); else 0 */
+    int Mg, Ng, Kg;              /* GEMM extents; of the largest parity class where nclass > 1 */
+    int BM, BN, bk;              /* output tile and k-tile depth (16 / 32 fp32 storage, 64 16-bit storage) */
+    int tile;                    /* the tile's code in `variant`: fp32 storage 0 128x128, 1 128x64, 2 64x64; 16-bit 0 128x128, 1 64x64 */
+    int walk;                    /* 1 wave-uniform k walk, 0 general walk (fp32 storage only) */
+    int epilogue;                /* 0 plain store, 1 fused epilogue, 2 the 16-bit inference conv's */
+    int out16;                   /* 16-bit output (16-bit storage, fwd / dgrad) */
+    int nclass;                  /* 4: the parity classes of a stride-2 dgrad in grid_y; else 0 */
+    int grid_x, grid_y, grid_z;  /* grid_x = cdiv(Mg, BM) * tiles_n, grid_y = max(nclass, 1), grid_z = splits */
+    int tiles_n;                 /* cdiv(Ng, BN) */
+    int splits, k_per_split;     /* wgrad: split-K; else 1 and Kg rounded up */
+    int wg_rows;                 /* uniform wgrad walk: 0 = a k-tile stays inside one output row, else output rows per k-tile */
+    int xcd_splits;              /* wgrad: the XCD-contiguous (split, tile) mapping */
+    int want_colsum;             /* wgrad: bias-gradient column sums behind each slab */
+    int reduce;                  /* wgrad: the kernel writes `splits` slabs into the workspace and the slab reduction follows */
+    int variant;                 /* what ds6g_last_igemm_variant and the profile records carry (ds6g.h) */
+    size_t slab_elems;           /* Mg * Ng (+ Mg with want_colsum): the split stride, in floats */
+    size_t ws_bytes_used;        /* splits * slab_elems * 4 where reduce is set; the BatchNorm partials of conv2d_fwd_bnstats; else 0 */
+};
 
 #endif /* DS6G_TYPES_H */
