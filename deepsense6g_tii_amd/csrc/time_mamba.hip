@@ -1,0 +1,246 @@
+// The temporal Mamba fusion head's arithmetic behind its shared Mamba layer (reference call site mambafuser_seq.py:265-282),
+// fp32: for the 17 rows of a sample - 3 modalities x 5 frames of the layer's output y, then the 2 gps rows -
+//   score   s[r] = max_c row[r][c] + (1 / 512) sum_c row[r][c]                (MaxPool1d(512) + AvgPool1d(512))
+//   attn    a = softmax(W5 s + b5) over the 5 frames of a modality (one Linear(5, 5) shared by the three),
+//           a_g = softmax(W2 s_g + b2) over the 2 gps rows
+//   out[c]  = sum_m sum_t a_m[t] y_m[t][c] + sum_j a_g[j] gps[j][c]
+// ONE launch forward, ONE backward.  One workgroup per sample, 512 threads: thread c owns channel c of all 17 rows in
+// registers, so every global access is a coalesced 2 KB row and the weighted sum over rows is thread-local.  The 17 row
+// reductions go butterfly-wise through the wave, then through an LDS table across the 8 waves in wave order; the two tiny
+// linears and softmaxes are done by 4 lanes (one per softmax group) out of LDS.  No float atomics: every sum has a fixed
+// order, two runs are bit-identical.  The backward leaves the 36 parameter-gradient values of a sample in a [B][36] slab
+// (W5 25, b5 5, W2 4, b2 2) for ds6g_batch_sum.
+#include "common.h"
+
+namespace {
+
+constexpr int TM_C = 512;          // channels == threads per workgroup
+constexpr int TM_S = 5;            // frames per modality
+constexpr int TM_R = 17;           // rows per sample: 3 * 5 + 2
+constexpr int TM_GPS = 15;         // first gps row
+constexpr int TM_W = TM_C / 64;    // waves per workgroup
+constexpr int TM_NP = 36;          // parameter-gradient values per sample
+
+// row r of sample b, channel c: y is the layer's output on the modality-major batch, row (m * B + b) * 5 + t
+__device__ __forceinline__ size_t y_off(int B, int b, int r, int c) {
+    const int m = r / TM_S, t = r - m * TM_S;
+    return (((size_t)m * B + b) * TM_S + t) * TM_C + c;
+}
+
+__device__ __forceinline__ void load_rows(const float* __restrict__ y, const float* __restrict__ gps, size_t ld_gps, int B,
+                                          int b, int c, float v[TM_R]) {
+#pragma unroll
+    for (int r = 0; r < TM_GPS; ++r) v[r] = y[y_off(B, b, r, c)];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) v[TM_GPS + j] = gps[(size_t)b * ld_gps + j * TM_C + c];
+}
+
+// softmax group g = 0, 1, 2 (a modality: 5 rows from 5 g, Linear(5, 5)) or 3 (gps: 2 rows from 15, Linear(2, 2))
+__device__ __forceinline__ int group_n(int g) { return g < 3 ? TM_S : 2; }
+
+__global__ __launch_bounds__(TM_C) void time_attn_fwd_kernel(const float* __restrict__ y, const float* __restrict__ gps,
+                                                             size_t ld_gps, const float* __restrict__ w5,
+                                                             const float* __restrict__ b5, const float* __restrict__ w2,
+                                                             const float* __restrict__ b2, float* __restrict__ out,
+                                                             float* __restrict__ attn, float* __restrict__ score,
+                                                             int* __restrict__ argmax, int B) {
+    __shared__ float s_max[TM_R][TM_W], s_sum[TM_R][TM_W];
+    __shared__ int s_idx[TM_R][TM_W];
+    __shared__ float s_score[TM_R], s_attn[TM_R];
+    const int b = blockIdx.x, c = threadIdx.x, wave = c >> 6, lane = c & 63;
+    float v[TM_R];
+    load_rows(y, gps, ld_gps, B, b, c, v);
+    // per row: (max, lowest channel holding it) and the sum, over the wave's 64 channels
+#pragma unroll
+    for (int r = 0; r < TM_R; ++r) {
+        float mx = v[r], sm = v[r];
+        int ix = c;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(mx, o, 64);
+            const int oi = __shfl_xor(ix, o, 64);
+            sm += __shfl_xor(sm, o, 64);
+            if (ov > mx || (ov == mx && oi < ix)) { mx = ov; ix = oi; }
+        }
+        if (lane == 0) { s_max[r][wave] = mx; s_idx[r][wave] = ix; s_sum[r][wave] = sm; }
+    }
+    __syncthreads();
+    if (c < TM_R) {
+        // the waves hold ascending channel ranges: a strict > keeps the lowest channel of a tie.  The running maximum starts
+        // at -inf, not 0: a row can be all negative.
+        float mx = -INFINITY, sm = 0.f;
+        int ix = 0;
+#pragma unroll
+        for (int w = 0; w < TM_W; ++w) {
+            if (s_max[c][w] > mx) { mx = s_max[c][w]; ix = s_idx[c][w]; }
+            sm += s_sum[c][w];
+        }
+        const float sc = mx + sm * (1.f / TM_C);
+        s_score[c] = sc;
+        score[(size_t)b * TM_R + c] = sc;
+        argmax[(size_t)b * TM_R + c] = ix;
+    }
+    __syncthreads();
+    if (c < 4) {
+        const int n = group_n(c), base = c * TM_S;
+        const float* W = c < 3 ? w5 : w2;
+        const float* bias = c < 3 ? b5 : b2;
+        float z[TM_S], zmax = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < TM_S; ++i) {
+            if (i < n) {
+                float acc = bias[i];
+                for (int j = 0; j < n; ++j) acc = fmaf(W[i * n + j], s_score[base + j], acc);
+                z[i] = acc;
+                zmax = fmaxf(zmax, acc);
+            }
+        }
+        float den = 0.f;
+#pragma unroll
+        for (int i = 0; i < TM_S; ++i) {
+            if (i < n) { z[i] = expf(z[i] - zmax); den += z[i]; }
+        }
+#pragma unroll
+        for (int i = 0; i < TM_S; ++i) {
+            if (i < n) {
+                const float a = z[i] / den;
+                s_attn[base + i] = a;
+                attn[(size_t)b * TM_R + base + i] = a;
+            }
+        }
+    }
+    __syncthreads();
+    // the reference's order: each modality's weighted sum over its frames, then image + lidar + radar + gps
+    float acc = 0.f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float f = 0.f;
+#pragma unroll
+        for (int i = 0; i < TM_S; ++i)
+            if (i < group_n(g)) f = fmaf(s_attn[g * TM_S + i], v[g * TM_S + i], f);
+        acc += f;
+    }
+    out[(size_t)b * TM_C + c] = acc;
+}
+
+// dy[r][c] = a[r] dout[c] + ds[r] / 512 + (c == argmax[r] ? ds[r] : 0),  ds = W^T (a (.) (da - sum a da)) per softmax group,
+// da[r] = sum_c dout[c] row[r][c]
+__global__ __launch_bounds__(TM_C) void time_attn_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ y,
+                                                             const float* __restrict__ gps, size_t ld_gps,
+                                                             const float* __restrict__ attn, const float* __restrict__ score,
+                                                             const int* __restrict__ argmax, const float* __restrict__ w5,
+                                                             const float* __restrict__ w2, float* __restrict__ dy,
+                                                             float* __restrict__ dgps, size_t ld_dgps,
+                                                             float* __restrict__ part, int B) {
+    __shared__ float s_red[TM_R][TM_W];
+    __shared__ float s_da[TM_R], s_attn[TM_R], s_score[TM_R], s_dz[TM_R], s_ds[TM_R];
+    __shared__ int s_arg[TM_R];
+    const int b = blockIdx.x, c = threadIdx.x, wave = c >> 6, lane = c & 63;
+    const float g = dout[(size_t)b * TM_C + c];
+    {
+        float v[TM_R];
+        load_rows(y, gps, ld_gps, B, b, c, v);
+#pragma unroll
+        for (int r = 0; r < TM_R; ++r) {
+            const float p = wave_reduce_sum(g * v[r]);
+            if (lane == 0) s_red[r][wave] = p;
+        }
+    }
+    if (c < TM_R) {
+        s_attn[c] = attn[(size_t)b * TM_R + c];
+        s_score[c] = score[(size_t)b * TM_R + c];
+        s_arg[c] = argmax[(size_t)b * TM_R + c];
+    }
+    __syncthreads();
+    if (c < TM_R) {
+        float sm = 0.f;
+#pragma unroll
+        for (int w = 0; w < TM_W; ++w) sm += s_red[c][w];
+        s_da[c] = sm;
+    }
+    __syncthreads();
+    if (c < 4) {
+        const int n = group_n(c), base = c * TM_S;
+        const float* W = c < 3 ? w5 : w2;
+        float dot = 0.f;
+        for (int i = 0; i < n; ++i) dot = fmaf(s_attn[base + i], s_da[base + i], dot);
+        float dz[TM_S];
+#pragma unroll
+        for (int i = 0; i < TM_S; ++i) {
+            dz[i] = i < n ? s_attn[base + i] * (s_da[base + i] - dot) : 0.f;
+            if (i < n) s_dz[base + i] = dz[i];
+        }
+#pragma unroll
+        for (int j = 0; j < TM_S; ++j) {
+            if (j < n) {
+                float acc = 0.f;
+#pragma unroll
+                for (int i = 0; i < TM_S; ++i)
+                    if (i < n) acc = fmaf(W[i * n + j], dz[i], acc);
+                s_ds[base + j] = acc;
+            }
+        }
+    }
+    __syncthreads();
+    if (c < TM_NP) {
+        // the sample's share of dW5 [5][5], db5 [5] (summed over its three modalities in index order), dW2 [2][2], db2 [2]
+        float p;
+        if (c < 30) {
+            const int i = c < 25 ? c / TM_S : c - 25, j = c < 25 ? c - i * TM_S : -1;
+            p = 0.f;
+#pragma unroll
+            for (int m = 0; m < 3; ++m) p += j >= 0 ? s_dz[m * TM_S + i] * s_score[m * TM_S + j] : s_dz[m * TM_S + i];
+        } else if (c < 34) {
+            const int i = (c - 30) >> 1, j = (c - 30) & 1;
+            p = s_dz[TM_GPS + i] * s_score[TM_GPS + j];
+        } else {
+            p = s_dz[TM_GPS + c - 34];
+        }
+        part[(size_t)b * TM_NP + c] = p;
+    }
+#pragma unroll
+    for (int r = 0; r < TM_R; ++r) {
+        const float ds = s_ds[r];
+        const float o = fmaf(s_attn[r], g, ds * (1.f / TM_C)) + (c == s_arg[r] ? ds : 0.f);
+        if (r < TM_GPS) dy[y_off(B, b, r, c)] = o;
+        else dgps[(size_t)b * ld_dgps + (r - TM_GPS) * TM_C + c] = o;
+    }
+}
+
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool tm_dims_ok(int B, int S, int C) { return B >= 1 && B <= (1 << 20) && S == TM_S && C == TM_C; }
+inline bool tm_ld_ok(long ld) { return ld >= 2 * TM_C && ld % 4 == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int ds6g_time_attn_fwd(const float* y, const float* gps, long ld_gps_sample, const float* w5, const float* b5,
+                       const float* w2, const float* b2, float* out, float* attn, float* score, int* argmax, int B, int S,
+                       int C, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(y && gps && w5 && b5 && w2 && b2 && out && attn && score && argmax);
+    DS6G_CHECK_ARG(tm_dims_ok(B, S, C) && tm_ld_ok(ld_gps_sample));
+    DS6G_CHECK_ARG(al16(y) && al16(gps) && al16(w5) && al16(b5) && al16(w2) && al16(b2) && al16(out) && al16(attn) &&
+                   al16(score) && al16(argmax));
+    hipLaunchKernelGGL(time_attn_fwd_kernel, dim3(B), dim3(TM_C), 0, (hipStream_t)stream, y, gps, (size_t)ld_gps_sample, w5,
+                       b5, w2, b2, out, attn, score, argmax, B);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+int ds6g_time_attn_bwd(const float* dout, const float* y, const float* gps, long ld_gps_sample, const float* attn,
+                       const float* score, const int* argmax, const float* w5, const float* w2, float* dy, float* dgps,
+                       long ld_dgps_sample, float* dparam_part, int B, int S, int C, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(dout && y && gps && attn && score && argmax && w5 && w2 && dy && dgps && dparam_part);
+    DS6G_CHECK_ARG(tm_dims_ok(B, S, C) && tm_ld_ok(ld_gps_sample) && tm_ld_ok(ld_dgps_sample));
+    DS6G_CHECK_ARG(al16(dout) && al16(y) && al16(gps) && al16(attn) && al16(score) && al16(argmax) && al16(w5) && al16(w2) &&
+                   al16(dy) && al16(dgps) && al16(dparam_part));
+    hipLaunchKernelGGL(time_attn_bwd_kernel, dim3(B), dim3(TM_C), 0, (hipStream_t)stream, dout, y, gps,
+                       (size_t)ld_gps_sample, attn, score, argmax, w5, w2, dy, dgps, (size_t)ld_dgps_sample, dparam_part, B);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+}  // extern "C"

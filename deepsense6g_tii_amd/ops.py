@@ -1134,3 +1134,56 @@ def token_unpack_bwd(dimage, dlidar, dradar, dgps, B, S):
     dtok = torch.empty((B, 192 * S + 2, C), dtype=F32, device=dimage.device)
     lib().token_unpack_bwd(_p(dimage), _p(dlidar), _p(dradar), _p(dgps), _p(dtok), B, S, C, _stream())
     return dtok
+
+
+# ------------------------------------------------------------------------------------------------
+# Temporal Mamba fusion head (csrc/time_mamba.hip)
+TIME_ROWS = 17          # rows of a sample: 3 modalities x 5 frames, then the 2 gps rows
+TIME_PARAM_VALUES = 36  # mlp.0.weight 25, mlp.0.bias 5, mlp_gps.0.weight 4, mlp_gps.0.bias 2
+
+
+def _gps_rows(gps, B):
+    """gps rows [B, 2, 512] whose samples may be strided (the last two token rows of a [B, T, 512] tensor) -> sample stride"""
+    assert gps.dtype == F32 and gps.is_cuda and tuple(gps.shape) == (B, 2, 512) and gps.stride(2) == 1 and \
+        gps.stride(1) == 512 and (B == 1 or (gps.stride(0) >= 1024 and gps.stride(0) % 4 == 0)), \
+        (gps.dtype, tuple(gps.shape), gps.stride())
+    return max(gps.stride(0), 1024) if B == 1 else gps.stride(0)   # a one-sample view reports an arbitrary stride
+
+
+def time_attn_fwd(y, gps, w5, b5, w2, b2, B):
+    """y [3*B*5, 512]: the shared Mamba layer's output on the modality-major batch; gps [B, 2, 512] (samples may be strided);
+    w5 / b5: mlp.0, w2 / b2: mlp_gps.0 -> (out [B, 512], attn [B, 17], score [B, 17], argmax [B, 17] int32)"""
+    _chk(y, 3 * B * 5, 512)
+    ld = _gps_rows(gps, B)
+    dev = y.device
+    out = torch.empty((B, 512), dtype=F32, device=dev)
+    attn = torch.empty((B, TIME_ROWS), dtype=F32, device=dev)
+    score = torch.empty((B, TIME_ROWS), dtype=F32, device=dev)
+    argmax = torch.empty((B, TIME_ROWS), dtype=torch.int32, device=dev)
+    lib().time_attn_fwd(_p(y), _p(gps), ld, _vec(w5, 5, 5), _vec(b5, 5), _vec(w2, 2, 2), _vec(b2, 2), _p(out), _p(attn),
+                        _p(score), _p(argmax), B, 5, 512, _stream())
+    return out, attn, score, argmax
+
+
+def time_attn_bwd(dout, y, gps, attn, score, argmax, w5, w2, B, dparams=None, accumulate=False):
+    """-> (dy [3*B*5, 512], dgps [B, 2, 512], dparams): dparams is ONE 36-float tensor (the caller's when given; added to when
+    accumulate) holding dmlp.0.weight [:25], dmlp.0.bias [25:30], dmlp_gps.0.weight [30:34], dmlp_gps.0.bias [34:36], the
+    per-sample shares summed over b in index order"""
+    _chk(dout, B, 512)
+    _chk(y, 3 * B * 5, 512)
+    _chk(attn, B, TIME_ROWS)
+    _chk(score, B, TIME_ROWS)
+    assert argmax.dtype == torch.int32 and argmax.is_cuda and argmax.is_contiguous() and tuple(argmax.shape) == (B, TIME_ROWS)
+    ld = _gps_rows(gps, B)
+    dev = y.device
+    dy = torch.empty((3 * B * 5, 512), dtype=F32, device=dev)
+    dgps = torch.empty((B, 2, 512), dtype=F32, device=dev)
+    part = torch.empty((B, TIME_PARAM_VALUES), dtype=F32, device=dev)
+    if dparams is None:
+        assert not accumulate
+        dparams = torch.empty(TIME_PARAM_VALUES, dtype=F32, device=dev)
+    st = _stream()
+    lib().time_attn_bwd(_p(dout), _p(y), _p(gps), ld, _p(attn), _p(score), _p(argmax), _vec(w5, 5, 5), _vec(w2, 2, 2), _p(dy),
+                        _p(dgps), 1024, _p(part), B, 5, 512, st)
+    lib().batch_sum(_p(part), _vec(dparams, TIME_PARAM_VALUES), TIME_PARAM_VALUES, B, TIME_PARAM_VALUES, int(accumulate), st)
+    return dy, dgps, dparams

@@ -462,7 +462,33 @@ int ds6g_token_unpack_fwd(const float* tokens, float* image, float* lidar, float
 int ds6g_token_unpack_bwd(const float* dimage, const float* dlidar, const float* dradar, const float* dgps, float* dtokens,
                           int B, int S, int C, void* stream);
 
-/* ---- spatial.hip -------------------------------------------------------------------------------*/
+/* ---- time_mamba.hip : the temporal Mamba fusion head behind its shared Mamba layer, fp32 (mambafuser_seq.py:233-284) --
+ * A sample has 17 rows of C = 512 floats: 3 modalities x S = 5 frames of the layer's output y, then its 2 gps rows.  y is
+ * the layer's output on the modality-major batch [3 * B * 5][512], row (m * B + b) * 5 + t (m = image, lidar, radar); the gps
+ * rows are addressed as gps + b * ld_gps_sample + j * 512, so they may be the last two token rows of a [B][T][512] stage
+ * output (ld_gps_sample = T * 512) as well as a [B][2][512] tensor (1024).  All pointers 16-byte aligned, B >= 1, S == 5,
+ * C == 512, the sample strides >= 1024 floats and multiples of 4; anything else returns DS6G_ERR_ARG before anything is
+ * launched.  One launch each, one workgroup per sample.  No float atomics: every sum has a fixed order, two runs are
+ * bit-identical.
+ *   time_attn_fwd  (:265-282) score[b][r] = max_c row[c] + (1 / 512) sum_c row[c]  (MaxPool1d(512) + AvgPool1d(512));
+ *                  attn[b][5 m .. 5 m + 5) = softmax(w5 score[b][5 m ..] + b5) per modality (mlp: one Linear(5, 5) for the
+ *                  three), attn[b][15 .. 17) = softmax(w2 score[b][15 ..] + b2) (mlp_gps);  out[b][c] = sum_r attn[b][r]
+ *                  row_r[c].  Also written for the backward: attn, score [B][17] and argmax [B][17] (int32: the channel of
+ *                  each row's maximum, the LOWEST one of a tie - torch's CPU max-pool rule).
+ *   time_attn_bwd  from dout [B][512] and the saved tensors: dy [3 * B * 5][512] (y's layout) and dgps (at dgps + b *
+ *                  ld_dgps_sample + j * 512), both written, not accumulated:
+ *                      d row_r[c] = attn[r] dout[c] + ds[r] / 512 + (c == argmax[r] ? ds[r] : 0),
+ *                      ds = W^T (attn (.) (da - sum attn da)) per softmax group,  da[r] = sum_c dout[c] row_r[c];
+ *                  dparam_part [B][36]: sample b's share of dw5 (25, row-major), db5 (5), dw2 (4), db2 (2) - sum it over
+ *                  b with ds6g_batch_sum(dparam_part, dst, 36, B, 36, accumulate). */
+int ds6g_time_attn_fwd(const float* y, const float* gps, long ld_gps_sample, const float* w5, const float* b5,
+                       const float* w2, const float* b2, float* out, float* attn, float* score, int* argmax, int B, int S,
+                       int C, void* stream);
+int ds6g_time_attn_bwd(const float* dout, const float* y, const float* gps, long ld_gps_sample, const float* attn,
+                       const float* score, const int* argmax, const float* w5, const float* w2, float* dy, float* dgps,
+                       long ld_dgps_sample, float* dparam_part, int B, int S, int C, void* stream);
+
+/* ---- spatial.hip-------------------------------------------------------------------------------*/
 /* normalize_imagenet + stack + NCHW->NHWC: model2_seq.py:36-45,481-482,491-493 */
 int ds6g_pack_input(const float* src, float* dst, int B, int Cs, int H, int W, int Cd, int frames_per_sample, int t,
                     int normalize_imagenet, void* stream);
