@@ -5,8 +5,9 @@
 //   bi-branch gate     out[b, t] = bmN[b, L-1-t] * (leaky_0.2(f2N[b, L-1-t]) + fm[b, t]): the reverse-walk Mamba's and fc2's
 //                      outputs stay in natural token order in memory and are read back to front, no flip copy;
 //   swap pack          three NCHW [B*S][C][8][8] maps + gps [B][2][C] -> tokens [B][T][C] = dropout(pos_emb + swapped tokens);
-//   token unpack       tokens -> three NCHW maps + [B][2][C], no swap.
-// All four are bandwidth-class.  Sums that cross workgroups (the sample statistics, the two sample sums of the LayerNorm
+//   token unpack       tokens -> three NCHW maps + [B][2][C], no swap;
+//   pool swap tokens   the pack for the model walk: three NHWC [B*S][H][H][C] maps, pooled to 8 x 8 as they are swapped.
+// All five are bandwidth-class.  Sums that cross workgroups (the sample statistics, the two sample sums of the LayerNorm
 // backward) go through partial slabs reduced in a fixed order; sums over the batch (dgamma, dbeta, dpos) are loops over b in
 // index order inside one thread: no float atomics, two runs are bit-identical.
 #include "common.h"
@@ -362,7 +363,8 @@ __global__ __launch_bounds__(256) void tokens_to_maps_kernel(const float* __rest
 // dpos[i] = sum over b, in index order, of the masked token gradient
 __global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__ dtok, float* __restrict__ dpos, int B,
                                                        size_t tc, uint32_t thr, float scale, uint64_t seed,
-                                                       uint64_t seed_off_in, const uint64_t* __restrict__ salt) {
+                                                       uint64_t seed_off_in, const uint64_t* __restrict__ salt,
+                                                       int accumulate) {
     const uint64_t seed_off = seed_off_in + ((salt && thr) ? *salt : (uint64_t)0);
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= tc) return;
@@ -371,7 +373,129 @@ __global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__
         const size_t o = (size_t)b * tc + i;
         acc += drop4(ld4(dtok + o), seed, seed_off + o, thr, scale);
     }
+    if (accumulate) acc += ld4(dpos + i);
     st4(dpos + i, acc);
+}
+
+// ---- NHWC token pack of the model walk --------------------------------------------------------------------------------
+// The walk keeps the three modality maps NHWC [B*S][H][H][C] at full resolution, so the pack pools as it swaps:
+//   tokens[b][(m S + f) 64 + ph 8 + pw][c] = dropout(pos + mean over window (ph, pw) of map_q[b S + f][.][.][c]),
+//   q = (m + seg(c)) % 3; seen from the SOURCE map q, channel c goes to the token rows of modality (q - seg(c)) mod 3.
+// Workgroup = (sample b, source map q, frame f, row ph of 8 windows), or the sample's two gps rows (blockIdx.x ==
+// gridDim.x - 1).  A pooled float4 is computed once and stored to the destination row of its segment; the two float4 groups
+// per row that straddle a segment cut (C/3 and 2 (C/3) are never multiples of 4 here) go element by element.
+constexpr int PST_CMAX = 512;      // widest map: the backward keeps 8 x C masked token gradients in LDS
+
+struct PoolMaps { const float* in[3]; float* out[3]; };
+
+__device__ __forceinline__ int swap_seg(int c, int s1, int s2) { return c < s1 ? 0 : (c < s2 ? 1 : 2); }
+// token row (inside the sample) that channel segment `sg` of source map q pairs with, at frame f and window hw
+__device__ __forceinline__ int swap_row(int q, int sg, int S, int f, int hw) {
+    const int m = q - sg;
+    return ((m < 0 ? m + 3 : m) * S + f) * HW + hw;
+}
+
+__global__ __launch_bounds__(256) void pool_swap_tokens_fwd_kernel(const PoolMaps maps, const float* __restrict__ gemb,
+                                                                   const float* __restrict__ pos, float* __restrict__ tok,
+                                                                   int S, int H, int C, uint32_t thr, float scale,
+                                                                   uint64_t seed, uint64_t seed_off_in,
+                                                                   const uint64_t* __restrict__ salt) {
+    const uint64_t seed_off = seed_off_in + ((salt && thr) ? *salt : (uint64_t)0);
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int T = 3 * S * HW + 2;
+    if ((int)blockIdx.x == 3 * S * 8) {     // the gps rows
+        for (int i = tid * 4; i < 2 * C; i += 1024) {
+            const size_t o = ((size_t)b * T + (T - 2)) * C + i;
+            const f32x4 v = ld4(gemb + (size_t)b * 2 * C + i) + ld4(pos + (size_t)(T - 2) * C + i);
+            st4(tok + o, drop4(v, seed, seed_off + o, thr, scale));
+        }
+        return;
+    }
+    const int ph = blockIdx.x & 7, qf = blockIdx.x >> 3;
+    const int q = qf / S, f = qf - q * S;
+    const int k = H >> 3, cg = C >> 2;
+    const int s1 = C / 3, s2 = s1 * 2;
+    const float inv = 1.0f / (float)(k * k);
+    const float* feat = maps.in[q] + ((size_t)b * S + f) * H * H * C;
+    for (int it = tid; it < 8 * cg; it += 256) {
+        const int pw = it / cg, c4 = (it - pw * cg) * 4;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        for (int r = 0; r < k; ++r)
+            for (int u = 0; u < k; ++u) s += ld4(feat + ((size_t)(ph * k + r) * H + pw * k + u) * C + c4);
+        s *= inv;
+        const int hw = ph * 8 + pw;
+        const int g0 = swap_seg(c4, s1, s2), g3 = swap_seg(c4 + 3, s1, s2);
+        if (g0 == g3) {
+            const int row = swap_row(q, g0, S, f, hw);
+            const size_t o = ((size_t)b * T + row) * C + c4;
+            st4(tok + o, drop4(s + ld4(pos + (size_t)row * C + c4), seed, seed_off + o, thr, scale));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int row = swap_row(q, swap_seg(c4 + j, s1, s2), S, f, hw);
+                const size_t o = ((size_t)b * T + row) * C + c4 + j;
+                float v = s[j] + pos[(size_t)row * C + c4 + j];
+                if (thr) v = ds6g_keep(seed, seed_off + o, thr) ? v * scale : 0.f;
+                tok[o] = v;
+            }
+        }
+    }
+}
+
+// dfeat_q = dfeat_in_q + (masked token gradient of the window) / k^2, dgemb = the masked gps-row gradient.  Same workgroups
+// as the forward: the 8 x C masked, scaled gradients of the row of windows are gathered into LDS through the inverse swap,
+// then spread over the k pixel rows x H pixels the windows cover (in == out is allowed: an element is read, then written,
+// by one thread).
+__global__ __launch_bounds__(256) void pool_swap_tokens_bwd_kernel(const float* __restrict__ dtok, const PoolMaps maps,
+                                                                   float* __restrict__ dgemb, int S, int H, int C,
+                                                                   uint32_t thr, float scale, uint64_t seed,
+                                                                   uint64_t seed_off_in, const uint64_t* __restrict__ salt) {
+    __shared__ f32x4 gs[8 * PST_CMAX / 4];
+    const uint64_t seed_off = seed_off_in + ((salt && thr) ? *salt : (uint64_t)0);
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int T = 3 * S * HW + 2;
+    if ((int)blockIdx.x == 3 * S * 8) {
+        for (int i = tid * 4; i < 2 * C; i += 1024) {
+            const size_t o = ((size_t)b * T + (T - 2)) * C + i;
+            st4(dgemb + (size_t)b * 2 * C + i, drop4(ld4(dtok + o), seed, seed_off + o, thr, scale));
+        }
+        return;
+    }
+    const int ph = blockIdx.x & 7, qf = blockIdx.x >> 3;
+    const int q = qf / S, f = qf - q * S;
+    const int k = H >> 3, cg = C >> 2;
+    const int s1 = C / 3, s2 = s1 * 2;
+    const float inv = 1.0f / (float)(k * k);
+    for (int it = tid; it < 8 * cg; it += 256) {
+        const int pw = it / cg, c4 = (it - pw * cg) * 4;
+        const int hw = ph * 8 + pw;
+        const int g0 = swap_seg(c4, s1, s2), g3 = swap_seg(c4 + 3, s1, s2);
+        f32x4 v;
+        if (g0 == g3) {
+            const size_t o = ((size_t)b * T + swap_row(q, g0, S, f, hw)) * C + c4;
+            v = drop4(ld4(dtok + o), seed, seed_off + o, thr, scale);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t o = ((size_t)b * T + swap_row(q, swap_seg(c4 + j, s1, s2), S, f, hw)) * C + c4 + j;
+                const float d = dtok[o];
+                v[j] = thr ? (ds6g_keep(seed, seed_off + o, thr) ? d * scale : 0.f) : d;
+            }
+        }
+        gs[it] = v * inv;
+    }
+    __syncthreads();
+    const size_t base = (((size_t)b * S + f) * H + (size_t)ph * k) * H * C;   // k full pixel rows: k * H * C contiguous floats
+    const float* din = maps.in[q];
+    float* dout = maps.out[q];
+    const int n4 = k * H * cg;
+    for (int it = tid; it < n4; it += 256) {
+        const int c4i = it % cg, w = (it / cg) % H;
+        f32x4 v = gs[(w / k) * cg + c4i];
+        const size_t o = base + (size_t)it * 4;
+        if (din) v += ld4(din + o);
+        st4(dout + o, v);
+    }
 }
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -386,6 +510,10 @@ inline bool gate_dims_ok(int B, int L, int C) {
 }
 inline bool tok_dims_ok(int B, int S, int C) {
     return B > 0 && B <= 65535 && S > 0 && S <= 4096 && C > 0 && C % TC == 0 && C <= 4096;
+}
+inline bool pool_dims_ok(int B, int S, int H, int C) {
+    return B > 0 && B <= 65535 && S > 0 && S <= 4096 && H >= 8 && H <= 64 && H % 8 == 0 && C >= 4 && C % 4 == 0 &&
+           C <= PST_CMAX;
 }
 
 }  // namespace
@@ -499,7 +627,50 @@ int ds6g_swap_pack_bwd(const float* dtokens, float* dimage, float* dlidar, float
     DS6G_LAUNCH_CHECK();
     const size_t tc = (size_t)(3 * S * HW + 2) * C;
     hipLaunchKernelGGL(pos_grad_kernel, dim3((unsigned)((tc / 4 + 255) / 256)), dim3(256), 0, st, dtokens, dpos_emb, B, tc,
+                       thr, scale, seed, seed_off, g_ds6g_salt, 0);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+int ds6g_pool_swap_tokens_fwd(const ds6g_map_desc* maps, const float* gemb, const float* pos_emb, float* tokens, int B, int S,
+                              int H, int C, float drop_p, uint64_t seed, uint64_t seed_off, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(maps && gemb && pos_emb && tokens && pool_dims_ok(B, S, H, C));
+    DS6G_CHECK_ARG(al16(gemb) && al16(pos_emb) && al16(tokens) && drop_p >= 0.f && drop_p < 1.f);
+    PoolMaps pm{};
+    for (int m = 0; m < 3; ++m) {
+        DS6G_CHECK_ARG(maps[m].in && al16(maps[m].in) && maps[m].frames_per_sample == S && maps[m].mod_off == m * S * HW);
+        pm.in[m] = (const float*)maps[m].in;
+    }
+    hipLaunchKernelGGL(pool_swap_tokens_fwd_kernel, dim3(3 * S * 8 + 1, B), dim3(256), 0, (hipStream_t)stream, pm, gemb,
+                       pos_emb, tokens, S, H, C, ds6g_drop_threshold(drop_p), 1.f / (1.f - drop_p), seed, seed_off,
+                       g_ds6g_salt);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+int ds6g_pool_swap_tokens_bwd(const ds6g_map_desc* maps, const float* dtokens, float* dgemb, float* dpos_emb,
+                              int accumulate_dpos, int B, int S, int H, int C, float drop_p, uint64_t seed,
+                              uint64_t seed_off, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(maps && dtokens && dgemb && dpos_emb && pool_dims_ok(B, S, H, C));
+    DS6G_CHECK_ARG(al16(dtokens) && al16(dgemb) && al16(dpos_emb) && drop_p >= 0.f && drop_p < 1.f);
+    PoolMaps pm{};
+    for (int m = 0; m < 3; ++m) {
+        DS6G_CHECK_ARG(maps[m].out && al16(maps[m].out) && al16(maps[m].in) && maps[m].frames_per_sample == S &&
+                       maps[m].mod_off == m * S * HW);
+        pm.in[m] = (const float*)maps[m].in;
+        pm.out[m] = (float*)maps[m].out;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t thr = ds6g_drop_threshold(drop_p);
+    const float scale = 1.f / (1.f - drop_p);
+    hipLaunchKernelGGL(pool_swap_tokens_bwd_kernel, dim3(3 * S * 8 + 1, B), dim3(256), 0, st, dtokens, pm, dgemb, S, H, C,
                        thr, scale, seed, seed_off, g_ds6g_salt);
+    DS6G_LAUNCH_CHECK();
+    const size_t tc = (size_t)(3 * S * HW + 2) * C;
+    hipLaunchKernelGGL(pos_grad_kernel, dim3((unsigned)((tc / 4 + 255) / 256)), dim3(256), 0, st, dtokens, dpos_emb, B, tc,
+                       thr, scale, seed, seed_off, g_ds6g_salt, accumulate_dpos ? 1 : 0);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }

@@ -47,9 +47,38 @@ def layer_forward(mod, ws, reverse, save, u2, Bsz, L, params):
     return out, ((u2, xz, xc, x_dbl, dt, draw, y, saved) if save else None)
 
 
-def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None):
+def grad_slots(shapes, device, gdst):
+    """Where a backward writes its parameter gradients.  gdst None: fresh tensors of `shapes` (the autograd nodes return
+    them).  gdst = one (device pointer, accumulate flag) per parameter (a model walk's gradient arena): the pointers
+    themselves.  -> (slots: [(pointer, accumulate)], tensors or None)"""
+    if gdst is None:
+        ts = tuple(torch.empty(s, dtype=F32, device=device) for s in shapes)
+        return [(t.data_ptr(), 0) for t in ts], ts
+    assert len(gdst) == len(shapes), (len(gdst), len(shapes))
+    return [(int(p), int(bool(a))) for p, a in gdst], None
+
+
+def deliver_pair(fn, slot_a, slot_b, shape_a, shape_b, device, has_flag=True):
+    """fn(ptr_a, ptr_b, accumulate) is a kernel that produces two gradients under ONE accumulate flag, or (has_flag False)
+    can only write them.  Where the two destinations agree on a flag the kernel can honour: one call, in place.  Otherwise
+    the pair goes through temporaries and ds6g_axpby writes or adds each one."""
+    (pa, aa), (pb, ab) = slot_a, slot_b
+    if aa == ab and (has_flag or not aa):
+        fn(pa, pb, aa)
+        return
+    ta, tb = (torch.empty(s, dtype=F32, device=device) for s in (shape_a, shape_b))
+    fn(ta.data_ptr(), tb.data_ptr(), 0)
+    st = ops._stream()
+    for t, p, a in ((ta, pa, aa), (tb, pb, ab)):
+        ops.lib().axpby(t.data_ptr(), p if a else 0, p, t.numel(), 1.0, 1.0, st)
+
+
+def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None, gdst=None):
     """-> (du [B*L, d_model], the nine parameter gradients in Mamba._params() order).  du_out: an existing gradient of the
-    layer's input that du is ADDED to (the in_proj data-gradient GEMM accumulates into it)"""
+    layer's input that du is ADDED to (the in_proj data-gradient GEMM accumulates into it).  gdst: nine (device pointer,
+    accumulate flag) pairs in the same order - the gradients are written there in place (added where the flag is set) and
+    None is returned in their stead; the conv and scan kernels have no accumulate flag, so a set flag takes those four
+    through a temporary and an add, a fresh gradient (the training case) does not."""
     u2, xz, xc, x_dbl, dt, draw, y, saved = tape
     w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
     M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
@@ -58,26 +87,32 @@ def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None):
     def empty(*shape):
         return torch.empty(shape, dtype=F32, device=dev)
 
-    g_out = empty(dm, D)
-    ops.linear_wgrad(y, dout2, g_out.data_ptr(), ws)
+    shapes = ((2 * D, dm), (D, 1, 4), (D,), (r + 32, D), (D, r), (D,), (D, 16), (D,), (dm, D))
+    (s_in, s_cw, s_cb, s_x, s_dtw, s_dtb, s_A, s_D, s_out), grads = grad_slots(shapes, dev, gdst)
+
+    ops.linear_wgrad(y, dout2, s_out[0], ws, accumulate=bool(s_out[1]))
     dy = ops.linear_dgrad(dout2, w_out.data_ptr(), D)
     dxz, dxdbl, dxc, ddraw = empty(M, 2 * D), empty(M, r + 32), empty(M, D), empty(M, D)
-    g_A, g_D = ops.selective_scan_bwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, xz[:, D:], dy, saved,
-                                      dxc, ddraw, dxdbl[:, r:r + 16], dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse)
-    g_dtw, g_dtb = empty(D, r), empty(D)
-    ops.linear_wgrad(dt, ddraw, g_dtw.data_ptr(), ws, dbias_ptr=g_dtb.data_ptr())
+
+    def scan(pa, pd, _acc):
+        ops.selective_scan_bwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, xz[:, D:], dy, saved, dxc,
+                               ddraw, dxdbl[:, r:r + 16], dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse, out=(pa, pd))
+    deliver_pair(scan, s_A, s_D, shapes[6], shapes[7], dev, has_flag=False)
+    deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(dt, ddraw, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_dtw, s_dtb,
+                 shapes[4], shapes[5], dev)
     ops.copy_cols(ops.linear_dgrad(ddraw, w_dt.data_ptr(), r), dxdbl[:, :r])
-    g_x = empty(r + 32, D)
-    ops.linear_wgrad(xc, dxdbl, g_x.data_ptr(), ws)
+    ops.linear_wgrad(xc, dxdbl, s_x[0], ws, accumulate=bool(s_x[1]))
     ops.linear_dgrad(dxdbl, w_x.data_ptr(), D, out=dxc, accumulate=True)
-    g_cw, g_cb = ops.causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc, dxz[:, :D], Bsz, L, ws, reverse)
-    g_in = empty(2 * D, dm)
-    ops.linear_wgrad(u2, dxz, g_in.data_ptr(), ws)
+
+    def conv(pw, pb, _acc):
+        ops.causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc, dxz[:, :D], Bsz, L, ws, reverse, out=(pw, pb))
+    deliver_pair(conv, s_cw, s_cb, shapes[1], shapes[2], dev, has_flag=False)
+    ops.linear_wgrad(u2, dxz, s_in[0], ws, accumulate=bool(s_in[1]))
     if du_out is None:
         du = ops.linear_dgrad(dxz, w_in.data_ptr(), dm)
     else:
         du = ops.linear_dgrad(dxz, w_in.data_ptr(), dm, out=du_out, accumulate=True)
-    return du, (g_in, g_cw, g_cb, g_x, g_dtw, g_dtb, g_A, g_D, g_out)
+    return du, grads
 
 
 class _MambaFn(torch.autograd.Function):

@@ -19,6 +19,12 @@ data-gradient GEMMs accumulating into one buffer, not by autograd.  The LayerNor
 csrc/mamba_fusion.hip, the two Mamba layers csrc/mamba.hip (mamba.layer_forward / layer_backward), fc1 / fc2 the fp32
 implicit-GEMM linears, ln_f the row LayerNorm kernel.
 
+The node's body is the pair block_forward / block_backward, plain functions with an explicit tape; block_backward (like
+mamba.layer_backward) can write the parameter gradients in place through (device pointer, accumulate flag) destinations.
+stage_forward / stage_backward (end of the file) are the whole stage on a model walk's conventions: NHWC maps at full
+resolution, the caller's workspace, gradients into the caller's arena, the pool-swap pack of csrc/mamba_fusion.hip in place
+of pooling + swap_pack.
+
 Initialisation follows the reference's self.apply(_init_weights) to the letter: EVERY nn.Linear under the stage is redrawn
 N(0, 0.02) with a zero bias - also the four inside each Mamba, so dt_proj.bias ends up 0 and dt_proj.weight loses its
 dt_rank**-0.5 scale - LayerNorm is (1, 0) and pos_emb zeros; A_log, D and conv1d keep the Mamba layer's own initialisation.
@@ -36,7 +42,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .mamba import Mamba, layer_forward, layer_backward
+from .mamba import Mamba, deliver_pair, grad_slots, layer_forward, layer_backward
 
 F32 = torch.float32
 
@@ -53,49 +59,77 @@ def _empty(dev, *shape):
     return torch.empty(shape, dtype=F32, device=dev)
 
 
+def block_forward(blk, ws, save, x2, B, T, params):
+    """one MambaBlock on x2 [B, T * C] (contiguous) -> (out [B * T, C], tape or None).  `params`: the 24 parameters in
+    MambaBlock._params() order; `ws`: a Workspace of at least blk.workspace_bytes(B, T).  The body of _BlockFn, and what a
+    model walk calls without autograd."""
+    ln_w, ln_b, w1, b1, w2, b2 = params[:6]
+    mp = params[6:]
+    C = blk.n_embd
+    M = B * T
+    xl, mean, rstd = ops.sample_layernorm_fwd(x2, ln_w, ln_b, ws)
+    x1 = ops.linear_fwd(xl.view(M, C), w1.data_ptr(), b1.data_ptr(), C)
+    fm, tape_f = layer_forward(blk.forward_mamba, ws, False, save, x1, B, T, mp[:9])
+    bm, tape_b = layer_forward(blk.backward_mamba, ws, True, save, x1, B, T, mp[9:])
+    f2 = ops.linear_fwd(x1, w2.data_ptr(), b2.data_ptr(), C)
+    out = ops.bimamba_gate_fwd(fm, bm, f2, B, T)
+    return out, ((x2, mean, rstd, xl, fm, bm, f2, *tape_f, *tape_b) if save else None)
+
+
+def block_backward(blk, ws, tape, dout2, B, T, params, gdst=None):
+    """dout2 [B * T, C] (contiguous) -> (dx [B, T * C], the 24 parameter gradients in MambaBlock._params() order).  gdst: 24
+    (device pointer, accumulate flag) pairs in that order - the gradients are written there in place and None is returned in
+    their stead (mamba.layer_backward's convention)."""
+    x2, mean, rstd, xl, fm, bm, f2 = tape[:7]
+    tape_f, tape_b = tape[7:15], tape[15:23]
+    ln_w, w1, w2, mp = params[0], params[2], params[4], params[6:]
+    C = blk.n_embd
+    M, dev = B * T, dout2.device
+    shapes = ((T, C), (T, C), (C, C), (C,), (C, C), (C,))
+    (s_lw, s_lb, s_w1, s_b1, s_w2, s_b2), own = grad_slots(shapes, dev, None if gdst is None else gdst[:6])
+    x1 = tape_f[0]
+    dfm, dbm, df2 = ops.bimamba_gate_bwd(dout2, fm, bm, f2, B, T)
+    deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(x1, df2, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_w2, s_b2,
+                 shapes[4], shapes[5], dev)
+    dx1 = ops.linear_dgrad(df2, w2.data_ptr(), C)               # the two Mamba layers add their input gradients to it
+    _, g_f = layer_backward(blk.forward_mamba, ws, False, B, T, tape_f, mp[:9], dfm, du_out=dx1,
+                            gdst=None if gdst is None else gdst[6:15])
+    _, g_b = layer_backward(blk.backward_mamba, ws, True, B, T, tape_b, mp[9:], dbm, du_out=dx1,
+                            gdst=None if gdst is None else gdst[15:24])
+    deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(xl.view(M, C), dx1, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_w1,
+                 s_b1, shapes[2], shapes[3], dev)
+    dxl = ops.linear_dgrad(dx1, w1.data_ptr(), C)
+    dx = None
+
+    def ln1_bwd(pw, pb, acc):
+        nonlocal dx
+        dx = ops.sample_layernorm_bwd(dxl.view(B, T * C), x2, mean, rstd, ln_w, pw, pb, ws, accumulate=bool(acc))
+    deliver_pair(ln1_bwd, s_lw, s_lb, shapes[0], shapes[1], dev)
+    return dx, (None if gdst is not None else (*own, *g_f, *g_b))
+
+
 class _BlockFn(torch.autograd.Function):
     """the whole MambaBlock; inputs after x: ln1.weight, ln1.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, the nine
     parameters of forward_mamba, the nine of backward_mamba"""
 
     @staticmethod
-    def forward(ctx, blk, save, x, ln_w, ln_b, w1, b1, w2, b2, *mp):
+    def forward(ctx, blk, save, x, *params):
         B, T, C = x.shape
-        M = B * T
         ws = blk._workspace(x.device, B, T)
-        x2 = x.detach().reshape(B, T * C).contiguous()
-        xl, mean, rstd = ops.sample_layernorm_fwd(x2, ln_w, ln_b, ws)
-        x1 = ops.linear_fwd(xl.view(M, C), w1.data_ptr(), b1.data_ptr(), C)
-        fm, tape_f = layer_forward(blk.forward_mamba, ws, False, save, x1, B, T, mp[:9])
-        bm, tape_b = layer_forward(blk.backward_mamba, ws, True, save, x1, B, T, mp[9:])
-        f2 = ops.linear_fwd(x1, w2.data_ptr(), b2.data_ptr(), C)
-        out = ops.bimamba_gate_fwd(fm, bm, f2, B, T)
+        out, tape = block_forward(blk, ws, save, x.detach().reshape(B, T * C).contiguous(), B, T, params)
         if save:
             ctx.blk, ctx.dims = blk, (B, T, C)
-            ctx.save_for_backward(x2, mean, rstd, xl, fm, bm, f2, ln_w, w1, w2, *tape_f, *tape_b, *mp)
+            ctx.save_for_backward(*tape, *params)
         return out.view(B, T, C)
 
     @staticmethod
     def backward(ctx, dout):
         st = ctx.saved_tensors
-        x2, mean, rstd, xl, fm, bm, f2, ln_w, w1, w2 = st[:10]
-        tape_f, tape_b, mp = st[10:18], st[18:26], st[26:]
         blk = ctx.blk
         B, T, C = ctx.dims
-        M, dev = B * T, dout.device
-        ws = blk._workspace(dev, B, T)
-        x1 = tape_f[0]
-        dfm, dbm, df2 = ops.bimamba_gate_bwd(dout.reshape(M, C).contiguous(), fm, bm, f2, B, T)
-        g_w2, g_b2 = _empty(dev, C, C), _empty(dev, C)
-        ops.linear_wgrad(x1, df2, g_w2.data_ptr(), ws, dbias_ptr=g_b2.data_ptr())
-        dx1 = ops.linear_dgrad(df2, w2.data_ptr(), C)           # the two Mamba layers add their input gradients to it
-        _, g_f = layer_backward(blk.forward_mamba, ws, False, B, T, tape_f, mp[:9], dfm, du_out=dx1)
-        _, g_b = layer_backward(blk.backward_mamba, ws, True, B, T, tape_b, mp[9:], dbm, du_out=dx1)
-        g_w1, g_b1 = _empty(dev, C, C), _empty(dev, C)
-        ops.linear_wgrad(xl.view(M, C), dx1, g_w1.data_ptr(), ws, dbias_ptr=g_b1.data_ptr())
-        dxl = ops.linear_dgrad(dx1, w1.data_ptr(), C)
-        g_lw, g_lb = _empty(dev, T, C), _empty(dev, T, C)
-        dx = ops.sample_layernorm_bwd(dxl.view(B, T * C), x2, mean, rstd, ln_w, g_lw, g_lb, ws)
-        return (None, None, dx.view(B, T, C), g_lw, g_lb, g_w1, g_b1, g_w2, g_b2, *g_f, *g_b)
+        ws = blk._workspace(dout.device, B, T)
+        dx, grads = block_backward(blk, ws, st[:23], dout.reshape(B * T, C).contiguous(), B, T, st[23:])
+        return (None, None, dx.view(B, T, C), *grads)
 
 
 class MambaBlock(nn.Module):
@@ -115,8 +149,11 @@ class MambaBlock(nn.Module):
         self.backward_mamba = Mamba(d_model=n_embd, d_state=d_state, d_conv=d_conv, expand=expand, device=device)
         self._ws = {}
 
+    def workspace_bytes(self, B, T):
+        return max(self.forward_mamba.workspace_bytes(B, T), ops.sample_layernorm_workspace_bytes(B, T * self.n_embd))
+
     def _workspace(self, device, B, T):
-        need = max(self.forward_mamba.workspace_bytes(B, T), ops.sample_layernorm_workspace_bytes(B, T * self.n_embd))
+        need = self.workspace_bytes(B, T)
         key = (device.index, ops._stream())
         ws = self._ws.get(key)
         if ws is None or ws.nbytes < need:
@@ -279,3 +316,62 @@ class MambaFusion(nn.Module):
                 x = _BlockFn.apply(blk, save, x, *bp)
             x = _LnFFn.apply(self, save, x, self.ln_f.weight, self.ln_f.bias)
             return _UnpackFn.apply(B, S, x)
+
+
+# ---- the stage on a model walk's conventions ---------------------------------------------------------------------------
+# The walk keeps the three modality maps NHWC [B * S, H, H, C] at full resolution and owns every buffer, the scratch and
+# the gradient destinations.  stage_forward / stage_backward are MambaFusion.forward without autograd on those conventions:
+# the pool-swap pack (csrc/mamba_fusion.hip) in place of adaptive pooling + swap_pack, the blocks, ln_f on the row kernel,
+# and the grouped upsample-add of the GPT stages in place of unpack + interpolate + add (the unpack does not undo the swap,
+# so that kernel is right as it stands; at H = 8 its weights are exactly 1 and it is the plain add).
+def stage_workspace_bytes(fus, B):
+    return fus.mambablocks[0].workspace_bytes(B, fus.n_tokens)
+
+
+def _stage_ws(fus, ws, B):
+    need = stage_workspace_bytes(fus, B)
+    if ws.nbytes < need:
+        raise ValueError(f"Mamba stage: the workspace has {ws.nbytes} bytes, B = {B} needs {need}")
+
+
+def stage_forward(fus, ws, save, feats, gemb, outs, B, drop=(0.0, 0, 0), w=None):
+    """feats: the three NHWC maps [B * S, H, H, C]; gemb [B, 2, C]: the embedded gps rows; outs: three maps like feats that
+    receive feats[m] + the bilinear upsampling of modality m's output tokens; drop = (p, seed, seed_off) of the embedding
+    dropout; w(p): device pointer of parameter p (default: where p.data lives).  -> (tokens after ln_f [B * T, C], tape or
+    None)"""
+    _stage_ws(fus, ws, B)
+    w = w or (lambda p: p.data_ptr())
+    S, C, T = fus.seq_len, fus.n_embd, fus.n_tokens
+    x = torch.empty((B, T, C), dtype=F32, device=gemb.device)
+    ops.pool_swap_tokens_fwd(feats, gemb, w(fus.pos_emb), x, S, *drop)
+    x = x.view(B, T * C)
+    tapes = []
+    for blk in fus.mambablocks:
+        x, tp = block_forward(blk, ws, save, x.view(B, T * C), B, T, blk._params())
+        tapes.append(tp)
+    x = x.view(B * T, C)
+    xo, mf, rf = ops.layernorm_fwd(x, w(fus.ln_f.weight), w(fus.ln_f.bias), fus.ln_f.eps)
+    ops.upsample_add_fwd3(feats, xo, outs, (S, S, S), (0, S * 64, 2 * S * 64), T)
+    return xo, ((tapes, x, mf, rf, drop) if save else None)
+
+
+def stage_backward(fus, ws, tape, dfeats_out, dgps_tok, dfeats, dgemb, B, g, w=None):
+    """dfeats_out: gradients of the three output maps; dgps_tok = (tensor, bcast): gradient of the two gps rows of the
+    stage's output tokens, [B, 2, C] or (bcast) one [B, C] row for both; g(p) -> (device pointer, accumulate flag) of
+    parameter p's gradient.  Writes dfeats (three maps: dfeats_out[m] + the pooled-token gradient; may be dfeats_out
+    themselves) and dgemb [B, 2, C]; every parameter gradient of the stage goes to its g(p)."""
+    _stage_ws(fus, ws, B)
+    w = w or (lambda p: p.data_ptr())
+    tapes, x_last, mf, rf, drop = tape
+    S, C, T = fus.seq_len, fus.n_embd, fus.n_tokens
+    dxo = torch.empty((B * T, C), dtype=F32, device=dgemb.device)
+    ops.upsample_add_bwd3(dfeats_out, dxo, (S, S, S), (0, S * 64, 2 * S * 64), T)
+    gsrc, bcast = dgps_tok
+    ops.lib().gps_rows(gsrc.data_ptr(), dxo.data_ptr(), B, C, T, 1, 0, int(bcast), ops._stream())
+    (gfw, af), (gfb, ab) = g(fus.ln_f.weight), g(fus.ln_f.bias)
+    assert af == ab, "ln_f.weight and ln_f.bias gradients must share one accumulate flag"
+    dx = ops.layernorm_bwd(dxo, x_last, mf, rf, w(fus.ln_f.weight), gfw, gfb, ws, accumulate=bool(af))
+    for blk, tp in zip(reversed(list(fus.mambablocks)), reversed(tapes)):
+        dx, _ = block_backward(blk, ws, tp, dx.view(B * T, C), B, T, blk._params(), gdst=[g(p) for p in blk._params()])
+    gpos, apos = g(fus.pos_emb)
+    ops.pool_swap_tokens_bwd(dx.view(B, T, C), dfeats_out, dfeats, dgemb, gpos, apos, S, *drop)

@@ -949,6 +949,15 @@ def _vec(t, *shape):
     return t.data_ptr()
 
 
+def _dst(t, *shape):
+    """a gradient destination: the caller's fp32 tensor of this many elements, or a raw 16-byte aligned device pointer (a
+    slice of a gradient arena) -> the pointer"""
+    if isinstance(t, int):
+        assert t and t % 16 == 0, t
+        return t
+    return _vec(t, *shape)
+
+
 def _prod(shape):
     n = 1
     for s in shape:
@@ -978,16 +987,18 @@ def causal_conv1d_silu_fwd(x, w, bias, B, L, reverse=False):
     return y
 
 
-def causal_conv1d_silu_bwd(x, w, bias, dy, dx, B, L, ws: Workspace, reverse=False):
-    """-> (dw (D, 1, 4), dbias (D,)); dx [B*L, D] is written in place (a column block allowed)"""
+def causal_conv1d_silu_bwd(x, w, bias, dy, dx, B, L, ws: Workspace, reverse=False, out=None):
+    """-> (dw (D, 1, 4), dbias (D,)); dx [B*L, D] is written in place (a column block allowed).  out: the caller's (dw, dbias)
+    tensors or device pointers, written (not added to) instead of two fresh tensors"""
     M, D = x.shape
     assert M == B * L and D % 128 == 0
     assert ws.nbytes >= int(lib().causal_conv1d_workspace_bytes(B, L, D)), "workspace too small for causal_conv1d_silu_bwd"
-    dw = torch.empty((D, 1, 4), dtype=F32, device=x.device)
-    db = torch.empty((D,), dtype=F32, device=x.device)
+    if out is None:
+        out = (torch.empty((D, 1, 4), dtype=F32, device=x.device), torch.empty((D,), dtype=F32, device=x.device))
+    dw, db = out
     lib().causal_conv1d_silu_bwd(_p(x), _rows_al(x, M, D), _vec(w, D, 1, 4), _vec(bias, D), _p(dy), _rows_al(dy, M, D),
-                                 _p(dx), _rows_al(dx, M, D), _p(dw), _p(db), B, L, D, int(reverse), ws.ptr, ws.nbytes,
-                                 _stream())
+                                 _p(dx), _rows_al(dx, M, D), _dst(dw, D, 1, 4), _dst(db, D), B, L, D, int(reverse), ws.ptr,
+                                 ws.nbytes, _stream())
     return dw, db
 
 
@@ -1007,22 +1018,23 @@ def selective_scan_fwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, B, L, ws: Wo
 
 
 def selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, du, ddelta, dBm, dCm, dz, B, L,
-                       ws: Workspace, reverse=False):
+                       ws: Workspace, reverse=False, out=None):
     """writes du, ddelta (= d delta_raw), dz [B*L, D] and dBm, dCm [B*L, 16] in place (column blocks allowed)
-    -> (dA_log (D, 16), dD (D,))"""
+    -> (dA_log (D, 16), dD (D,)).  out: the caller's (dA_log, dD) tensors or device pointers, written (not added to)"""
     M, D = u.shape
     assert M == B * L and D % 128 == 0
     assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_bwd"
     assert saved.dtype == F32 and saved.is_cuda and saved.is_contiguous() and \
         saved.numel() == int(lib().selective_scan_saved_floats(B, L, D)), tuple(saved.shape)
-    dA = torch.empty((D, 16), dtype=F32, device=u.device)
-    dD = torch.empty((D,), dtype=F32, device=u.device)
+    if out is None:
+        out = (torch.empty((D, 16), dtype=F32, device=u.device), torch.empty((D,), dtype=F32, device=u.device))
+    dA, dD = out
     lib().selective_scan_bwd(_p(u), _rows_al(u, M, D), _p(delta_raw), _rows_al(delta_raw, M, D), _vec(dt_bias, D),
                              _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16), _vec(Dp, D),
                              _p(z), _rows_al(z, M, D), _p(dy), _rows_al(dy, M, D), _p(saved), _p(du), _rows_al(du, M, D),
                              _p(ddelta), _rows_al(ddelta, M, D), _p(dBm), _rows_al(dBm, M, 16), _p(dCm),
-                             _rows_al(dCm, M, 16), _p(dz), _rows_al(dz, M, D), _p(dA), _p(dD), B, L, D, int(reverse),
-                             ws.ptr, ws.nbytes, _stream())
+                             _rows_al(dCm, M, 16), _p(dz), _rows_al(dz, M, D), _dst(dA, D, 16), _dst(dD, D), B, L, D,
+                             int(reverse), ws.ptr, ws.nbytes, _stream())
     return dA, dD
 
 
@@ -1046,7 +1058,8 @@ def sample_layernorm_fwd(x, gamma, beta, ws: Workspace, eps=1e-5):
 
 
 def sample_layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, ws: Workspace, accumulate=False):
-    """-> dx [B, n]; dgamma / dbeta (n elements each, the caller's tensors) are written, or added to when accumulate"""
+    """-> dx [B, n]; dgamma / dbeta (n elements each, the caller's tensors or device pointers) are written, or added to when
+    accumulate"""
     B, n = x.shape
     _chk(x)
     _chk(dy, B, n)
@@ -1054,7 +1067,7 @@ def sample_layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, ws: Workspace,
     _chk(rstd, B)
     assert n % 4 == 0 and ws.nbytes >= sample_layernorm_workspace_bytes(B, n), (B, n, ws.nbytes)
     dx = torch.empty_like(x)
-    lib().sample_layernorm_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _vec(gamma, n), _p(dx), _vec(dgamma, n), _vec(dbeta, n), B, n,
+    lib().sample_layernorm_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _vec(gamma, n), _p(dx), _dst(dgamma, n), _dst(dbeta, n), B, n,
                                int(accumulate), ws.ptr, ws.nbytes, _stream())
     return dx
 
@@ -1113,6 +1126,47 @@ def swap_pack_bwd(dtokens, B, S, drop_p=0.0, seed=0, seed_off=0):
     lib().swap_pack_bwd(_p(dtokens), _p(dmaps[0]), _p(dmaps[1]), _p(dmaps[2]), _p(dgps), _p(dpos), B, S, C, float(drop_p), seed,
                         seed_off, _stream())
     return (*dmaps, dgps, dpos)
+
+
+def _pool_swap_descs(ins, outs, S, C):
+    """descriptor array of the pool-swap pack: three fp32 NHWC maps [B * S, H, H, C] (ins[m] may be None) -> (descs, B, H)"""
+    ref = outs[0] if outs is not None else ins[0]
+    N, H, _, _ = ref.shape
+    assert len(ins) == 3 and (outs is None or len(outs) == 3) and S >= 1 and N % S == 0, (len(ins), N, S)
+    assert H % 8 == 0 and 8 <= H <= 64 and C % 4 == 0 and 4 <= C <= 512, (H, C)
+    descs = (_MapDesc * 3)()
+    for m in range(3):
+        for t in (ins[m], outs[m] if outs is not None else None):
+            if t is not None:
+                _chk(t, N, H, H, C)
+                assert t.data_ptr() % 16 == 0
+        descs[m].inp, descs[m].out = _p(ins[m]), _p(outs[m]) if outs is not None else 0
+        descs[m].frames_per_sample, descs[m].mod_off = S, m * S * 64
+    return descs, N // S, H
+
+
+def pool_swap_tokens_fwd(feats, gemb, pos_emb_ptr, tokens, S, drop_p=0.0, seed=0, seed_off=0):
+    """the Mamba stage's token pack on the walk's layout: tokens [B, T, C] (T = 192 S + 2) = embd_drop(pos_emb + the 8 x 8
+    average pool of the three NHWC maps feats[m] [B * S, H, H, C] with swap_pack_fwd's channel swap; the two gps rows from
+    gemb [B, 2, C]), one launch"""
+    C = feats[0].shape[3]
+    descs, B, H = _pool_swap_descs(feats, None, S, C)
+    _chk(gemb, B, 2, C)
+    _chk(tokens, B, 192 * S + 2, C)
+    lib().pool_swap_tokens_fwd(ctypes.addressof(descs), _p(gemb), pos_emb_ptr, _p(tokens), B, S, H, C, float(drop_p), seed,
+                               seed_off, _stream())
+
+
+def pool_swap_tokens_bwd(dtokens, dfeats_in, dfeats, dgemb, dpos_ptr, accumulate, S, drop_p=0.0, seed=0, seed_off=0):
+    """backward of pool_swap_tokens_fwd from dtokens [B, T, C], the mask regenerated: dfeats[q] = dfeats_in[q] (None: zero;
+    may be dfeats[q] itself) + the token gradient spread back over its windows through the inverse swap; dgemb [B, 2, C]
+    written; the (T, C) gradient of pos_emb at dpos_ptr written, or added to when `accumulate`"""
+    C = dfeats[0].shape[3]
+    descs, B, H = _pool_swap_descs(dfeats_in if dfeats_in is not None else (None,) * 3, dfeats, S, C)
+    _chk(dtokens, B, 192 * S + 2, C)
+    _chk(dgemb, B, 2, C)
+    lib().pool_swap_tokens_bwd(ctypes.addressof(descs), _p(dtokens), _p(dgemb), dpos_ptr, int(bool(accumulate)), B, S, H, C,
+                               float(drop_p), seed, seed_off, _stream())
 
 
 def token_unpack_fwd(tokens, B, S):

@@ -461,6 +461,26 @@ int ds6g_token_unpack_fwd(const float* tokens, float* image, float* lidar, float
                           void* stream);
 int ds6g_token_unpack_bwd(const float* dimage, const float* dlidar, const float* dradar, const float* dgps, float* dtokens,
                           int B, int S, int C, void* stream);
+/* The pack on the model walk's layout: the three modality maps arrive NHWC at full resolution, [B*S][H][H][C] each, as the
+ * ds6g_map_desc array of the grouped glue kernels (ds6g_types.h; frames_per_sample == S and mod_off == m * S * 64 for map m,
+ * anything else is DS6G_ERR_ARG).  H % 8 == 0, 8 <= H <= 64; C % 4 == 0, C <= 512; fp32; T = 192 S + 2.
+ *   pool_swap_tokens_fwd  maps[m].in = map m, gemb [B][2][C], pos_emb [T][C] -> tokens [B][T][C]:
+ *                             tokens[b][(m S + f) 64 + h 8 + w][c] = dropout(pos_emb + mean over the (H/8)^2 window (h, w) of
+ *                             map_q[b S + f][.][.][c]),  q = (m + seg(c)) % 3 with swap_pack_fwd's seg;
+ *                             tokens[b][T - 2 + j][c] = dropout(pos_emb + gemb[b][j][c]).
+ *                         = avgpool_tokens_fwd3 + gps_tokens_fwd + the channel swap in ONE launch, per element the same
+ *                         arithmetic; dropout counter = seed_off + flat element index of tokens (ds6g_dropout's rule, with
+ *                         the device salt of ds6g_set_dropout_salt).
+ *   pool_swap_tokens_bwd  from dtokens [B][T][C], the mask regenerated: maps[q].out = maps[q].in (dfeat_in, nullable, may
+ *                         equal out) + the masked token gradient spread over its window / (H/8)^2, the channels of segment j
+ *                         of map q taken from token modality (q - j) mod 3; dgemb [B][2][C] written; dpos_emb [T][C] = (its
+ *                         old value when accumulate_dpos, +) the sum over b in index order.  Two launches.
+ * No float atomics: two runs are bit-identical. */
+int ds6g_pool_swap_tokens_fwd(const ds6g_map_desc* maps, const float* gemb, const float* pos_emb, float* tokens, int B, int S,
+                              int H, int C, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
+int ds6g_pool_swap_tokens_bwd(const ds6g_map_desc* maps, const float* dtokens, float* dgemb, float* dpos_emb,
+                              int accumulate_dpos, int B, int S, int H, int C, float drop_p, uint64_t seed,
+                              uint64_t seed_off, void* stream);
 
 /* ---- time_mamba.hip : the temporal Mamba fusion head behind its shared Mamba layer, fp32 (mambafuser_seq.py:233-284) --
  * A sample has 17 rows of C = 512 floats: 3 modalities x S = 5 frames of the layer's output y, then its 2 gps rows.  y is
