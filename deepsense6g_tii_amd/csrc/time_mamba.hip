@@ -9,7 +9,8 @@
 // reductions go butterfly-wise through the wave, then through an LDS table across the 8 waves in wave order; the two tiny
 // linears and softmaxes are done by 4 lanes (one per softmax group) out of LDS.  No float atomics: every sum has a fixed
 // order, two runs are bit-identical.  The backward leaves the 36 parameter-gradient values of a sample in a [B][36] slab
-// (W5 25, b5 5, W2 4, b2 2) for ds6g_batch_sum.
+// (W5 25, b5 5, W2 4, b2 2) for ds6g_batch_sum, or for ds6g_temporal_param_grads, which delivers the sums to the four
+// parameters' own gradients.  Below them: the grouped head pool that feeds the head from a model walk (ds6g_pool_rows3_*).
 #include "common.h"
 
 namespace {
@@ -207,7 +208,63 @@ __global__ __launch_bounds__(TM_C) void time_attn_bwd_kernel(const float* __rest
     }
 }
 
+// The sample shares of the 36 parameter-gradient values summed over b in index order (ds6g_batch_sum's arithmetic: the sum
+// starts at 0, the old value is added last) and written to, or added to, the four parameters' own gradients.
+struct TimeParamDst {
+    float* p[4];
+    int acc[4];
+};
+
+__global__ __launch_bounds__(64) void time_param_grads_kernel(const float* __restrict__ part, int B, TimeParamDst d) {
+    const int c = threadIdx.x;
+    if (c >= TM_NP) return;
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += part[(size_t)b * TM_NP + c];
+    const int k = c < 25 ? 0 : c < 30 ? 1 : c < 34 ? 2 : 3;
+    const int i = c - (k == 0 ? 0 : k == 1 ? 25 : k == 2 ? 30 : 34);
+    float* o = d.p[k] + i;
+    if (d.acc[k]) s += *o;
+    *o = s;
+}
+
+// ---- the grouped head pool: the frames of the three 8 x 8 modality maps <-> the head's modality-major rows --------------------
+// rows[m * N + n][c] = mean over the 64 positions of map m's frame n.  One launch for the three maps (blockIdx.z = m), a
+// thread per (frame, 4 channels): 64 coalesced 16-byte loads summed in position order - ds6g_global_pool's arithmetic.
+struct PoolRows3 {
+    const float* in[3];
+    float* out[3];
+};
+
+__global__ __launch_bounds__(256) void pool_rows3_fwd_kernel(PoolRows3 g, float* __restrict__ rows, int N, int C) {
+    const int cg = C >> 2;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)N * cg) return;
+    const int m = blockIdx.z;
+    const float* __restrict__ feat = g.in[m];
+    const int c4 = (int)(i % cg) * 4;
+    const long n = i / cg;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int p = 0; p < 64; ++p) s += ld4(feat + (n * 64 + p) * C + c4);
+    st4(rows + ((long)m * N + n) * C + c4, s * (1.0f / 64.0f));
+}
+
+// out_m[n][p][c] = (in_m or 0) + drows[m * N + n][c] / 64: a thread per 16 bytes of a map, every element written exactly once
+// (in_m may be out_m: the thread that writes an element is the one that read it, so neither pointer is __restrict__)
+__global__ __launch_bounds__(256) void pool_rows3_bwd_kernel(PoolRows3 g, const float* __restrict__ drows, int N, int C) {
+    const int cg = C >> 2;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)N * 64 * cg) return;
+    const int m = blockIdx.z;
+    const int c4 = (int)(i % cg) * 4;
+    const long n = i / ((long)64 * cg);
+    f32x4 v = ld4(drows + ((long)m * N + n) * C + c4) * (1.0f / 64.0f);
+    const float* in = g.in[m];
+    if (in) v += ld4(in + i * 4);
+    st4(g.out[m] + i * 4, v);
+}
+
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool pool_rows3_dims_ok(int N, int C) { return N >= 1 && C >= 4 && C % 4 == 0 && (long)N * 64 * C <= (1L << 31); }
 inline bool tm_dims_ok(int B, int S, int C) { return B >= 1 && B <= (1 << 20) && S == TM_S && C == TM_C; }
 inline bool tm_ld_ok(long ld) { return ld >= 2 * TM_C && ld % 4 == 0; }
 
@@ -239,6 +296,42 @@ int ds6g_time_attn_bwd(const float* dout, const float* y, const float* gps, long
                    al16(dy) && al16(dgps) && al16(dparam_part));
     hipLaunchKernelGGL(time_attn_bwd_kernel, dim3(B), dim3(TM_C), 0, (hipStream_t)stream, dout, y, gps,
                        (size_t)ld_gps_sample, attn, score, argmax, w5, w2, dy, dgps, (size_t)ld_dgps_sample, dparam_part, B);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+int ds6g_temporal_param_grads(const float* dparam_part, int B, float* dw5, int acc_w5, float* db5, int acc_b5, float* dw2,
+                          int acc_w2, float* db2, int acc_b2, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(dparam_part && dw5 && db5 && dw2 && db2 && B >= 1 && B <= (1 << 20));
+    DS6G_CHECK_ARG(((uintptr_t)dparam_part & 3) == 0 && ((uintptr_t)dw5 & 3) == 0 && ((uintptr_t)db5 & 3) == 0 &&
+                   ((uintptr_t)dw2 & 3) == 0 && ((uintptr_t)db2 & 3) == 0);
+    const TimeParamDst d = {{dw5, db5, dw2, db2}, {acc_w5 != 0, acc_b5 != 0, acc_w2 != 0, acc_b2 != 0}};
+    hipLaunchKernelGGL(time_param_grads_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dparam_part, B, d);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+int ds6g_pool_rows3_fwd(const float* feat0, const float* feat1, const float* feat2, float* rows, int N, int C, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(feat0 && feat1 && feat2 && rows && pool_rows3_dims_ok(N, C));
+    DS6G_CHECK_ARG(al16(feat0) && al16(feat1) && al16(feat2) && al16(rows));
+    const PoolRows3 g = {{feat0, feat1, feat2}, {nullptr, nullptr, nullptr}};
+    hipLaunchKernelGGL(pool_rows3_fwd_kernel, dim3(cdiv((long)N * (C / 4), 256), 1, 3), dim3(256), 0, (hipStream_t)stream, g,
+                       rows, N, C);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
+int ds6g_pool_rows3_bwd(const float* drows, const float* dfeat_in0, const float* dfeat_in1, const float* dfeat_in2,
+                        float* dfeat0, float* dfeat1, float* dfeat2, int N, int C, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(drows && dfeat0 && dfeat1 && dfeat2 && pool_rows3_dims_ok(N, C));
+    DS6G_CHECK_ARG(al16(drows) && al16(dfeat_in0) && al16(dfeat_in1) && al16(dfeat_in2) && al16(dfeat0) && al16(dfeat1) &&
+                   al16(dfeat2));
+    const PoolRows3 g = {{dfeat_in0, dfeat_in1, dfeat_in2}, {dfeat0, dfeat1, dfeat2}};
+    hipLaunchKernelGGL(pool_rows3_bwd_kernel, dim3(cdiv((long)N * 64 * (C / 4), 256), 1, 3), dim3(256), 0,
+                       (hipStream_t)stream, g, drows, N, C);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }

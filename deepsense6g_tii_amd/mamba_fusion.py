@@ -34,7 +34,7 @@ the reference trains.
 Supported: fp32, HIP device only, n_embd in {64, 128, 256, 512}, d_state 16, d_conv 4, 8 x 8 anchors, config.n_views == 1 (the
 reference's cat of the three modalities only lines up then), ln_size == (T, n_embd).  Train and eval; dropout is off in eval;
 no tape is kept when no gradient is needed.  Not covered: 16-bit storage, the frozen inference engine,
-EncoderWithMamba / MambaFuser, missing-modality options (TimeMamba is time_mamba.py).
+missing-modality options (TimeMamba is time_mamba.py, the model mamba_fuser.py).
 """
 from __future__ import annotations
 

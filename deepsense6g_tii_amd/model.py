@@ -196,8 +196,8 @@ _GptRec = _record("_GptRec", "x h m1 r1 q k v y lse off_a pa off_p pr x1 h2 m2 r
 # a GPT fusion stage: blocks = its _GptRecs; x_last, mf, rf = input and statistics of ln_f
 _StageRec = _record("_StageRec", "s C T fps offs pe off_e gps_src blocks x_last mf rf fshapes")
 # the head: fused tokens, join MLP hiddens, final feature-map shapes, (join output, saved state) of the GRU head or None,
-# feature-map dtype
-_HeadRec = _record("_HeadRec", "fused h1 h2 fshapes gru fdtype")
+# feature-map dtype, the record of the fused-feature hook (_head_fwd; None for the 17-token sum)
+_HeadRec = _record("_HeadRec", "fused h1 h2 fshapes gru fdtype hook")
 # a whole training forward: stems / stages per trunk / stage, layers[stage][trunk] = [_BlockRec]; walk = the _Walk it ran
 # under (the backward walk takes weights and storage from there, whatever forward ran in between)
 _Tape = _record("_Tape", "B stems layers stages head gps salt walk")
@@ -301,7 +301,7 @@ class TransFuser(nn.Module):
         self.device = torch.device(device)
         self.config = config
         self.pred_len = getattr(config, "pred_len", 4)
-        self.encoder = Encoder(config)
+        self.encoder = self._make_encoder(config)
         self.join = nn.Sequential(nn.Linear(512, 256), nn.ReLU(inplace=True), nn.Linear(256, 128),
                                   nn.ReLU(inplace=True), nn.Linear(128, 64))
         # the 30->5 variant (model2_seq_30to5.py:842-843) appends an autoregressive GRU head; TransFuser30to5 sets this
@@ -349,6 +349,10 @@ class TransFuser(nn.Module):
         if self.device.type == "cuda":
             lib()  # fail loudly now if the HIP library is missing
             self._build_arena()
+
+    def _make_encoder(self, config):
+        """the parameter container behind self.encoder (a subclass with other fusion stages builds its own)"""
+        return Encoder(config)
 
     def load_pretrained_weight(self):  # model2_seq.py:875-878
         self.load_state_dict(torch.load("mamba_fusion.pth", weights_only=True))
@@ -1055,18 +1059,8 @@ class TransFuser(nn.Module):
             stage_ctx.append(sc)
             C, T = sc.C, sc.T
             gps_src = (xo, xo.data_ptr() + (T - 2) * C * 4, 2, T * C, C)
-        # head: global pool, 17-token sum, join MLP
-        C, T = 512, stage_ctx[-1].T
-        pooled = []
-        for m in range(3):
-            N = feats[m].shape[0]
-            assert feats[m].shape[1:] == (8, 8, 512)
-            pl = torch.empty((N, 512), dtype=F32, device=self.device)
-            ops.global_pool(feats[m], pl)
-            pooled.append(pl)
-        fused = torch.empty((B, 512), dtype=F32, device=self.device)
-        L.head_sum(pooled[0].data_ptr(), pooled[1].data_ptr(), pooled[2].data_ptr(), xo.data_ptr(), fused.data_ptr(), B,
-                   512, cfg.n_views * S, S, T, st)
+        # head: fused features (global pool + 17-token sum), join MLP
+        fused, head_rec = self._head_fwd(wk, feats, xo, B, stage_ctx[-1].T)
         if cap is not None:
             cap["fused"] = fused.clone()
         j0, j2, j4 = self.join[0], self.join[2], self.join[4]
@@ -1089,9 +1083,40 @@ class TransFuser(nn.Module):
             logits = pred
         tape = None
         if record:
-            head = _HeadRec(fused, h1, h2, [f.shape for f in feats], gru, feats[0].dtype)
+            head = _HeadRec(fused, h1, h2, [f.shape for f in feats], gru, feats[0].dtype, head_rec)
             tape = _Tape(B, stem_ctx, layer_ctx, stage_ctx, head, gps, self._salt_cur if train else None, wk)
         return logits, tape
+
+    def _head_fwd(self, wk, feats, xo, B, T):
+        """the fused features of the head: global pool of the three final maps, then the sum of their frames and of the two
+        gps rows of the last stage's tokens xo [B * T, 512] (17 rows per sample at seq_len 5) -> (fused [B, 512], the
+        record that _head_bwd gets back through the tape: None here)"""
+        cfg = self.config
+        S = cfg.seq_len
+        pooled = []
+        for m in range(3):
+            N = feats[m].shape[0]
+            assert feats[m].shape[1:] == (8, 8, 512)
+            pl = torch.empty((N, 512), dtype=F32, device=self.device)
+            ops.global_pool(feats[m], pl)
+            pooled.append(pl)
+        fused = torch.empty((B, 512), dtype=F32, device=self.device)
+        lib().head_sum(pooled[0].data_ptr(), pooled[1].data_ptr(), pooled[2].data_ptr(), xo.data_ptr(), fused.data_ptr(), B,
+                       512, cfg.n_views * S, S, T, ops._stream())
+        return fused, None
+
+    def _head_bwd(self, wk, head, dfused, B):
+        """mirror of _head_fwd: dfused [B, 512] -> (gradients of the three final maps, dgps_tok = (tensor, bcast): the gradient
+        of the two gps rows of the last stage's output tokens as _stage_bwd takes it)"""
+        cfg = self.config
+        S = cfg.seq_len
+        dfeats = []
+        for m in range(3):
+            d = torch.empty(tuple(head.fshapes[m]), dtype=head.fdtype, device=self.device)
+            fps = cfg.n_views * S if m == 0 else S
+            ops.head_bwd(dfused, d, fps)
+            dfeats.append(d)
+        return dfeats, (dfused, True)
 
     # ================================================================ backward walk =============
     def _conv_wgrad(self, wk, conv, x, dy, R, stride):
@@ -1385,13 +1410,7 @@ class TransFuser(nn.Module):
         small_bwd(j0, dh1, h1, fused, dfused, B, 256, 512)
         self._milestone_done(0)
         trunks = self._trunks()
-        dfeats = []
-        for m in range(3):
-            d = torch.empty(tuple(fshapes[m]), dtype=fdtype, device=self.device)
-            fps = cfg.n_views * S if m == 0 else S
-            ops.head_bwd(dfused, d, fps)
-            dfeats.append(d)
-        dgps = (dfused, True)
+        dfeats, dgps = self._head_bwd(wk, head, dfused, B)
         for s in range(4, 0, -1):
             dfeats, dprev = self._stage_bwd(wk, tape.stages[s - 1], dfeats, dgps, B)
             self._milestone_done(1 + 2 * (4 - s))

@@ -1219,10 +1219,11 @@ def time_attn_fwd(y, gps, w5, b5, w2, b2, B):
     return out, attn, score, argmax
 
 
-def time_attn_bwd(dout, y, gps, attn, score, argmax, w5, w2, B, dparams=None, accumulate=False):
+def time_attn_bwd(dout, y, gps, attn, score, argmax, w5, w2, B, dparams=None, accumulate=False, dst=None):
     """-> (dy [3*B*5, 512], dgps [B, 2, 512], dparams): dparams is ONE 36-float tensor (the caller's when given; added to when
     accumulate) holding dmlp.0.weight [:25], dmlp.0.bias [25:30], dmlp_gps.0.weight [30:34], dmlp_gps.0.bias [34:36], the
-    per-sample shares summed over b in index order"""
+    per-sample shares summed over b in index order.  dst: four (device pointer, accumulate flag) pairs in that order - the
+    same sums go straight to those destinations (one launch) and dparams is None"""
     _chk(dout, B, 512)
     _chk(y, 3 * B * 5, 512)
     _chk(attn, B, TIME_ROWS)
@@ -1233,11 +1234,45 @@ def time_attn_bwd(dout, y, gps, attn, score, argmax, w5, w2, B, dparams=None, ac
     dy = torch.empty((3 * B * 5, 512), dtype=F32, device=dev)
     dgps = torch.empty((B, 2, 512), dtype=F32, device=dev)
     part = torch.empty((B, TIME_PARAM_VALUES), dtype=F32, device=dev)
-    if dparams is None:
+    if dst is not None:
+        assert dparams is None and not accumulate and len(dst) == 4 and all(int(p) and int(p) % 4 == 0 for p, _ in dst), dst
+    elif dparams is None:
         assert not accumulate
         dparams = torch.empty(TIME_PARAM_VALUES, dtype=F32, device=dev)
     st = _stream()
     lib().time_attn_bwd(_p(dout), _p(y), _p(gps), ld, _p(attn), _p(score), _p(argmax), _vec(w5, 5, 5), _vec(w2, 2, 2), _p(dy),
                         _p(dgps), 1024, _p(part), B, 5, 512, st)
+    if dst is not None:
+        lib().temporal_param_grads(_p(part), B, *(v for p, a in dst for v in (int(p), int(bool(a)))), st)
+        return dy, dgps, None
     lib().batch_sum(_p(part), _vec(dparams, TIME_PARAM_VALUES), TIME_PARAM_VALUES, B, TIME_PARAM_VALUES, int(accumulate), st)
     return dy, dgps, dparams
+
+
+def pool_rows3_fwd(feats, rows):
+    """rows [3 * N, C] (modality-major: map m's frame n is row m * N + n) = the mean over the 64 positions of the three fp32
+    NHWC maps feats[m] [N, 8, 8, C], one launch"""
+    assert len(feats) == 3
+    N, _, _, C = feats[0].shape
+    for f in feats:
+        _chk(f, N, 8, 8, C)
+    _chk(rows, 3 * N, C)
+    assert C % 4 == 0 and N >= 1, (N, C)
+    lib().pool_rows3_fwd(_p(feats[0]), _p(feats[1]), _p(feats[2]), _p(rows), N, C, _stream())
+    return rows
+
+
+def pool_rows3_bwd(drows, dfeats_in, dfeats):
+    """backward of pool_rows3_fwd: dfeats[m] [N, 8, 8, C] = (dfeats_in[m] or 0) + drows[m * N + n] / 64 at every position, one
+    launch; dfeats_in: None, or three maps each of which may be None or dfeats[m] itself"""
+    assert len(dfeats) == 3
+    dfeats_in = (None,) * 3 if dfeats_in is None else dfeats_in
+    assert len(dfeats_in) == 3
+    N, _, _, C = dfeats[0].shape
+    for t in (*dfeats, *dfeats_in):
+        if t is not None:
+            _chk(t, N, 8, 8, C)
+    _chk(drows, 3 * N, C)
+    assert C % 4 == 0 and N >= 1, (N, C)
+    lib().pool_rows3_bwd(_p(drows), *(_p(t) for t in dfeats_in), *(_p(t) for t in dfeats), N, C, _stream())
+    return dfeats

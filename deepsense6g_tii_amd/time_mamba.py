@@ -21,7 +21,7 @@ Parameters keep torch's and the Mamba layer's own initialisation (the reference 
 mlp_gps are parameter holders: the arithmetic is the HIP kernels'.
 
 Supported: fp32, HIP device only, d_model 512, d_state 16, d_conv 4, 5 frames.  Train and eval; no tape is kept when no
-gradient is needed.  Not covered: 16-bit storage, the frozen inference engine, EncoderWithMamba / MambaFuser.
+gradient is needed.  Not covered: 16-bit storage, the frozen inference engine.  The model that calls the pair is mamba_fuser.py.
 """
 from __future__ import annotations
 
@@ -52,14 +52,21 @@ def time_mamba_forward(mod, ws, save, rows, gps, ld_gps_sample, B, params=None):
     return out, ((*ltape, y, attn, score, argmax) if save else None)
 
 
-def time_mamba_backward(mod, ws, tape, dout, gps, ld_gps_sample, B, params=None):
+def time_mamba_backward(mod, ws, tape, dout, gps, ld_gps_sample, B, params=None, gdst=None):
     """dout [B, 512] (contiguous) -> (drows [3*B*5, 512] in rows' layout, dgps [B, 2, 512], the 13 parameter gradients in
-    TimeMamba._params() order)"""
+    TimeMamba._params() order).  gdst: 13 (device pointer, accumulate flag) pairs in that order - the gradients are written
+    there in place (added where the flag is set) and None is returned in their stead (mamba.layer_backward's convention)."""
     params = mod._params() if params is None else params
     ltape, (y, attn, score, argmax) = tape[:8], tape[8:]
-    dy, dgps, dp = ops.time_attn_bwd(dout, y, _gps_view(gps, ld_gps_sample, B), attn, score, argmax, params[9], params[11], B)
-    drows, g_layer = layer_backward(mod.mamba, ws, False, 3 * B, FRAMES, ltape, params[:9], dy)
-    return drows, dgps, (*g_layer, dp[:25].view(5, 5), dp[25:30], dp[30:34].view(2, 2), dp[34:36])
+    gv = _gps_view(gps, ld_gps_sample, B)
+    if gdst is None:
+        dy, dgps, dp = ops.time_attn_bwd(dout, y, gv, attn, score, argmax, params[9], params[11], B)
+        drows, g_layer = layer_backward(mod.mamba, ws, False, 3 * B, FRAMES, ltape, params[:9], dy)
+        return drows, dgps, (*g_layer, dp[:25].view(5, 5), dp[25:30], dp[30:34].view(2, 2), dp[34:36])
+    assert len(gdst) == 13, len(gdst)
+    dy, dgps, _ = ops.time_attn_bwd(dout, y, gv, attn, score, argmax, params[9], params[11], B, dst=gdst[9:])
+    drows, _ = layer_backward(mod.mamba, ws, False, 3 * B, FRAMES, ltape, params[:9], dy, gdst=gdst[:9])
+    return drows, dgps, None
 
 
 class _TimeFn(torch.autograd.Function):

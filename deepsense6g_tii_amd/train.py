@@ -502,6 +502,8 @@ class CapturedTrainStep:
     Single process only (the data-parallel all-reduce stays on the eager path)."""
 
     def __init__(self, model, optimizer, batch, ema=None, warmup=2):
+        if not getattr(model, "GRAPH_CAPTURE", True):
+            raise NotImplementedError(f"CapturedTrainStep: graph replay of the {type(model).__name__} walk is not supported")
         if model.grad_ready_hook is not None:
             if getattr(optimizer, "_overlap", None) is not None:
                 raise RuntimeError("CapturedTrainStep: FusedAdamW.enable_overlap() is active (per-bucket updates issued from "

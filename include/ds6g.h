@@ -507,6 +507,21 @@ int ds6g_time_attn_fwd(const float* y, const float* gps, long ld_gps_sample, con
 int ds6g_time_attn_bwd(const float* dout, const float* y, const float* gps, long ld_gps_sample, const float* attn,
                        const float* score, const int* argmax, const float* w5, const float* w2, float* dy, float* dgps,
                        long ld_dgps_sample, float* dparam_part, int B, int S, int C, void* stream);
+/* temporal_param_grads (behind time_attn_bwd): dparam_part [B][36] summed over b in index order with ds6g_batch_sum's arithmetic and delivered to the
+ * four parameters' own gradients dw5 [25], db5 [5], dw2 [4], db2 [2] (4-byte aligned, e.g. slices of a gradient arena), each
+ * written, or added to where its acc_* flag is set.  One launch; a null pointer or B < 1 is DS6G_ERR_ARG. */
+int ds6g_temporal_param_grads(const float* dparam_part, int B, float* dw5, int acc_w5, float* db5, int acc_b5, float* dw2,
+                          int acc_w2, float* db2, int acc_b2, void* stream);
+/* The grouped head pool between the three fp32 NHWC maps [N][8][8][C] of the last stage (three independent base pointers) and
+ * the head's modality-major rows [3 N][C]; one launch each way in place of three ds6g_global_pool / ds6g_head_bwd launches.
+ * N >= 1, C % 4 == 0, N * 64 * C <= 2^31, all pointers 16-byte aligned; anything else is DS6G_ERR_ARG before anything is
+ * launched.  Memory-bound: 16-byte loads and stores, no atomics, fixed summation order (two runs are bit-identical).
+ *   pool_rows3_fwd  rows[m N + n][c] = (1 / 64) sum over the 64 positions p (in index order) of feat_m[n][p][c].
+ *   pool_rows3_bwd  dfeat_m[n][p][c] = (dfeat_in_m[n][p][c], or 0 where dfeat_in_m is null) + drows[m N + n][c] / 64; every
+ *                   element is written exactly once; dfeat_in_m may be dfeat_m itself. */
+int ds6g_pool_rows3_fwd(const float* feat0, const float* feat1, const float* feat2, float* rows, int N, int C, void* stream);
+int ds6g_pool_rows3_bwd(const float* drows, const float* dfeat_in0, const float* dfeat_in1, const float* dfeat_in2,
+                        float* dfeat0, float* dfeat1, float* dfeat2, int N, int C, void* stream);
 
 /* ---- spatial.hip-------------------------------------------------------------------------------*/
 /* normalize_imagenet + stack + NCHW->NHWC: model2_seq.py:36-45,481-482,491-493 */
