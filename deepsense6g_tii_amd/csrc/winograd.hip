@@ -15,6 +15,7 @@
 // global -> registers directly in fragment layout (each wave needs only its own 4 positions: nothing to share).
 // The next chunk's patch and U fragments are prefetched into registers while the MFMAs of the current chunk run.
 #include "common.h"
+#include "wino_plan.h"
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
@@ -929,6 +930,124 @@ __global__ __launch_bounds__(256) void winograd_wgrad_finish_kernel(const float*
     }
 }
 
+// ---- host: every call is PLANNED first (wino_plan.h: integer arithmetic on the shape, the workspace size and the knobs - no
+// HIP call, no pointer; ds6g_winograd_plan shows it to tests), then the plan is RUN.  DESIGN.md 3.1b has the rules.
+static_assert(WINO_ERR_ARG == DS6G_ERR_ARG && WINO_ERR_LAUNCH == DS6G_ERR_LAUNCH && WINO_ERR_WORKSPACE == DS6G_ERR_WORKSPACE &&
+              WINO_PLAIN_END == OOB_OFF && WINO_TILES == WG_TILES && WINO_KB == WG_KB && WINO_CH == WG_CH && WINO_PC_KB == PC_KB &&
+              WINO_PC_LDS_BYTES == PC_LDS_BYTES && WINO_WW_T == WW_T && WINO_WW_CB == WW_CB && WINO_WW_CB == WW_KB, "wino_plan.h");
+
+bool pc_set_lds() {
+    bool ok = true;
+#define PC_ATTR(D) ok = ok && hipFuncSetAttribute((const void*)winograd_pc_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES) == hipSuccess;
+    PC_ATTR(0)
+#ifdef DS6G_WINO_ABLATE
+    PC_ATTR(1) PC_ATTR(2) PC_ATTR(3) PC_ATTR(4) PC_ATTR(7) PC_ATTR(8) PC_ATTR(16) PC_ATTR(24) PC_ATTR(9) PC_ATTR(10) PC_ATTR(18) PC_ATTR(17) PC_ATTR(19) PC_ATTR(32) PC_ATTR(64) PC_ATTR(80) PC_ATTR(96)
+#endif
+#undef PC_ATTR
+    return ok;
+}
+
+// CU count of the calling thread's current device, with the 128 KiB dynamic-LDS attribute of winograd_pc_kernel set on
+// that device - once per device and process, safe under concurrent first calls (a process may drive several devices, one
+// thread each, as torch.nn.DataParallel callers do).  -> 0 on failure.
+int pc_device_cus() {
+    static std::mutex mu;
+    static int cus[64] = {};   // 0 = not initialised, -1 = failed
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!cus[dev]) {
+        hipDeviceProp_t prop;
+        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && pc_set_lds()) ? prop.multiProcessorCount : -1;
+    }
+    return cus[dev] > 0 ? cus[dev] : 0;
+}
+
+int wino_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+
+// The knobs of a call: the environment is read once per process, the debug flag per call.  n_cu <= 0: the CUs of the CURRENT
+// device (the LDS attribute is per device too) - asked for only where the persistent kernel would run, so a call that plans
+// another kernel cannot fail on the query; a failed query leaves 0 and the planner answers DS6G_ERR_LAUNCH.
+WinoKnobs wino_knobs(const WinoProblem& q, int n_cu) {
+    static const WinoKnobs env = [] {
+        WinoKnobs k;
+        k.pc = wino_env("DS6G_WINO_PC", k.pc);
+        k.cu_reserve = wino_env("DS6G_PC_CU_RESERVE", k.cu_reserve);
+        k.pc_xcd = wino_env("DS6G_PC_XCD", k.pc_xcd);
+        k.ww_xcd = wino_env("DS6G_WW_XCD", k.ww_xcd);
+        return k;
+    }();
+    WinoKnobs kn = env;
+    kn.kb64 = g_wino_kb64;
+    kn.n_cu = (n_cu > 0 || !wino_wants_pc(q, kn)) ? n_cu : pc_device_cus();
+    return kn;
+}
+
+// step 3 of every entry point: plan the problem (a refusal is reported and returned)
+int wino_plan_call(const WinoProblem& q, WinoPlan& pl) {
+    const int rc = wino_plan(q, wino_knobs(q, 0), &pl);
+    if (rc) fprintf(stderr, "[ds6g] wino_plan refuses op %d, N %d H %d W %d C %d K %d, workspace %zu B: code %d\n", q.op, q.N, q.H,
+                    q.W, q.C, q.K, q.ws_bytes, rc);
+    return rc;
+}
+
+// step 4 of the three conv forms: runs the plan.  bias / residual / relu: the inference epilogue (all 0: none)
+int run_conv(const WinoProblem& q, const float* x, const float* u, float* y, const float* bias, const float* residual, int relu,
+             hipStream_t st) {
+    WinoPlan pl;
+    if (const int rc = wino_plan_call(q, pl)) return rc;
+    WinoParams p{};
+    p.x = x; p.u = u; p.y = y; p.N = q.N; p.H = q.H; p.W = q.W; p.C = q.C; p.K = q.K;
+    p.TH = pl.TH; p.TW = pl.TW; p.BTH = pl.BTH; p.BTW = pl.BTW;
+    p.rows_total = pl.rows_total; p.col_blocks = pl.col_blocks;
+    p.x_bytes = pl.x_bytes; p.u_bytes = pl.u_bytes;
+    p.accumulate = q.accumulate;
+    p.bias = bias; p.residual = residual; p.relu = relu;
+    p.items = pl.items; p.xcd_gk = pl.xcd; p.btw_shift = pl.btw_shift; p.th_magic = pl.th_magic;
+    static const int dbg = wino_env("DS6G_WINO_DBG", 0);  // selects something in a -DDS6G_WINO_ABLATE build only: not planned
+    p.dbg = dbg;
+    const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z), block(pl.block);
+    void* rec = ds6g_prof_open(pl.variant, pl.flops, st);
+    if (pl.kernel == DS6G_WINO_K_PC) {
+#ifdef DS6G_WINO_ABLATE
+        static unsigned long long* tdbg = nullptr;
+        if ((p.dbg & 64) && !tdbg) { (void)hipMalloc(&tdbg, 64 * 8 * 8); }
+        p.tdbg = tdbg;
+        switch (p.dbg) {
+#define PC_CASE(D) case D: hipLaunchKernelGGL(winograd_pc_kernel<D>, grid, block, pl.lds_bytes, st, p); break;
+            PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(7) PC_CASE(8) PC_CASE(16) PC_CASE(24) PC_CASE(9) PC_CASE(10) PC_CASE(18) PC_CASE(17) PC_CASE(19) PC_CASE(32) PC_CASE(64) PC_CASE(80) PC_CASE(96)
+#undef PC_CASE
+            default: hipLaunchKernelGGL(winograd_pc_kernel<0>, grid, block, pl.lds_bytes, st, p);
+        }
+        if (p.dbg & 64) {
+            static int shown = 0;
+            if (shown++ % 64 == 3) {  // a warm launch of each shape when the caller loops a few dozen times
+                unsigned long long h[64 * 8];
+                (void)hipDeviceSynchronize();
+                (void)hipMemcpy(h, tdbg, sizeof(h), hipMemcpyDeviceToHost);
+                const int T = pl.rounds * (q.C / WG_CH);
+                fprintf(stderr, "pc steps (C=%d K=%d H=%d), cycles\n", q.C, q.K, q.H);
+                for (int t = 1; t < T && t < 64; ++t) {
+                    const long long m0 = (long long)h[(t - 1) * 8 + 3];  // mover left the previous barrier
+                    fprintf(stderr, "  %2d: step %6lld | mult work %6lld wait %6lld | mover work %6lld wait %6lld\n", t,
+                            (long long)(h[t * 8 + 1] - h[(t - 1) * 8 + 1]), (long long)(h[t * 8 + 0] - h[(t - 1) * 8 + 1]),
+                            (long long)(h[t * 8 + 1] - h[t * 8 + 0]), (long long)h[t * 8 + 2] - m0, (long long)(h[t * 8 + 3] - h[t * 8 + 2]));
+                }
+            }
+        }
+#else
+        hipLaunchKernelGGL(winograd_pc_kernel<0>, grid, block, pl.lds_bytes, st, p);
+#endif
+    } else if (pl.kernel == DS6G_WINO_K_FWD2) {
+        hipLaunchKernelGGL(winograd_fwd_kernel<2>, grid, block, 0, st, p);
+    } else {
+        hipLaunchKernelGGL(winograd_fwd_kernel<1>, grid, block, 0, st, p);
+    }
+    ds6g_prof_close(rec, st);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -946,26 +1065,26 @@ int ds6g_winograd_weights(const float* w, float* u, int K, int C, int transpose_
     return DS6G_OK;
 }
 
-// 1 if the shape is supported by ds6g_conv3x3_winograd_fwd
-int ds6g_winograd_supported(int N, int H, int W, int C, int K) {
-    if (H % 2 || W % 2 || C % WG_CH || K % WG_KB || N <= 0) return 0;
-    const int TW = W / 2;
-    if (TW >= 8 ? TW % 8 != 0 : 32 % TW != 0) return 0;
-    const size_t xb = (size_t)N * H * W * C * 4, ub = (size_t)16 * K * C * 4;
-    return xb < OOB_OFF && ub < OOB_OFF;
+// 1 if the shape is supported by ds6g_conv3x3_winograd_fwd / _bias_act_fwd
+int ds6g_winograd_supported(int N, int H, int W, int C, int K) { return wino_shape_ok(DS6G_WINO_FWD, N, H, W, C, K); }
+// 1 if ds6g_conv3x3_winograd_wgrad supports the shape
+int ds6g_winograd_wgrad_supported(int N, int H, int W, int C, int K) { return wino_shape_ok(DS6G_WINO_WGRAD, N, H, W, C, K); }
+
+// test instrumentation: the plan the entry point `op` would run on a device of n_cu CUs (<= 0: the current device), or its refusal
+int ds6g_winograd_plan(int op, int N, int H, int W, int C, int K, int accumulate, int n_cu, size_t ws_bytes,
+                       struct ds6g_wino_plan* plan) {
+    const WinoProblem q = {op, N, H, W, C, K, accumulate, ws_bytes};
+    return wino_plan(q, wino_knobs(q, n_cu), plan);
 }
 
 // y[N][H][W][K] = conv3x3 (stride 1, pad 1) of x[N][H][W][C] with the filter whose Winograd transform is u
 // (ds6g_winograd_weights; transpose_flip = 1 there turns this call into the data gradient of the same conv);
 // accumulate: y += result
-static int wino_fwd_launch(const float* x, const float* u, float* y, int N, int H, int W, int C, int K, int accumulate,
-                           const float* bias, const float* residual, int relu, void* stream);
-
 int ds6g_conv3x3_winograd_fwd(const float* x, const float* u, float* y, int N, int H, int W, int C, int K, int accumulate,
                               void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && u && y && ds6g_winograd_supported(N, H, W, C, K));
-    return wino_fwd_launch(x, u, y, N, H, W, C, K, accumulate, nullptr, nullptr, 0, stream);
+    DS6G_CHECK_ARG(x && u && y);
+    return run_conv({DS6G_WINO_FWD, N, H, W, C, K, accumulate, 0}, x, u, y, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // inference form (eval-mode BN folded into the filter by ds6g_bn_fold before ds6g_winograd_weights):
@@ -973,138 +1092,8 @@ int ds6g_conv3x3_winograd_fwd(const float* x, const float* u, float* y, int N, i
 int ds6g_conv3x3_winograd_bias_act_fwd(const float* x, const float* u, const float* bias, const float* residual, float* y,
                                        int N, int H, int W, int C, int K, int relu, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && u && y && ds6g_winograd_supported(N, H, W, C, K) && relu >= 0 && relu <= 2);
-    return wino_fwd_launch(x, u, y, N, H, W, C, K, 0, bias, residual, relu, stream);
-}
-
-static bool pc_set_lds() {
-    bool ok = true;
-#define PC_ATTR(D) ok = ok && hipFuncSetAttribute((const void*)winograd_pc_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES) == hipSuccess;
-    PC_ATTR(0)
-#ifdef DS6G_WINO_ABLATE
-    PC_ATTR(1) PC_ATTR(2) PC_ATTR(3) PC_ATTR(4) PC_ATTR(7) PC_ATTR(8) PC_ATTR(16) PC_ATTR(24) PC_ATTR(9) PC_ATTR(10) PC_ATTR(18) PC_ATTR(17) PC_ATTR(19) PC_ATTR(32) PC_ATTR(64) PC_ATTR(80) PC_ATTR(96)
-#endif
-#undef PC_ATTR
-    return ok;
-}
-
-// CU count of the calling thread's current device, with the 128 KiB dynamic-LDS attribute of winograd_pc_kernel set on
-// that device - once per device and process, safe under concurrent first calls (a process may drive several devices, one
-// thread each, as torch.nn.DataParallel callers do).  -> 0 on failure.
-static int pc_device_cus() {
-    static std::mutex mu;
-    static int cus[64] = {};   // 0 = not initialised, -1 = failed
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && pc_set_lds()) ? prop.multiProcessorCount : -1;
-    }
-    return cus[dev] > 0 ? cus[dev] : 0;
-}
-
-static int wino_fwd_launch(const float* x, const float* u, float* y, int N, int H, int W, int C, int K, int accumulate,
-                           const float* bias, const float* residual, int relu, void* stream) {
-    WinoParams p{};
-    p.x = x; p.u = u; p.y = y; p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
-    p.TH = H / 2; p.TW = W / 2;
-    p.BTW = p.TW >= 8 ? 8 : p.TW;
-    p.BTH = WG_TILES / p.BTW;
-    p.rows_total = N * p.TH;
-    p.col_blocks = p.TW / p.BTW;
-    p.x_bytes = (unsigned)((size_t)N * H * W * C * 4);
-    p.u_bytes = (unsigned)((size_t)16 * K * C * 4);
-    p.accumulate = accumulate;
-    p.bias = bias; p.residual = residual; p.relu = relu;
-    { const char* e = getenv("DS6G_WINO_DBG"); p.dbg = e ? atoi(e) : 0; }
-    const int row_blocks = (p.rows_total + p.BTH - 1) / p.BTH;
-    static const int pc_on = [] { const char* e = getenv("DS6G_WINO_PC"); return e ? atoi(e) : 1; }();
-    const bool use_pc = pc_on && K % PC_KB == 0 && C >= 2 * WG_CH && (size_t)N * H * W * C * 4 + (size_t)(W + 1) * C * 4 < 0x40000000u;
-    // CUs of the CURRENT device = persistent workgroups of winograd_pc_kernel; the LDS attribute is per device too
-    int n_cu = 0;
-    if (use_pc && (n_cu = pc_device_cus()) <= 0) return DS6G_ERR_LAUNCH;
-    // profiler variant 20000 (20002: the producer / consumer kernel): forward / data gradient; flops = those of the direct
-    // 3x3 convolution it replaces
-    void* rec = ds6g_prof_open(use_pc ? 20002 : 20000, 2.0 * N * H * W * (double)K * 9.0 * C, (hipStream_t)stream);
-    if (use_pc && K % PC_KB == 0 && C >= 2 * WG_CH) {
-        p.items = row_blocks * p.col_blocks * (K / PC_KB);
-        p.btw_shift = __builtin_ctz((unsigned)p.BTW);
-        p.th_magic = (unsigned)(((1ull << 32) + (unsigned)p.TH - 1) / (unsigned)p.TH);
-        // one persistent workgroup per CU.  DS6G_PC_CU_RESERVE=n leaves n CUs out: a workgroup needs a whole CU (all its
-        // VGPRs, 128 KiB of LDS), so when other resident kernels (RCCL channels under data parallelism) hold a few CUs, a
-        // full-size grid would run its last workgroups in a second round
-        static const int reserve = [] { const char* e = getenv("DS6G_PC_CU_RESERVE"); return e ? atoi(e) : 0; }();
-        const int cus = n_cu - reserve > 1 ? n_cu - reserve : 1;
-        // the smallest grid that needs no more rounds than all CUs would: at the model's batch (60 frames) every layer has a
-        // multiple of 240 items, so 240 workgroups are as fast as 256 (measured: 175.5 vs 176.1 samples/s) and 16 CUs stay
-        // free for whatever else is resident
-        const int rounds = (p.items + cus - 1) / cus;
-        const int grid = (p.items + rounds - 1) / rounds;
-        // XCD-aware item order (see the kernel): gk channel-block groups x gt = 8 / gk tile-block groups of XCDs; per launch the
-        // L2s then fetch about |U| gt + |x| gk bytes (every XCD of a tile-block group reads that group's x once per channel
-        // group it is in; every U slice is read by the gt XCDs that share it) - pick the minimum.  DS6G_PC_XCD=0 switches
-        // it off, 1 / 2 / 4 / 8 force gk.
-        {
-            static const int xcd_env = [] { const char* e = getenv("DS6G_PC_XCD"); return e ? atoi(e) : -1; }();
-            const int kblocks = K / PC_KB, ntb = p.items / kblocks;
-            p.xcd_gk = 0;
-            if (xcd_env != 0 && grid % 8 == 0 && p.items % grid == 0) {
-                double best = 0;
-                for (int gk = 1; gk <= 8; gk *= 2) {
-                    const int gt = 8 / gk;
-                    if (kblocks % gk || ntb % gt || (xcd_env > 0 && gk != xcd_env)) continue;
-                    const double cost = (double)p.u_bytes * gt + (double)p.x_bytes * gk;
-                    if (!p.xcd_gk || cost < best) { best = cost; p.xcd_gk = gk; }
-                }
-            }
-        }
-#ifdef DS6G_WINO_ABLATE
-        static unsigned long long* tdbg = nullptr;
-        if ((p.dbg & 64) && !tdbg) { (void)hipMalloc(&tdbg, 64 * 8 * 8); }
-        p.tdbg = tdbg;
-        switch (p.dbg) {
-#define PC_CASE(D) case D: hipLaunchKernelGGL(winograd_pc_kernel<D>, dim3((unsigned)grid), dim3(512), PC_LDS_BYTES, (hipStream_t)stream, p); break;
-            PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(7) PC_CASE(8) PC_CASE(16) PC_CASE(24) PC_CASE(9) PC_CASE(10) PC_CASE(18) PC_CASE(17) PC_CASE(19) PC_CASE(32) PC_CASE(64) PC_CASE(80) PC_CASE(96)
-#undef PC_CASE
-            default: hipLaunchKernelGGL(winograd_pc_kernel<0>, dim3((unsigned)grid), dim3(512), PC_LDS_BYTES, (hipStream_t)stream, p);
-        }
-        if (p.dbg & 64) {
-            static int shown = 0;
-            if (shown++ % 64 == 3) {  // a warm launch of each shape when the caller loops a few dozen times
-                unsigned long long h[64 * 8];
-                (void)hipDeviceSynchronize();
-                (void)hipMemcpy(h, tdbg, sizeof(h), hipMemcpyDeviceToHost);
-                const int T = ((p.items + grid - 1) / grid) * (C / WG_CH);
-                fprintf(stderr, "pc steps (C=%d K=%d H=%d), cycles\n", C, K, H);
-                for (int t = 1; t < T && t < 64; ++t) {
-                    const long long m0 = (long long)h[(t - 1) * 8 + 3];  // mover left the previous barrier
-                    fprintf(stderr, "  %2d: step %6lld | mult work %6lld wait %6lld | mover work %6lld wait %6lld\n", t,
-                            (long long)(h[t * 8 + 1] - h[(t - 1) * 8 + 1]), (long long)(h[t * 8 + 0] - h[(t - 1) * 8 + 1]),
-                            (long long)(h[t * 8 + 1] - h[t * 8 + 0]), (long long)h[t * 8 + 2] - m0, (long long)(h[t * 8 + 3] - h[t * 8 + 2]));
-                }
-            }
-        }
-#else
-        hipLaunchKernelGGL(winograd_pc_kernel<0>, dim3((unsigned)grid), dim3(512), PC_LDS_BYTES, (hipStream_t)stream, p);
-#endif
-    } else if (K % (2 * WG_KB) == 0 && g_wino_kb64) {
-        const long blocks = (long)row_blocks * p.col_blocks * (K / (2 * WG_KB));
-        hipLaunchKernelGGL(winograd_fwd_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-    } else {
-        const long blocks = (long)row_blocks * p.col_blocks * (K / WG_KB);
-        hipLaunchKernelGGL(winograd_fwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-    }
-    ds6g_prof_close(rec, (hipStream_t)stream);
-    DS6G_LAUNCH_CHECK();
-    return DS6G_OK;
-}
-
-// 1 if ds6g_conv3x3_winograd_wgrad supports the shape
-int ds6g_winograd_wgrad_supported(int N, int H, int W, int C, int K) {
-    if (H % 2 || W % 2 || C % WW_CB || K % WW_KB || N <= 0) return 0;
-    const size_t xb = (size_t)N * H * W * C * 4 + (size_t)(W + 1) * C * 4, yb = (size_t)N * H * W * K * 4;
-    return xb < 0x40000000u && yb < OOB_OFF;
+    DS6G_CHECK_ARG(x && u && y && relu >= 0 && relu <= 2);
+    return run_conv({DS6G_WINO_BIAS_ACT, N, H, W, C, K, 0, 0}, x, u, y, bias, residual, relu, (hipStream_t)stream);
 }
 
 // dw[K][3][3][C] (+)= weight gradient of the 3x3 / stride 1 / pad 1 conv from x [N][H][W][C] and dy [N][H][W][K];
@@ -1112,37 +1101,26 @@ int ds6g_winograd_wgrad_supported(int N, int H, int W, int C, int K) {
 int ds6g_conv3x3_winograd_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K,
                                 int accumulate, float* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(x && dy && dw && ws && ds6g_winograd_wgrad_supported(N, H, W, C, K));
-    const size_t slab = (size_t)16 * K * C * sizeof(float);
-    DS6G_CHECK_WS(ws_bytes >= slab);
+    DS6G_CHECK_ARG(x && dy && dw && ws);
+    const WinoProblem q = {DS6G_WINO_WGRAD, N, H, W, C, K, accumulate, ws_bytes};
+    WinoPlan pl;
+    if (const int rc = wino_plan_call(q, pl)) return rc;
     WinoWgradParams p{};
     p.x = x; p.dy = dy; p.du = ws; p.N = N; p.H = H; p.W = W; p.C = C; p.K = K;
-    p.TH = H / 2; p.TW = W / 2;
-    p.tiles_total = N * p.TH * p.TW;
-    p.x_bytes = (unsigned)((size_t)N * H * W * C * 4);
-    p.dy_bytes = (unsigned)((size_t)N * H * W * K * 4);
-    const int base = (K / WW_KB) * (C / WW_CB) * 4;
-    const int chunks = (p.tiles_total + WW_T - 1) / WW_T;
-    // ~1024 workgroups, at least 12 chunks per split, bounded by the scratch
-    long splits = (1024 + base - 1) / base;
-    if (splits > chunks / 12) splits = chunks / 12;
-    const long by_ws = (long)(ws_bytes / slab);
-    if (splits > by_ws) splits = by_ws;
-    if (splits < 1) splits = 1;
-    const int cps = (int)((chunks + splits - 1) / splits);
-    p.tiles_per_split = cps * WW_T;
-    splits = (chunks + cps - 1) / cps;
-    { static const int xcd_env = [] { const char* e = getenv("DS6G_WW_XCD"); return e ? atoi(e) : 1; }(); p.xcd = xcd_env; }
-    void* rec = ds6g_prof_open(20001, 2.0 * N * H * W * (double)K * 9.0 * C, (hipStream_t)stream);
-    hipLaunchKernelGGL(winograd_wgrad_kernel, dim3((unsigned)((K / WW_KB) * (C / WW_CB)), 4, (unsigned)splits), dim3(256), 0,
-                       (hipStream_t)stream, p);
+    p.TH = pl.TH; p.TW = pl.TW;
+    p.tiles_total = pl.tiles_total; p.tiles_per_split = pl.tiles_per_split;
+    p.x_bytes = pl.x_bytes; p.dy_bytes = pl.dy_bytes;
+    p.xcd = pl.xcd;
+    void* rec = ds6g_prof_open(pl.variant, pl.flops, (hipStream_t)stream);
+    hipLaunchKernelGGL(winograd_wgrad_kernel, dim3(pl.grid_x, pl.grid_y, pl.grid_z), dim3(pl.block), 0, (hipStream_t)stream, p);
     ds6g_prof_close(rec, (hipStream_t)stream);
     DS6G_LAUNCH_CHECK();
     const long n = (long)K * C;
     hipLaunchKernelGGL(winograd_wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)ws, dw, K, C, (int)splits, accumulate);
+                       (const float*)ws, dw, K, C, pl.splits, accumulate);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
 
 }  // extern "C"
+

@@ -154,6 +154,14 @@ int ds6g_conv3x3_winograd_bias_act_fwd(const float* x, const float* u, const flo
 int ds6g_winograd_wgrad_supported(int N, int H, int W, int C, int K);
 int ds6g_conv3x3_winograd_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K,
                                 int accumulate, float* ws, size_t ws_bytes, void* stream);
+/* test instrumentation, host arithmetic only: the launch that the Winograd entry point `op` (DS6G_WINO_FWD / _BIAS_ACT / _WGRAD,
+ * ds6g_types.h) would make for this shape, `accumulate` and workspace size on a device of n_cu compute units (<= 0: the calling
+ * thread's current device, the one case that makes a HIP call) under the process's current debug flags and environment - the
+ * entry points run what this very planner (csrc/wino_plan.h) returns - or the refusal of that call: DS6G_ERR_ARG for a shape
+ * ds6g_winograd_supported / _wgrad_supported refuses, DS6G_ERR_WORKSPACE for a weight gradient with less than one slab of
+ * 16*K*C floats, DS6G_ERR_LAUNCH where the persistent kernel is planned and no CU count is known. */
+int ds6g_winograd_plan(int op, int N, int H, int W, int C, int K, int accumulate, int n_cu, size_t ws_bytes,
+                       struct ds6g_wino_plan* plan);
 /* nn.Linear of the GPT blocks with fused epilogue y = residual + dropout(act(x w^T + b)):
  * model2_seq.py:97-99 (q,k,v), :109 (proj + resid_drop), :121-126 (MLP, ReLU), :131-132 (residuals). */
 int ds6g_linear_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int relu,

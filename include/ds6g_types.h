@@ -1,4 +1,4 @@
-/* Descriptor structs of the batched entry points of ds6g.h and the attention and GEMM launch plans, in a header of their own so that
+/* Descriptor structs of the batched entry points of ds6g.h and the attention, GEMM and Winograd launch plans, in a header of their own so that
  * the public header and the kernel sources (csrc/common.h) share ONE definition.  The host reads a caller's descriptor
  * array during the call and hands the descriptors to the kernel by value, in its arguments. */
 #ifndef DS6G_TYPES_H
@@ -90,6 +90,35 @@ struct ds6g_gemm_plan {
     int variant;                 /* what ds6g_last_igemm_variant and the profile records carry (ds6g.h) */
     size_t slab_elems;           /* Mg * Ng (+ Mg with want_colsum): the split stride, in floats */
     size_t ws_bytes_used;        /* splits * slab_elems * 4 where reduce is set; the BatchNorm partials of conv2d_fwd_bnstats; else 0 */
+};
+
+/* ---- the launch of one Winograd call, fully decided (ds6g_winograd_plan; csrc/wino_plan.h plans every call of
+ * csrc/winograd.hip with it, then the entry point runs it).  DESIGN.md 3.1b has the table of the rules. */
+enum { DS6G_WINO_FWD = 0,      /* ds6g_conv3x3_winograd_fwd: the forward; on dy and the dgrad filter the data gradient */
+       DS6G_WINO_BIAS_ACT = 1, /* ds6g_conv3x3_winograd_bias_act_fwd */
+       DS6G_WINO_WGRAD = 2 };  /* ds6g_conv3x3_winograd_wgrad */
+enum { DS6G_WINO_K_FWD1 = 0,   /* winograd_fwd_kernel<1>: one workgroup per 32 tiles x 32 output channels */
+       DS6G_WINO_K_FWD2 = 1,   /* winograd_fwd_kernel<2>: 64 output channels (debug flag 0x02000000) */
+       DS6G_WINO_K_PC = 2,     /* winograd_pc_kernel: persistent producer / consumer workgroups over 32-tile x 64-channel items */
+       DS6G_WINO_K_WGRAD = 3 };/* winograd_wgrad_kernel (+ winograd_wgrad_finish_kernel over the split slabs) */
+struct ds6g_wino_plan {
+    int op, kernel;              /* DS6G_WINO_*, DS6G_WINO_K_* */
+    int TH, TW;                  /* tiles per image column / row: H / 2, W / 2 */
+    int BTW, BTH;                /* conv forms: tile columns / rows per tile block, BTW * BTH = 32 */
+    int rows_total;              /* N * TH */
+    int row_blocks, col_blocks;  /* cdiv(rows_total, BTH), TW / BTW */
+    int items, rounds;           /* persistent kernel: tile blocks x K / 64 items in cdiv(items, CUs - reserve) rounds; else 0 */
+    int grid_x, grid_y, grid_z;  /* persistent: cdiv(items, rounds); fwd<TNK>: tile blocks x K / (32 TNK); wgrad: (K/64 C/64, 4, splits) */
+    int block, lds_bytes;        /* threads per workgroup; dynamic LDS (the persistent kernel's 128 KiB, else 0) */
+    int xcd;                     /* persistent: gk of the XCD item order (0: plain order); wgrad: the XCD-contiguous order's flag */
+    int btw_shift;               /* persistent: log2(BTW) */
+    unsigned th_magic;           /* persistent: ceil(2^32 / TH): row / TH = umulhi(row, th_magic) */
+    unsigned x_bytes, u_bytes, dy_bytes; /* sizes behind the buffer resources: x; U (conv forms); dy (wgrad) */
+    int tiles_total;             /* wgrad: N * TH * TW */
+    int splits, tiles_per_split; /* wgrad: splits of the tile range, each a multiple of 16 tiles, none empty */
+    int variant;                 /* the profile record's: 20000 winograd_fwd_kernel, 20001 wgrad, 20002 persistent */
+    double flops;                /* the profile record's: 2 N H W K 9 C, the direct convolution's */
+    size_t ws_bytes_used;        /* wgrad: splits slabs of 16 K C floats */
 };
 
 #endif /* DS6G_TYPES_H */
