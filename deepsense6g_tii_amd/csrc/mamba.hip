@@ -6,6 +6,11 @@
 //   forward and backward, in either direction.
 // Data is token-major: row = b * L + t, channels contiguous; every operand is pointer + row stride (floats), so the column
 // halves of in_proj's output and the column slices of x_proj's output are read in place.
+// Every kernel is a template on the storage type T of the WIDE activations (x, y, dy, dx of the conv; u, z, y, dy, dz of the
+// scan): float behind the fp32 entry points, __bf16 / _Float16 behind the ds6g_h16_* ones (row strides then in elements of T).
+// Parameters, delta_raw, Bm / Cm, their gradients, du, the scan state, checkpoints, slabs and all arithmetic are fp32 for every
+// T.  A 16-bit workgroup keeps the fp32 mapping - 16 channels, now 32-byte row pieces moved as two 16-byte loads and widened on
+// the way into LDS - because the scan is instruction-issue-bound, not byte-bound (DESIGN.md 3.9a has the decision).
 //
 // Scan mapping: lane = (channel, state).  The 16 states of a channel are one DPP row, so <h, C>, d delta and du are row
 // reductions without LDS; a workgroup is 16 channels x 16 states and walks ONE chunk of SCAN_CHUNK positions whose operands
@@ -53,43 +58,82 @@ __device__ __forceinline__ float sigmoid_(float v) { return 1.f / (1.f + expf(-v
 // mamba_ssm's softplus: v for v > 20, else log1p(exp(v))
 __device__ __forceinline__ float softplus_(float v) { return v > 20.f ? v : log1pf(expf(v)); }
 
+// T: the storage type of the wide activations u, z, y, dy, dz - float, or __bf16 / _Float16 on the 16-bit-storage path
+// (ds6g_h16_selective_scan_*).  Everything else, and everything held in LDS or registers, is fp32 for every T.
+template <typename T>
 struct ScanP {
-    const float *u, *raw, *dt_bias, *A_log, *Bm, *Cm, *Dp, *z, *dy;
+    const T *u, *z, *dy;
+    const float *raw, *dt_bias, *A_log, *Bm, *Cm, *Dp;
     int ld_u, ld_raw, ld_b, ld_c, ld_z, ld_dy;
-    float *y; int ld_y;
+    T *y; int ld_y;
     float *hin;      // [B][nc][D][16] states at chunk starts (slot 0 is never touched: it is zero)
     float *sumd;     // [B][nc][D]
     float *gl;       // [B][nc][D][16] gradient w.r.t. the state at chunk starts
-    float *du, *draw, *dz; int ld_du, ld_draw, ld_dz;
+    float *du, *draw; T *dz; int ld_du, ld_draw, ld_dz;
     float *slab_bc;  // [D / 16][B * L][32]
     float *slab_a;   // [B * nc][D][16]
     float *slab_d;   // [B * nc][D]
     int B, L, D, nc, rev;
 };
 
-// tile[s][0..15] <- src[row(s0 + s)][col0 .. col0 + 16), zeros for s >= len.  128 threads (part selects which half of the
-// workgroup) move one float4 each.
-__device__ __forceinline__ void stage16(float* tile, const float* __restrict__ src, int ld, size_t rowbase, int L, int s0,
-                                        int len, int rev, int col0, int part) {
-    const int i = (int)threadIdx.x - part * 128;
-    if (i < 0 || i >= 128) return;
-    const int s = i >> 2, q = i & 3;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (s < len) {
-        const int t = rev ? L - 1 - (s0 + s) : s0 + s;
-        v = ld4(src + (rowbase + t) * (size_t)ld + col0 + q * 4);
-    }
-    st4(tile + s * 16 + q * 4, v);
+// one 16-byte piece of a row as fp32: 4 floats, or 8 elements of a 16-bit type
+template <typename S> struct Piece { static constexpr int N = 16 / (int)sizeof(S); };
+__device__ __forceinline__ void ld_piece(const float* p, float (&v)[4]) {
+    const f32x4 t = ld4(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = t[e];
 }
-// dst[row(s0 + s)][col0 .. col0 + 16) <- tile[s][0..15] for s < len
-__device__ __forceinline__ void unstage16(const float* tile, float* __restrict__ dst, int ld, size_t rowbase, int L, int s0,
-                                          int len, int rev, int col0, int part) {
+__device__ __forceinline__ void st_piece(float* p, const float (&v)[4]) { st4(p, f32x4{v[0], v[1], v[2], v[3]}); }
+template <typename H>
+__device__ __forceinline__ void ld_piece(const H* p, float (&v)[8]) {
+    const typename H16<H>::x8 t = *reinterpret_cast<const typename H16<H>::x8*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+}
+template <typename H>
+__device__ __forceinline__ void st_piece(H* p, const float (&v)[8]) {   // round to nearest even, one rounding per element
+    typename H16<H>::x8 t;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t[e] = (H)v[e];
+    *reinterpret_cast<typename H16<H>::x8*>(p) = t;
+}
+
+// tile[s][0..15] <- src[row(s0 + s)][col0 .. col0 + 16) as fp32, zeros for s >= len.  One 16-byte piece per thread: 128
+// threads for an fp32 source (part selects which half of the workgroup), the first 64 of them for a 16-bit one.
+template <typename S>
+__device__ __forceinline__ void stage16(float* tile, const S* __restrict__ src, int ld, size_t rowbase, int L, int s0,
+                                        int len, int rev, int col0, int part) {
+    constexpr int PN = Piece<S>::N, PPR = 16 / PN;   // elements per piece, pieces per row
     const int i = (int)threadIdx.x - part * 128;
-    if (i < 0 || i >= 128) return;
-    const int s = i >> 2, q = i & 3;
+    if (i < 0 || i >= SCAN_CHUNK * PPR) return;
+    const int s = i / PPR, q = i % PPR;
+    float v[PN];
+#pragma unroll
+    for (int e = 0; e < PN; ++e) v[e] = 0.f;
     if (s < len) {
         const int t = rev ? L - 1 - (s0 + s) : s0 + s;
-        st4(dst + (rowbase + t) * (size_t)ld + col0 + q * 4, ld4(tile + s * 16 + q * 4));
+        ld_piece(src + (rowbase + t) * (size_t)ld + col0 + q * PN, v);
+    }
+#pragma unroll
+    for (int e = 0; e < PN; e += 4) st4(tile + s * 16 + q * PN + e, f32x4{v[e], v[e + 1], v[e + 2], v[e + 3]});
+}
+// dst[row(s0 + s)][col0 .. col0 + 16) <- tile[s][0..15] for s < len, rounded to dst's type
+template <typename S>
+__device__ __forceinline__ void unstage16(const float* tile, S* __restrict__ dst, int ld, size_t rowbase, int L, int s0,
+                                          int len, int rev, int col0, int part) {
+    constexpr int PN = Piece<S>::N, PPR = 16 / PN;
+    const int i = (int)threadIdx.x - part * 128;
+    if (i < 0 || i >= SCAN_CHUNK * PPR) return;
+    const int s = i / PPR, q = i % PPR;
+    if (s < len) {
+        const int t = rev ? L - 1 - (s0 + s) : s0 + s;
+        float v[PN];
+#pragma unroll
+        for (int e = 0; e < PN; e += 4) {
+            const f32x4 w = ld4(tile + s * 16 + q * PN + e);
+            v[e] = w[0]; v[e + 1] = w[1]; v[e + 2] = w[2]; v[e + 3] = w[3];
+        }
+        st_piece(dst + (rowbase + t) * (size_t)ld + col0 + q * PN, v);
     }
 }
 
@@ -104,7 +148,8 @@ __device__ __forceinline__ void unstage16(const float* tile, float* __restrict__
     const size_t chunk_id = (size_t)b * p.nc + c
 
 // forward state pass: chunk c (< nc - 1) from h = 0 -> hin slot c + 1 (its end state), sumd[c]
-__global__ __launch_bounds__(256) void scan_state_kernel(const ScanP p) {
+template <typename T>
+__global__ __launch_bounds__(256) void scan_state_kernel(const ScanP<T> p) {
     __shared__ float s_dl[TILE], s_u[TILE], s_B[TILE];
     SCAN_IDS();
     stage16(s_dl, p.raw, p.ld_raw, rowbase, p.L, s0, len, p.rev, d0, 0);
@@ -129,7 +174,8 @@ __global__ __launch_bounds__(256) void scan_state_kernel(const ScanP p) {
 
 // hin[c + 1] = exp(A sum_delta_c) hin[c] + hin[c + 1] for c = 0 .. nc - 2 (hin[0] = 0, never stored); one thread per
 // (b, channel, state)
-__global__ __launch_bounds__(256) void scan_carry_kernel(const ScanP p) {
+template <typename T>
+__global__ __launch_bounds__(256) void scan_carry_kernel(const ScanP<T> p) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t per = (size_t)p.D * NS;
     if (i >= (size_t)p.B * per) return;
@@ -146,7 +192,8 @@ __global__ __launch_bounds__(256) void scan_carry_kernel(const ScanP p) {
 }
 
 // forward emit pass
-__global__ __launch_bounds__(256) void scan_emit_kernel(const ScanP p) {
+template <typename T>
+__global__ __launch_bounds__(256) void scan_emit_kernel(const ScanP<T> p) {
     __shared__ float s_dl[TILE], s_u[TILE], s_z[TILE], s_B[TILE], s_C[TILE];
     SCAN_IDS();
     stage16(s_dl, p.raw, p.ld_raw, rowbase, p.L, s0, len, p.rev, d0, 0);
@@ -173,7 +220,8 @@ __global__ __launch_bounds__(256) void scan_emit_kernel(const ScanP p) {
 
 // backward local pass: chunk c (>= 1) from a zero incoming gradient -> gl slot c (gradient w.r.t. the state the chunk
 // starts from), sumd[c]
-__global__ __launch_bounds__(256) void scan_bwd_local_kernel(const ScanP p) {
+template <typename T>
+__global__ __launch_bounds__(256) void scan_bwd_local_kernel(const ScanP<T> p) {
     __shared__ float s_dl[TILE], s_z[TILE], s_dy[TILE], s_C[TILE];
     SCAN_IDS();
     stage16(s_dl, p.raw, p.ld_raw, rowbase, p.L, s0, len, p.rev, d0, 0);
@@ -197,7 +245,8 @@ __global__ __launch_bounds__(256) void scan_bwd_local_kernel(const ScanP p) {
 }
 
 // G[c] = exp(A sum_delta_c) G[c + 1] + local[c] for c = nc - 1 .. 1 (G[nc] = 0), in place
-__global__ __launch_bounds__(256) void scan_bwd_carry_kernel(const ScanP p) {
+template <typename T>
+__global__ __launch_bounds__(256) void scan_bwd_carry_kernel(const ScanP<T> p) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t per = (size_t)p.D * NS;
     if (i >= (size_t)p.B * per) return;
@@ -214,7 +263,8 @@ __global__ __launch_bounds__(256) void scan_bwd_carry_kernel(const ScanP p) {
 }
 
 // backward main pass
-__global__ __launch_bounds__(256) void scan_bwd_main_kernel(const ScanP p) {
+template <typename T>
+__global__ __launch_bounds__(256) void scan_bwd_main_kernel(const ScanP<T> p) {
     __shared__ float s_dl[TILE], s_u[TILE], s_sg[TILE], s_dyv[TILE], s_dzf[TILE], s_B[TILE], s_C[TILE];
     __shared__ float s_red[4][SCAN_CHUNK][32];
     SCAN_IDS();
@@ -325,9 +375,12 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
 
 // ---- causal depthwise conv1d (4 taps) + bias + SiLU ----------------------------------------------------------------
 // position s of the walk is token t = s (forward) or L - 1 - s (reverse); y_s = silu(bias + sum_k w[k] x_{s - 3 + k})
-__global__ __launch_bounds__(256) void conv1d_silu_fwd_kernel(const float* __restrict__ x, int ld_x,
+// T: the storage type of x / y (and dy / dx below): float, or __bf16 / _Float16.  A lane keeps its four channels for every T
+// (the weight registers and the reduction layout do not change), so a 16-bit lane moves 8 bytes and 32 lanes one 256-byte row.
+template <typename T>
+__global__ __launch_bounds__(256) void conv1d_silu_fwd_kernel(const T* __restrict__ x, int ld_x,
                                                               const float* __restrict__ w, const float* __restrict__ bias,
-                                                              float* __restrict__ y, int ld_y, int B, int L, int D, int rev) {
+                                                              T* __restrict__ y, int ld_y, int B, int L, int D, int rev) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int q4 = D >> 2;
     if (i >= (size_t)B * L * q4) return;
@@ -355,10 +408,11 @@ __global__ __launch_bounds__(256) void conv1d_silu_fwd_kernel(const float* __res
 
 // backward: recomputes the pre-activation.  Workgroup = 128 channels (32 quads) x 8 position lanes over CONV_TT positions
 // of one sample; its dweight / dbias partial goes to slab[(b * nblk + blk)][D][5].
-__global__ __launch_bounds__(256) void conv1d_silu_bwd_kernel(const float* __restrict__ x, int ld_x,
+template <typename T>
+__global__ __launch_bounds__(256) void conv1d_silu_bwd_kernel(const T* __restrict__ x, int ld_x,
                                                               const float* __restrict__ w, const float* __restrict__ bias,
-                                                              const float* __restrict__ dy, int ld_dy,
-                                                              float* __restrict__ dx, int ld_dx, float* __restrict__ slab,
+                                                              const T* __restrict__ dy, int ld_dy,
+                                                              T* __restrict__ dx, int ld_dx, float* __restrict__ slab,
                                                               int L, int D, int rev) {
     __shared__ float red[8][32][20];
     const int tid = threadIdx.x, cq = tid & 31, tr = tid >> 5;
@@ -446,8 +500,20 @@ __global__ __launch_bounds__(256) void copy_cols_kernel(const float* __restrict_
     st4(dst + row * ld_dst + q, ld4(src + row * ld_src + q));
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void cast_h16_f32_kernel(const T* __restrict__ src, float* __restrict__ dst, long n8) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    float v[8];
+    ld_piece(src + i * 8, v);
+    st4(dst + i * 8, f32x4{v[0], v[1], v[2], v[3]});
+    st4(dst + i * 8 + 4, f32x4{v[4], v[5], v[6], v[7]});
+}
+
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline bool ld_ok(int ld, int width) { return ld >= width && ld % 4 == 0; }
+// row stride of an operand stored as T, in elements: whole 16-byte pieces (4 floats, 8 elements of a 16-bit type)
+template <typename T> inline bool ld_okT(int ld, int width) { return ld >= width && ld % (16 / (int)sizeof(T)) == 0; }
 inline int nchunks(int L) { return (L + SCAN_CHUNK - 1) / SCAN_CHUNK; }
 inline bool dims_ok(int B, int L, int D) {
     // grid limits (blockIdx.y / .z), the int token arithmetic of the kernels, and the conv backward's 128-channel tile (the
@@ -490,79 +556,122 @@ size_t ds6g_causal_conv1d_workspace_bytes(int B, int L, int D) {
     return (size_t)B * ((L + CONV_TT - 1) / CONV_TT) * D * 5 * sizeof(float);
 }
 
-int ds6g_causal_conv1d_silu_fwd(const float* x, int ld_x, const float* w, const float* bias, float* y, int ld_y, int B,
-                                int L, int D, int reverse, void* stream) {
+// The four operators over the storage type T of their wide operands (x, y, dy, dx; u, z, y, dy, dz): float behind the fp32
+// entry points, __bf16 / _Float16 behind the ds6g_h16_* ones.  Same checks, same launches, same workspace for every T.
+extern "C++" template <typename T>
+static int conv1d_silu_fwd(const void* x, int ld_x, const float* w, const float* bias, void* y, int ld_y, int B, int L, int D,
+                           int reverse, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && w && bias && y && dims_ok(B, L, D));
-    DS6G_CHECK_ARG(ld_ok(ld_x, D) && ld_ok(ld_y, D) && al16(x) && al16(w) && al16(bias) && al16(y));
+    DS6G_CHECK_ARG(ld_okT<T>(ld_x, D) && ld_okT<T>(ld_y, D) && al16(x) && al16(w) && al16(bias) && al16(y));
     const size_t n = (size_t)B * L * (D / 4);
-    hipLaunchKernelGGL(conv1d_silu_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ld_x,
-                       w, bias, y, ld_y, B, L, D, reverse ? 1 : 0);
+    hipLaunchKernelGGL(conv1d_silu_fwd_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const T*)x, ld_x, w, bias, (T*)y, ld_y, B, L, D, reverse ? 1 : 0);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_causal_conv1d_silu_fwd(const float* x, int ld_x, const float* w, const float* bias, float* y, int ld_y, int B,
+                                int L, int D, int reverse, void* stream) {
+    return conv1d_silu_fwd<float>(x, ld_x, w, bias, y, ld_y, B, L, D, reverse, stream);
+}
+int ds6g_h16_causal_conv1d_silu_fwd(int st16, const void* x, int ld_x, const float* w, const float* bias, void* y, int ld_y,
+                                    int B, int L, int D, int reverse, void* stream) {
+    DS6G_RETURN_H16(st16, conv1d_silu_fwd, x, ld_x, w, bias, y, ld_y, B, L, D, reverse, stream);
+}
 
-int ds6g_causal_conv1d_silu_bwd(const float* x, int ld_x, const float* w, const float* bias, const float* dy, int ld_dy,
-                                float* dx, int ld_dx, float* dw, float* dbias, int B, int L, int D, int reverse, void* ws,
-                                size_t ws_bytes, void* stream) {
+extern "C++" template <typename T>
+static int conv1d_silu_bwd(const void* x, int ld_x, const float* w, const float* bias, const void* dy, int ld_dy, void* dx,
+                           int ld_dx, float* dw, float* dbias, int B, int L, int D, int reverse, void* ws, size_t ws_bytes,
+                           void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(x && w && bias && dy && dx && dw && dbias && ws && dims_ok(B, L, D));
-    DS6G_CHECK_ARG(ld_ok(ld_x, D) && ld_ok(ld_dy, D) && ld_ok(ld_dx, D));
+    DS6G_CHECK_ARG(ld_okT<T>(ld_x, D) && ld_okT<T>(ld_dy, D) && ld_okT<T>(ld_dx, D));
     DS6G_CHECK_ARG(al16(x) && al16(w) && al16(bias) && al16(dy) && al16(dx) && al16(ws));
     DS6G_CHECK_WS(ws_bytes >= ds6g_causal_conv1d_workspace_bytes(B, L, D));
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (L + CONV_TT - 1) / CONV_TT;
-    hipLaunchKernelGGL(conv1d_silu_bwd_kernel, dim3(D / CONV_CB, nblk, B), dim3(256), 0, st, x, ld_x, w, bias, dy, ld_dy, dx,
-                       ld_dx, (float*)ws, L, D, reverse ? 1 : 0);
+    hipLaunchKernelGGL(conv1d_silu_bwd_kernel<T>, dim3(D / CONV_CB, nblk, B), dim3(256), 0, st, (const T*)x, ld_x, w, bias,
+                       (const T*)dy, ld_dy, (T*)dx, ld_dx, (float*)ws, L, D, reverse ? 1 : 0);
     DS6G_LAUNCH_CHECK();
     hipLaunchKernelGGL(conv1d_param_reduce_kernel, dim3(cdiv((long)D * 5, 256)), dim3(256), 0, st, (const float*)ws, B * nblk,
                        D, dw, dbias);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_causal_conv1d_silu_bwd(const float* x, int ld_x, const float* w, const float* bias, const float* dy, int ld_dy,
+                                float* dx, int ld_dx, float* dw, float* dbias, int B, int L, int D, int reverse, void* ws,
+                                size_t ws_bytes, void* stream) {
+    return conv1d_silu_bwd<float>(x, ld_x, w, bias, dy, ld_dy, dx, ld_dx, dw, dbias, B, L, D, reverse, ws, ws_bytes, stream);
+}
+int ds6g_h16_causal_conv1d_silu_bwd(int st16, const void* x, int ld_x, const float* w, const float* bias, const void* dy,
+                                    int ld_dy, void* dx, int ld_dx, float* dw, float* dbias, int B, int L, int D, int reverse,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, conv1d_silu_bwd, x, ld_x, w, bias, dy, ld_dy, dx, ld_dx, dw, dbias, B, L, D, reverse, ws, ws_bytes,
+                    stream);
+}
 
-int ds6g_selective_scan_fwd(const float* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
-                            const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
-                            const float* z, int ld_z, float* y, int ld_y, float* saved, int B, int L, int D, int reverse,
-                            void* ws, size_t ws_bytes, void* stream) {
+// 16-bit T: u, z, y are T; delta_raw, Bm, Cm (and everything else) stay fp32 - they come from the fp32 side of the layer's
+// storage map (x_proj's output and dt_proj's)
+extern "C++" template <typename T>
+static int selective_scan_fwd(const void* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                              const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                              const void* z, int ld_z, void* y, int ld_y, float* saved, int B, int L, int D, int reverse,
+                              void* ws, size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(u && delta_raw && dt_bias && A_log && Bm && Cm && Dp && z && y && ws && dims_ok(B, L, D));
-    DS6G_CHECK_ARG(ld_ok(ld_u, D) && ld_ok(ld_delta, D) && ld_ok(ld_z, D) && ld_ok(ld_y, D) && ld_ok(ld_b, NS) &&
+    DS6G_CHECK_ARG(ld_okT<T>(ld_u, D) && ld_ok(ld_delta, D) && ld_okT<T>(ld_z, D) && ld_okT<T>(ld_y, D) && ld_ok(ld_b, NS) &&
                    ld_ok(ld_c, NS));
     DS6G_CHECK_ARG(al16(u) && al16(delta_raw) && al16(Bm) && al16(Cm) && al16(z) && al16(y) && al16(ws) && al16(saved));
     DS6G_CHECK_WS(ws_bytes >= ds6g_selective_scan_workspace_bytes(B, L, D));
     hipStream_t st = (hipStream_t)stream;
     const ScanWs o = scan_ws(B, L, D);
     float* wsf = (float*)ws;
-    ScanP p{};
-    p.u = u; p.raw = delta_raw; p.dt_bias = dt_bias; p.A_log = A_log; p.Bm = Bm; p.Cm = Cm; p.Dp = Dp; p.z = z;
+    ScanP<T> p{};
+    p.u = (const T*)u; p.raw = delta_raw; p.dt_bias = dt_bias; p.A_log = A_log; p.Bm = Bm; p.Cm = Cm; p.Dp = Dp;
+    p.z = (const T*)z;
     p.ld_u = ld_u; p.ld_raw = ld_delta; p.ld_b = ld_b; p.ld_c = ld_c; p.ld_z = ld_z;
-    p.y = y; p.ld_y = ld_y;
+    p.y = (T*)y; p.ld_y = ld_y;
     p.hin = saved ? saved : wsf + o.st;
     p.sumd = wsf + o.sumd;
     p.B = B; p.L = L; p.D = D; p.nc = nchunks(L); p.rev = reverse ? 1 : 0;
     if (p.nc > 1) {
-        hipLaunchKernelGGL(scan_state_kernel, dim3(D / CPB, p.nc - 1, B), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(scan_state_kernel<T>, dim3(D / CPB, p.nc - 1, B), dim3(256), 0, st, p);
         DS6G_LAUNCH_CHECK();
-        hipLaunchKernelGGL(scan_carry_kernel, dim3(cdiv((long)B * D * NS, 256)), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(scan_carry_kernel<T>, dim3(cdiv((long)B * D * NS, 256)), dim3(256), 0, st, p);
         DS6G_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(scan_emit_kernel, dim3(D / CPB, p.nc, B), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(scan_emit_kernel<T>, dim3(D / CPB, p.nc, B), dim3(256), 0, st, p);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
-
-int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+int ds6g_selective_scan_fwd(const float* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
                             const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
-                            const float* z, int ld_z, const float* dy, int ld_dy, const float* saved, float* du, int ld_du,
-                            float* ddelta, int ld_ddelta, float* dBm, int ld_dbm, float* dCm, int ld_dcm, float* dz,
-                            int ld_dz, float* dA_log, float* dD, int B, int L, int D, int reverse, void* ws,
-                            size_t ws_bytes, void* stream) {
+                            const float* z, int ld_z, float* y, int ld_y, float* saved, int B, int L, int D, int reverse,
+                            void* ws, size_t ws_bytes, void* stream) {
+    return selective_scan_fwd<float>(u, ld_u, delta_raw, ld_delta, dt_bias, A_log, Bm, ld_b, Cm, ld_c, Dp, z, ld_z, y, ld_y,
+                                     saved, B, L, D, reverse, ws, ws_bytes, stream);
+}
+int ds6g_h16_selective_scan_fwd(int st16, const void* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                                const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                                const void* z, int ld_z, void* y, int ld_y, float* saved, int B, int L, int D, int reverse,
+                                void* ws, size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, selective_scan_fwd, u, ld_u, delta_raw, ld_delta, dt_bias, A_log, Bm, ld_b, Cm, ld_c, Dp, z, ld_z, y,
+                    ld_y, saved, B, L, D, reverse, ws, ws_bytes, stream);
+}
+
+// 16-bit T: u, z, dy, dz are T; du, ddelta, dBm, dCm stay fp32 (du is the buffer x_proj's data gradient is added to in fp32)
+extern "C++" template <typename T>
+static int selective_scan_bwd(const void* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                              const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                              const void* z, int ld_z, const void* dy, int ld_dy, const float* saved, float* du, int ld_du,
+                              float* ddelta, int ld_ddelta, float* dBm, int ld_dbm, float* dCm, int ld_dcm, void* dz,
+                              int ld_dz, float* dA_log, float* dD, int B, int L, int D, int reverse, void* ws,
+                              size_t ws_bytes, void* stream) {
     DS6G_ENTER();
     DS6G_CHECK_ARG(u && delta_raw && dt_bias && A_log && Bm && Cm && Dp && z && dy && saved && du && ddelta && dBm && dCm &&
                    dz && dA_log && dD && ws && dims_ok(B, L, D));
-    DS6G_CHECK_ARG(ld_ok(ld_u, D) && ld_ok(ld_delta, D) && ld_ok(ld_z, D) && ld_ok(ld_dy, D) && ld_ok(ld_b, NS) &&
-                   ld_ok(ld_c, NS) && ld_ok(ld_du, D) && ld_ok(ld_ddelta, D) && ld_ok(ld_dz, D) && ld_ok(ld_dbm, NS) &&
+    DS6G_CHECK_ARG(ld_okT<T>(ld_u, D) && ld_ok(ld_delta, D) && ld_okT<T>(ld_z, D) && ld_okT<T>(ld_dy, D) && ld_ok(ld_b, NS) &&
+                   ld_ok(ld_c, NS) && ld_ok(ld_du, D) && ld_ok(ld_ddelta, D) && ld_okT<T>(ld_dz, D) && ld_ok(ld_dbm, NS) &&
                    ld_ok(ld_dcm, NS));
     DS6G_CHECK_ARG(al16(u) && al16(delta_raw) && al16(Bm) && al16(Cm) && al16(z) && al16(dy) && al16(saved) && al16(du) &&
                    al16(ddelta) && al16(dBm) && al16(dCm) && al16(dz) && al16(ws));
@@ -570,22 +679,23 @@ int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, in
     hipStream_t st = (hipStream_t)stream;
     const ScanWs o = scan_ws(B, L, D);
     float* wsf = (float*)ws;
-    ScanP p{};
-    p.u = u; p.raw = delta_raw; p.dt_bias = dt_bias; p.A_log = A_log; p.Bm = Bm; p.Cm = Cm; p.Dp = Dp; p.z = z; p.dy = dy;
+    ScanP<T> p{};
+    p.u = (const T*)u; p.raw = delta_raw; p.dt_bias = dt_bias; p.A_log = A_log; p.Bm = Bm; p.Cm = Cm; p.Dp = Dp;
+    p.z = (const T*)z; p.dy = (const T*)dy;
     p.ld_u = ld_u; p.ld_raw = ld_delta; p.ld_b = ld_b; p.ld_c = ld_c; p.ld_z = ld_z; p.ld_dy = ld_dy;
     p.hin = const_cast<float*>(saved);
     p.sumd = wsf + o.sumd; p.gl = wsf + o.st;
-    p.du = du; p.draw = ddelta; p.dz = dz; p.ld_du = ld_du; p.ld_draw = ld_ddelta; p.ld_dz = ld_dz;
+    p.du = du; p.draw = ddelta; p.dz = (T*)dz; p.ld_du = ld_du; p.ld_draw = ld_ddelta; p.ld_dz = ld_dz;
     p.slab_bc = wsf + o.slab_bc; p.slab_a = wsf + o.slab_a; p.slab_d = wsf + o.slab_d;
     p.B = B; p.L = L; p.D = D; p.nc = nchunks(L); p.rev = reverse ? 1 : 0;
     if (p.nc > 1) {
         // chunk 0 is computed too (nobody reads its slot): one chunk in nc, and no special case in the kernel
-        hipLaunchKernelGGL(scan_bwd_local_kernel, dim3(D / CPB, p.nc, B), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(scan_bwd_local_kernel<T>, dim3(D / CPB, p.nc, B), dim3(256), 0, st, p);
         DS6G_LAUNCH_CHECK();
-        hipLaunchKernelGGL(scan_bwd_carry_kernel, dim3(cdiv((long)B * D * NS, 256)), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(scan_bwd_carry_kernel<T>, dim3(cdiv((long)B * D * NS, 256)), dim3(256), 0, st, p);
         DS6G_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(scan_bwd_main_kernel, dim3(D / CPB, p.nc, B), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(scan_bwd_main_kernel<T>, dim3(D / CPB, p.nc, B), dim3(256), 0, st, p);
     DS6G_LAUNCH_CHECK();
     const size_t rows = (size_t)B * L;
     hipLaunchKernelGGL(scan_bc_reduce_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st,
@@ -597,6 +707,42 @@ int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, in
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(D, 256)), dim3(256), 0, st, (const float*)p.slab_d, B * p.nc, D, dD);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
+}
+int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                            const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                            const float* z, int ld_z, const float* dy, int ld_dy, const float* saved, float* du, int ld_du,
+                            float* ddelta, int ld_ddelta, float* dBm, int ld_dbm, float* dCm, int ld_dcm, float* dz,
+                            int ld_dz, float* dA_log, float* dD, int B, int L, int D, int reverse, void* ws,
+                            size_t ws_bytes, void* stream) {
+    return selective_scan_bwd<float>(u, ld_u, delta_raw, ld_delta, dt_bias, A_log, Bm, ld_b, Cm, ld_c, Dp, z, ld_z, dy, ld_dy,
+                                     saved, du, ld_du, ddelta, ld_ddelta, dBm, ld_dbm, dCm, ld_dcm, dz, ld_dz, dA_log, dD, B, L,
+                                     D, reverse, ws, ws_bytes, stream);
+}
+int ds6g_h16_selective_scan_bwd(int st16, const void* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                                const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                                const void* z, int ld_z, const void* dy, int ld_dy, const float* saved, float* du, int ld_du,
+                                float* ddelta, int ld_ddelta, float* dBm, int ld_dbm, float* dCm, int ld_dcm, void* dz,
+                                int ld_dz, float* dA_log, float* dD, int B, int L, int D, int reverse, void* ws,
+                                size_t ws_bytes, void* stream) {
+    DS6G_RETURN_H16(st16, selective_scan_bwd, u, ld_u, delta_raw, ld_delta, dt_bias, A_log, Bm, ld_b, Cm, ld_c, Dp, z, ld_z, dy,
+                    ld_dy, saved, du, ld_du, ddelta, ld_ddelta, dBm, ld_dbm, dCm, ld_dcm, dz, ld_dz, dA_log, dD, B, L, D,
+                    reverse, ws, ws_bytes, stream);
+}
+
+// dst (fp32) = src (bf16 / f16), exact; n % 8 == 0, both 16-byte aligned.  The layer's 16-bit path widens xc with it for the
+// fp32 weight-gradient GEMM of x_proj, whose r + 32 output rows the 16-bit GEMM's shape rules do not admit.
+extern "C++" template <typename T>
+static int cast_h16_f32(const void* src, float* dst, long n, void* stream) {
+    DS6G_ENTER();
+    DS6G_CHECK_ARG(src && dst && n > 0 && n % 8 == 0 && al16(src) && al16(dst));
+    const long n8 = n / 8;
+    hipLaunchKernelGGL(cast_h16_f32_kernel<T>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const T*)src, dst, n8);
+    DS6G_LAUNCH_CHECK();
+    return DS6G_OK;
+}
+int ds6g_cast_h16_f32(int st16, const void* src, float* dst, long n, void* stream) {
+    DS6G_RETURN_H16(st16, cast_h16_f32, src, dst, n, stream);
 }
 
 int ds6g_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, long rows, int cols, void* stream) {

@@ -12,9 +12,27 @@ The four projections are the fp32 implicit-GEMM linears (ops.linear_*); the conv
 extension: forward(u, reverse=True) walks the sequence back to front (== flip(forward(flip(u))) without the copies), which
 the reference's backward_mamba branch needs (mambafuser_seq.py:100-101).
 
+16-bit storage: a bf16 / f16 input runs the same layer with its wide activations stored in that type.
+Parameters are fp32 masters with fp32 gradients; all arithmetic inside a kernel, the scan state, its checkpoints and every
+reduction slab are fp32.  r = dt_rank, rows16 = r + 32 rounded up to a multiple of 8:
+
+    tensor                          storage   produced by
+    u, xz (x | z), xc, y, out       16-bit    in_proj / x_proj / out_proj on the 16-bit GEMM (ops.bf16_linear_*), the 16-bit
+    dout, dy, dxz (dx | dz), du     16-bit    conv and scan kernels (ds6g_h16_*)
+    x_dbl (dt | Bm | Cm | 0)        fp32      x_proj forward: 16-bit GEMM on a zero-padded rows16-row weight copy, fp32 output
+    dt, delta_raw, ddelta           fp32      dt_proj: the fp32 linears, as on the fp32 path (it contracts over r = 4 .. 32)
+    dxdbl (ddt | dBm | dCm)         fp32      the scan's slab reduction and dt_proj's data gradient
+    dxc                             fp32      the scan's du plus x_proj's data gradient (fp32 GEMM: it contracts over r + 32),
+                                              then ONE rounding to the 16-bit copy the conv backward reads
+    x_proj.weight's gradient        fp32      fp32 GEMM on xc widened to fp32 (ds6g_cast_h16_f32; not kept on the tape)
+    weight copies                   16-bit    in_proj, out_proj (forward and data gradient), x_proj (forward only): cast from
+                                              the fp32 masters on every call, or the caller's own (w16=)
+The tape of one layer is u, xz, xc, y (16-bit) and x_dbl, dt, delta_raw, the chunk checkpoints (fp32).
+
 Supported: d_state 16, d_conv 4, d_model % 64 == 0 (expand * d_model % 128 == 0, dt_rank % 4 == 0), bias=False,
-conv_bias=True, fp32, any B, L >= 1.  Anything else raises ValueError at construction.  Not covered: bf16 / f16 storage, the
-frozen inference engine, the single-step inference_params path.
+conv_bias=True, fp32 parameters, fp32 / bf16 / f16 activations, any B, L >= 1.  Anything else raises ValueError at
+construction.  Not covered: 16-bit storage of the stage (MambaBlock / MambaFusion), the head (TimeMamba) and the model
+(MambaFuser) above this layer, the frozen inference engine, the single-step inference_params path.
 """
 from __future__ import annotations
 
@@ -29,10 +47,52 @@ F32 = torch.float32
 _MIN_WS = 64 << 20   # room for the split-K slabs of the projection weight gradients
 
 
-def layer_forward(mod, ws, reverse, save, u2, Bsz, L, params):
+def x_proj_rows16(r):
+    """rows of the 16-bit copy of x_proj.weight: r + 32 rounded up to the 16-bit GEMM's multiple of 8, the added rows zero"""
+    return (r + 32 + 7) // 8 * 8
+
+
+def weight_copies16(mod, params, dtype):
+    """-> the `w16` of layer_forward / layer_backward: device pointers of 16-bit copies of (in_proj.weight, x_proj.weight
+    zero-padded to x_proj_rows16 rows, out_proj.weight), cast from the fp32 masters now; the tensors ride along so the
+    pointers stay valid"""
+    w_in, w_x, w_out = params[0], params[3], params[8]
+    n_x = x_proj_rows16(mod.dt_rank)
+    x16 = torch.zeros((n_x, mod.d_inner), dtype=dtype, device=w_x.device) if n_x != w_x.shape[0] else \
+        torch.empty((n_x, mod.d_inner), dtype=dtype, device=w_x.device)
+    ops.cast_bf16(w_x, out=x16[:w_x.shape[0]])
+    ts = (ops.cast_bf16(w_in, dtype=dtype), x16, ops.cast_bf16(w_out, dtype=dtype))
+    return tuple(t.data_ptr() for t in ts), ts
+
+
+def _layer_forward16(mod, ws, reverse, save, u2, Bsz, L, params, w16):
+    """layer_forward on 16-bit token rows (the storage map of the module docstring)"""
+    w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
+    M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
+    if w16 is None:
+        w16, _alive = weight_copies16(mod, params, u2.dtype)   # _alive: until the launches below are queued
+    p_in, p_x, p_out = w16
+    xz = ops.bf16_linear_fwd(u2, p_in, 0, 2 * D)
+    z = xz[:, D:]
+    xc = ops.h16_causal_conv1d_silu_fwd(xz[:, :D], conv_w, conv_b, Bsz, L, reverse)
+    x_dbl = ops.bf16_linear_fwd(xc, p_x, 0, x_proj_rows16(r), out16=False)    # fp32 [M, rows16]: dt | Bm | Cm | zero columns
+    dt = ops.copy_cols(x_dbl[:, :r], torch.empty((M, r), dtype=F32, device=u2.device))
+    draw = ops.linear_fwd(dt, w_dt.data_ptr(), 0, D)       # fp32; dt_proj.bias is added inside the scan
+    y, saved = ops.h16_selective_scan_fwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:r + 32], Dp, z, Bsz, L, ws,
+                                          reverse, save)
+    out = ops.bf16_linear_fwd(y, p_out, 0, dm)
+    return out, ((u2, xz, xc, x_dbl, dt, draw, y, saved) if save else None)
+
+
+def layer_forward(mod, ws, reverse, save, u2, Bsz, L, params, w16=None):
     """the layer on token rows u2 [B*L, d_model] (contiguous) -> (out [B*L, d_model], tape or None).  `params`: the nine
     parameters in Mamba._params() order; `ws`: a Workspace of at least mod.workspace_bytes(B, L).  Shared by _MambaFn and by
-    the block-level Function of mamba_fusion.py, which runs two layers inside one autograd node."""
+    the block-level Function of mamba_fusion.py, which runs two layers inside one autograd node.
+    A bf16 / f16 u2 runs the 16-bit-storage path and returns `out` in u2's dtype.  w16 (that path only): the device pointers
+    weight_copies16 returns, for a caller that keeps 16-bit weight copies of its own; None casts the three weights here, on
+    every call."""
+    if u2.dtype != F32:
+        return _layer_forward16(mod, ws, reverse, save, u2, Bsz, L, params, w16)
     w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
     M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
     xz = ops.linear_fwd(u2, w_in.data_ptr(), 0, 2 * D)
@@ -73,12 +133,61 @@ def deliver_pair(fn, slot_a, slot_b, shape_a, shape_b, device, has_flag=True):
         ops.lib().axpby(t.data_ptr(), p if a else 0, p, t.numel(), 1.0, 1.0, st)
 
 
-def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None, gdst=None):
+def _layer_backward16(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out, gdst, w16):
+    """layer_backward on a 16-bit tape and dout2 (the storage map of the module docstring); parameter gradients fp32"""
+    u2, xz, xc, x_dbl, dt, draw, y, saved = tape
+    w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
+    M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
+    dev, h16 = dout2.device, dout2.dtype
+    if w16 is None:
+        w16, _alive = weight_copies16(mod, params, h16)
+    p_in, _, p_out = w16
+
+    def empty(*shape, dtype=F32):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    shapes = ((2 * D, dm), (D, 1, 4), (D,), (r + 32, D), (D, r), (D,), (D, 16), (D,), (dm, D))
+    (s_in, s_cw, s_cb, s_x, s_dtw, s_dtb, s_A, s_D, s_out), grads = grad_slots(shapes, dev, gdst)
+
+    ops.bf16_linear_wgrad(y, dout2, s_out[0], ws, accumulate=bool(s_out[1]))
+    dy = ops.bf16_linear_dgrad(dout2, p_out, D)
+    dxz, dxdbl, dxc, ddraw = empty(M, 2 * D, dtype=h16), empty(M, r + 32), empty(M, D), empty(M, D)
+    Bm, Cm = x_dbl[:, r:r + 16], x_dbl[:, r + 16:r + 32]
+
+    def scan(pa, pd, _acc):
+        ops.h16_selective_scan_bwd(xc, draw, b_dt, A_log, Bm, Cm, Dp, xz[:, D:], dy, saved, dxc, ddraw, dxdbl[:, r:r + 16],
+                                   dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse, out=(pa, pd))
+    deliver_pair(scan, s_A, s_D, shapes[6], shapes[7], dev, has_flag=False)
+    deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(dt, ddraw, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_dtw, s_dtb,
+                 shapes[4], shapes[5], dev)
+    ops.copy_cols(ops.linear_dgrad(ddraw, w_dt.data_ptr(), r), dxdbl[:, :r])
+    # x_proj's r + 32 rows fit neither the 16-bit wgrad (rows % 8) nor its dgrad (contraction % 64): both stay fp32 GEMMs, the
+    # weight gradient on an fp32 widening of xc, the data gradient added to the scan's fp32 du
+    ops.linear_wgrad(ops.cast_f32(xc), dxdbl, s_x[0], ws, accumulate=bool(s_x[1]))
+    ops.linear_dgrad(dxdbl, w_x.data_ptr(), D, out=dxc, accumulate=True)
+    dxc16 = ops.cast_bf16(dxc, dtype=h16)
+
+    def conv(pw, pb, _acc):
+        ops.h16_causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc16, dxz[:, :D], Bsz, L, ws, reverse, out=(pw, pb))
+    deliver_pair(conv, s_cw, s_cb, shapes[1], shapes[2], dev, has_flag=False)
+    ops.bf16_linear_wgrad(u2, dxz, s_in[0], ws, accumulate=bool(s_in[1]))
+    if du_out is None:
+        du = ops.bf16_linear_dgrad(dxz, p_in, dm)
+    else:
+        du = ops.bf16_linear_dgrad(dxz, p_in, dm, out16=du_out.dtype != F32, out=du_out, accumulate=True)
+    return du, grads
+
+
+def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None, gdst=None, w16=None):
     """-> (du [B*L, d_model], the nine parameter gradients in Mamba._params() order).  du_out: an existing gradient of the
     layer's input that du is ADDED to (the in_proj data-gradient GEMM accumulates into it).  gdst: nine (device pointer,
     accumulate flag) pairs in the same order - the gradients are written there in place (added where the flag is set) and
     None is returned in their stead; the conv and scan kernels have no accumulate flag, so a set flag takes those four
-    through a temporary and an add, a fresh gradient (the training case) does not."""
+    through a temporary and an add, a fresh gradient (the training case) does not.
+    A bf16 / f16 dout2 (with the tape of a 16-bit forward) runs the 16-bit-storage path: du has dout2's dtype, du_out may be
+    of that dtype (added to with one rounding) or fp32, the parameter gradients and gdst stay fp32; w16 as in layer_forward."""
+    if dout2.dtype != F32:
+        return _layer_backward16(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out, gdst, w16)
     u2, xz, xc, x_dbl, dt, draw, y, saved = tape
     w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
     M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
@@ -194,7 +303,7 @@ class Mamba(nn.Module):
 
     def workspace_bytes(self, B, L):
         from ._lib import lib
-        D = self.d_inner
+        D = self.d_inner   # the 16-bit-storage path runs the same scan / conv slabs and split-K slabs no larger than fp32's
         return max(int(lib().selective_scan_workspace_bytes(B, L, D)), int(lib().causal_conv1d_workspace_bytes(B, L, D)),
                    _MIN_WS)
 
@@ -211,12 +320,15 @@ class Mamba(nn.Module):
                 self.dt_proj.bias, self.A_log, self.D, self.out_proj.weight)
 
     def forward(self, hidden_states, reverse=False):
-        """hidden_states: (B, L, d_model) fp32 on the HIP device -> (B, L, d_model)"""
+        """hidden_states: (B, L, d_model) fp32, bf16 or f16 on the HIP device -> (B, L, d_model) of the same dtype.  A 16-bit
+        input runs the 16-bit-storage path (module docstring): its gradient is 16-bit, the parameters and their gradients fp32"""
         u = hidden_states
         if not u.is_cuda:
             raise RuntimeError("deepsense6g_tii_amd.Mamba runs on MI355X HIP kernels only (no CPU path)")
-        if u.dim() != 3 or u.shape[2] != self.d_model or u.dtype != F32 or u.shape[0] < 1 or u.shape[1] < 1:
-            raise ValueError(f"Mamba: expected a (B, L, {self.d_model}) fp32 tensor, got {tuple(u.shape)} {u.dtype}")
+        if u.dim() != 3 or u.shape[2] != self.d_model or u.dtype not in (F32, ops.BF16, ops.F16) or u.shape[0] < 1 or \
+                u.shape[1] < 1:
+            raise ValueError(f"Mamba: expected a (B, L, {self.d_model}) fp32, bf16 or f16 tensor, got {tuple(u.shape)} "
+                             f"{u.dtype}")
         params = self._params()
         for p in params:
             if p.device != u.device:

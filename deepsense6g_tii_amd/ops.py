@@ -1038,6 +1038,89 @@ def selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, d
     return dA, dD
 
 
+# The same four operators on 16-bit storage (ds6g_h16_causal_conv1d_* / ds6g_h16_selective_scan_*): the wide activations are
+# bf16 / f16, every operand of one call shares that dtype; the narrow operands, the parameters and their gradients stay fp32.
+def _rows_al16(t, M, C, dtype):
+    assert t.dtype == dtype and dtype in _ST16, (t.dtype, dtype)
+    assert t.is_cuda and t.dim() == 2 and tuple(t.shape) == (M, C) and t.stride(1) == 1, (tuple(t.shape), t.stride())
+    ld = max(t.stride(0), C)   # a one-row view reports an arbitrary stride
+    assert t.data_ptr() % 16 == 0 and ld % 8 == 0, (t.data_ptr(), ld)
+    return ld
+
+
+def cast_f32(src, out=None):
+    """fp32 copy (exact) of a contiguous bf16 / f16 tensor whose numel is a multiple of 8"""
+    _chk16(src)
+    dst = out if out is not None else torch.empty(src.shape, dtype=F32, device=src.device)
+    _chk(dst)
+    assert dst.numel() == src.numel()
+    lib().cast_h16_f32(_ST16[src.dtype], _p(src), _p(dst), src.numel(), _stream())
+    return dst
+
+
+def h16_causal_conv1d_silu_fwd(x, w, bias, B, L, reverse=False):
+    """causal_conv1d_silu_fwd on a 16-bit x [B*L, D] (a column block allowed) -> y [B*L, D] of x's dtype; w, bias fp32"""
+    M, D = x.shape
+    assert M == B * L and D % 128 == 0
+    y = torch.empty((M, D), dtype=x.dtype, device=x.device)
+    lib().h16_causal_conv1d_silu_fwd(_ST16[x.dtype], _p(x), _rows_al16(x, M, D, x.dtype), _vec(w, D, 1, 4), _vec(bias, D), _p(y),
+                                     D, B, L, D, int(reverse), _stream())
+    return y
+
+
+def h16_causal_conv1d_silu_bwd(x, w, bias, dy, dx, B, L, ws: Workspace, reverse=False, out=None):
+    """causal_conv1d_silu_bwd on 16-bit x, dy, dx (column blocks allowed) -> fp32 (dw, dbias), as the fp32 wrapper"""
+    M, D = x.shape
+    assert M == B * L and D % 128 == 0
+    assert ws.nbytes >= int(lib().causal_conv1d_workspace_bytes(B, L, D)), "workspace too small for causal_conv1d_silu_bwd"
+    if out is None:
+        out = (torch.empty((D, 1, 4), dtype=F32, device=x.device), torch.empty((D,), dtype=F32, device=x.device))
+    dw, db = out
+    dt = x.dtype
+    lib().h16_causal_conv1d_silu_bwd(_ST16[dt], _p(x), _rows_al16(x, M, D, dt), _vec(w, D, 1, 4), _vec(bias, D), _p(dy),
+                                     _rows_al16(dy, M, D, dt), _p(dx), _rows_al16(dx, M, D, dt), _dst(dw, D, 1, 4), _dst(db, D),
+                                     B, L, D, int(reverse), ws.ptr, ws.nbytes, _stream())
+    return dw, db
+
+
+def h16_selective_scan_fwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, B, L, ws: Workspace, reverse=False, save=False):
+    """selective_scan_fwd with 16-bit u, z (column blocks allowed) -> (y of their dtype, saved fp32 or None); delta_raw, Bm,
+    Cm and the parameters are fp32"""
+    M, D = u.shape
+    assert M == B * L and D % 128 == 0
+    assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_fwd"
+    dt = u.dtype
+    y = torch.empty((M, D), dtype=dt, device=u.device)
+    saved = torch.empty(int(lib().selective_scan_saved_floats(B, L, D)), dtype=F32, device=u.device) if save else None
+    lib().h16_selective_scan_fwd(_ST16[dt], _p(u), _rows_al16(u, M, D, dt), _p(delta_raw), _rows_al(delta_raw, M, D),
+                                 _vec(dt_bias, D), _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16),
+                                 _vec(Dp, D), _p(z), _rows_al16(z, M, D, dt), _p(y), D, _p(saved), B, L, D, int(reverse),
+                                 ws.ptr, ws.nbytes, _stream())
+    return y, saved
+
+
+def h16_selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, du, ddelta, dBm, dCm, dz, B, L,
+                           ws: Workspace, reverse=False, out=None):
+    """selective_scan_bwd with 16-bit u, z, dy and a 16-bit dz; du, ddelta [B*L, D] and dBm, dCm [B*L, 16] are written as fp32
+    -> fp32 (dA_log, dD), as the fp32 wrapper"""
+    M, D = u.shape
+    assert M == B * L and D % 128 == 0
+    assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_bwd"
+    assert saved.dtype == F32 and saved.is_cuda and saved.is_contiguous() and \
+        saved.numel() == int(lib().selective_scan_saved_floats(B, L, D)), tuple(saved.shape)
+    if out is None:
+        out = (torch.empty((D, 16), dtype=F32, device=u.device), torch.empty((D,), dtype=F32, device=u.device))
+    dA, dD = out
+    dt = u.dtype
+    lib().h16_selective_scan_bwd(_ST16[dt], _p(u), _rows_al16(u, M, D, dt), _p(delta_raw), _rows_al(delta_raw, M, D),
+                                 _vec(dt_bias, D), _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16),
+                                 _vec(Dp, D), _p(z), _rows_al16(z, M, D, dt), _p(dy), _rows_al16(dy, M, D, dt), _p(saved),
+                                 _p(du), _rows_al(du, M, D), _p(ddelta), _rows_al(ddelta, M, D), _p(dBm), _rows_al(dBm, M, 16),
+                                 _p(dCm), _rows_al(dCm, M, 16), _p(dz), _rows_al16(dz, M, D, dt), _dst(dA, D, 16), _dst(dD, D),
+                                 B, L, D, int(reverse), ws.ptr, ws.nbytes, _stream())
+    return dA, dD
+
+
 # ------------------------------------------------------------------------------------------------
 # Mamba fusion stage (csrc/mamba_fusion.hip)
 def sample_layernorm_workspace_bytes(B, n):

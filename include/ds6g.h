@@ -424,6 +424,31 @@ int ds6g_selective_scan_bwd(const float* u, int ld_u, const float* delta_raw, in
                             int ld_dz, float* dA_log, float* dD, int B, int L, int D, int reverse, void* ws,
                             size_t ws_bytes, void* stream);
 int ds6g_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, long rows, int cols, void* stream);
+/* The same four operators on 16-bit storage (st16: DS6G_ST_BF16 / DS6G_ST_F16) - the same kernels instantiated on the
+ * storage type, the same chunking, workspace and saved-floats queries, fp32 arithmetic, no atomics.  What is 16-bit and what
+ * stays fp32 follows the layer's storage map (deepsense6g_tii_amd/mamba.py):
+ *   conv   16-bit: x, y, dy, dx                      fp32: w, bias, dw, dbias
+ *   scan   16-bit: u, z, y, dy, dz                   fp32: delta_raw, ddelta, Bm, Cm, dBm, dCm, du (x_proj's data gradient is
+ *          added to du in fp32 afterwards), dt_bias, A_log, Dp, saved, the workspace, dA_log, dD
+ * Row strides are in ELEMENTS of the operand's own type and cover whole 16-byte pieces: % 8 for a 16-bit operand, % 4 for an
+ * fp32 one; every pointer 16-byte aligned.  Refusals (DS6G_ERR_ARG / DS6G_ERR_WORKSPACE) come before any launch.
+ *   cast_h16_f32   dst (fp32) = src (16-bit), exact; n % 8 == 0 (the inverse of ds6g_cast_f32_h16). */
+int ds6g_h16_causal_conv1d_silu_fwd(int st16, const void* x, int ld_x, const float* w, const float* bias, void* y, int ld_y,
+                                    int B, int L, int D, int reverse, void* stream);
+int ds6g_h16_causal_conv1d_silu_bwd(int st16, const void* x, int ld_x, const float* w, const float* bias, const void* dy,
+                                    int ld_dy, void* dx, int ld_dx, float* dw, float* dbias, int B, int L, int D, int reverse,
+                                    void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_selective_scan_fwd(int st16, const void* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                                const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                                const void* z, int ld_z, void* y, int ld_y, float* saved, int B, int L, int D, int reverse,
+                                void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_selective_scan_bwd(int st16, const void* u, int ld_u, const float* delta_raw, int ld_delta, const float* dt_bias,
+                                const float* A_log, const float* Bm, int ld_b, const float* Cm, int ld_c, const float* Dp,
+                                const void* z, int ld_z, const void* dy, int ld_dy, const float* saved, float* du, int ld_du,
+                                float* ddelta, int ld_ddelta, float* dBm, int ld_dbm, float* dCm, int ld_dcm, void* dz,
+                                int ld_dz, float* dA_log, float* dD, int B, int L, int D, int reverse, void* ws,
+                                size_t ws_bytes, void* stream);
+int ds6g_cast_h16_f32(int st16, const void* src, float* dst, long n, void* stream);
 
 /* ---- mamba_fusion.hip : the bi-branch Mamba fusion stage around the Mamba layer, fp32 (mambafuser_seq.py:74-231) -------
  * Pointers 16-byte aligned, row strides (ld_*) in floats and multiples of 4; bad arguments return DS6G_ERR_ARG before
