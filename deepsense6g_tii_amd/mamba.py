@@ -8,13 +8,24 @@ interchangeable with mamba_ssm.Mamba(d_model, d_state=16, d_conv=4, expand=2).
     h_t   = exp(delta_t A) h_{t-1} + delta_t x_t Bm_t,  A = -exp(A_log);   y_t = <h_t, Cm_t> + D x_t
     out   = out_proj(y * silu(z))
 
-The four projections are the fp32 implicit-GEMM linears (ops.linear_*); the conv and the scan are csrc/mamba.hip.  One
-extension: forward(u, reverse=True) walks the sequence back to front (== flip(forward(flip(u))) without the copies), which
-the reference's backward_mamba branch needs (mambafuser_seq.py:100-101).
+The four projections are the implicit-GEMM linears (ops.linear_* / ops.bf16_linear_*); the conv and the scan are
+csrc/mamba.hip.  One extension: forward(u, reverse=True) walks the sequence back to front (== flip(forward(flip(u)))
+without the copies), which the reference's backward_mamba branch needs (mambafuser_seq.py:100-101).
 
-16-bit storage: a bf16 / f16 input runs the same layer with its wide activations stored in that type.
+Storage: the input's dtype (fp32, bf16 or f16) is the type the layer's wide activations are stored in.
+layer_forward / layer_backward state the launch sequence once; the conv and scan wrappers (ops.causal_conv1d_silu_*,
+ops.selective_scan_*) pick their entry point by operand dtype, and the storage decides only:
+
+    choice                              fp32               16-bit
+    in_proj / x_proj / out_proj weight  the masters        16-bit copies (weight_copies16, or the caller's w16=)
+    in_proj / out_proj GEMMs            ops.linear_*       ops.bf16_linear_*
+    x_proj forward                      r + 32 columns     rows16 columns from the zero-padded copy, fp32 output
+    x_proj weight gradient reads        xc                 ops.cast_f32(xc)
+    conv backward reads                 dxc                ops.cast_bf16(dxc), ONE rounding
+    dxz, du                             fp32               the 16-bit type
+
 Parameters are fp32 masters with fp32 gradients; all arithmetic inside a kernel, the scan state, its checkpoints and every
-reduction slab are fp32.  r = dt_rank, rows16 = r + 32 rounded up to a multiple of 8:
+reduction slab are fp32.  On 16-bit storage, with r = dt_rank and rows16 = r + 32 rounded up to a multiple of 8:
 
     tensor                          storage   produced by
     u, xz (x | z), xc, y, out       16-bit    in_proj / x_proj / out_proj on the 16-bit GEMM (ops.bf16_linear_*), the 16-bit
@@ -65,45 +76,50 @@ def weight_copies16(mod, params, dtype):
     return tuple(t.data_ptr() for t in ts), ts
 
 
-def _layer_forward16(mod, ws, reverse, save, u2, Bsz, L, params, w16):
-    """layer_forward on 16-bit token rows (the storage map of the module docstring)"""
-    w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
-    M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
-    if w16 is None:
-        w16, _alive = weight_copies16(mod, params, u2.dtype)   # _alive: until the launches below are queued
-    p_in, p_x, p_out = w16
-    xz = ops.bf16_linear_fwd(u2, p_in, 0, 2 * D)
-    z = xz[:, D:]
-    xc = ops.h16_causal_conv1d_silu_fwd(xz[:, :D], conv_w, conv_b, Bsz, L, reverse)
-    x_dbl = ops.bf16_linear_fwd(xc, p_x, 0, x_proj_rows16(r), out16=False)    # fp32 [M, rows16]: dt | Bm | Cm | zero columns
-    dt = ops.copy_cols(x_dbl[:, :r], torch.empty((M, r), dtype=F32, device=u2.device))
-    draw = ops.linear_fwd(dt, w_dt.data_ptr(), 0, D)       # fp32; dt_proj.bias is added inside the scan
-    y, saved = ops.h16_selective_scan_fwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:r + 32], Dp, z, Bsz, L, ws,
-                                          reverse, save)
-    out = ops.bf16_linear_fwd(y, p_out, 0, dm)
-    return out, ((u2, xz, xc, x_dbl, dt, draw, y, saved) if save else None)
+def _check_params(name, params, device):
+    for p in params:
+        if p.device != device:
+            raise RuntimeError(f"{name}: parameters and input must be on the same HIP device")
+        if p.dtype != F32 or not p.is_contiguous():
+            raise ValueError(f"{name}: parameters must be contiguous fp32 tensors")
+
+
+def stream_workspace(cache, device, need):
+    """the ops.Workspace of at least `need` bytes for the current stream of `device`, from a module's own `cache` (raw
+    stream handle -> Workspace; stream order makes the reuse safe)"""
+    key = (device.index, ops._stream())
+    ws = cache.get(key)
+    if ws is None or ws.nbytes < need:
+        cache[key] = ws = ops.Workspace(device, need)
+    return ws
 
 
 def layer_forward(mod, ws, reverse, save, u2, Bsz, L, params, w16=None):
     """the layer on token rows u2 [B*L, d_model] (contiguous) -> (out [B*L, d_model], tape or None).  `params`: the nine
     parameters in Mamba._params() order; `ws`: a Workspace of at least mod.workspace_bytes(B, L).  Shared by _MambaFn and by
     the block-level Function of mamba_fusion.py, which runs two layers inside one autograd node.
-    A bf16 / f16 u2 runs the 16-bit-storage path and returns `out` in u2's dtype.  w16 (that path only): the device pointers
-    weight_copies16 returns, for a caller that keeps 16-bit weight copies of its own; None casts the three weights here, on
-    every call."""
-    if u2.dtype != F32:
-        return _layer_forward16(mod, ws, reverse, save, u2, Bsz, L, params, w16)
+    u2's dtype is the storage type (the map of the module docstring), and `out`'s.  w16 (16-bit storage only): the device
+    pointers weight_copies16 returns, for a caller that keeps 16-bit weight copies of its own; None casts the three weights
+    here, on every call."""
     w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
     M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
-    xz = ops.linear_fwd(u2, w_in.data_ptr(), 0, 2 * D)
+    if u2.dtype == F32:
+        linear, (p_in, p_x, p_out) = ops.linear_fwd, (w_in.data_ptr(), w_x.data_ptr(), w_out.data_ptr())
+        n_x, x_dbl_kw = r + 32, {}
+    else:
+        if w16 is None:
+            w16, _alive = weight_copies16(mod, params, u2.dtype)   # _alive: until the launches below are queued
+        linear, (p_in, p_x, p_out) = ops.bf16_linear_fwd, w16
+        n_x, x_dbl_kw = x_proj_rows16(r), dict(out16=False)        # fp32 x_dbl from the zero-padded weight copy
+    xz = linear(u2, p_in, 0, 2 * D)
     z = xz[:, D:]
     xc = ops.causal_conv1d_silu_fwd(xz[:, :D], conv_w, conv_b, Bsz, L, reverse)
-    x_dbl = ops.linear_fwd(xc, w_x.data_ptr(), 0, r + 32)
+    x_dbl = linear(xc, p_x, 0, n_x, **x_dbl_kw)             # fp32 [M, n_x]: dt | Bm | Cm (| zero columns)
     dt = ops.copy_cols(x_dbl[:, :r], torch.empty((M, r), dtype=F32, device=u2.device))
-    draw = ops.linear_fwd(dt, w_dt.data_ptr(), 0, D)       # dt_proj.bias is added inside the scan
-    y, saved = ops.selective_scan_fwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, z, Bsz, L, ws,
+    draw = ops.linear_fwd(dt, w_dt.data_ptr(), 0, D)       # fp32; dt_proj.bias is added inside the scan
+    y, saved = ops.selective_scan_fwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:r + 32], Dp, z, Bsz, L, ws,
                                       reverse, save)
-    out = ops.linear_fwd(y, w_out.data_ptr(), 0, dm)
+    out = linear(y, p_out, 0, dm)
     return out, ((u2, xz, xc, x_dbl, dt, draw, y, saved) if save else None)
 
 
@@ -133,15 +149,25 @@ def deliver_pair(fn, slot_a, slot_b, shape_a, shape_b, device, has_flag=True):
         ops.lib().axpby(t.data_ptr(), p if a else 0, p, t.numel(), 1.0, 1.0, st)
 
 
-def _layer_backward16(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out, gdst, w16):
-    """layer_backward on a 16-bit tape and dout2 (the storage map of the module docstring); parameter gradients fp32"""
+def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None, gdst=None, w16=None):
+    """-> (du [B*L, d_model], the nine parameter gradients in Mamba._params() order).  du_out: an existing gradient of the
+    layer's input that du is ADDED to (the in_proj data-gradient GEMM accumulates into it).  gdst: nine (device pointer,
+    accumulate flag) pairs in the same order - the gradients are written there in place (added where the flag is set) and
+    None is returned in their stead; the conv and scan kernels have no accumulate flag, so a set flag takes those four
+    through a temporary and an add, a fresh gradient (the training case) does not.
+    dout2's dtype is the storage type, the one of the forward that made the tape, and du's.  On 16-bit storage du_out may be
+    of that dtype (added to with one rounding) or fp32; the parameter gradients and gdst are fp32; w16 as in layer_forward."""
     u2, xz, xc, x_dbl, dt, draw, y, saved = tape
     w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
     M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
-    dev, h16 = dout2.device, dout2.dtype
-    if w16 is None:
-        w16, _alive = weight_copies16(mod, params, h16)
-    p_in, _, p_out = w16
+    dev, st = dout2.device, dout2.dtype
+    h16 = st != F32
+    if not h16:
+        wgrad, dgrad, p_in, p_out = ops.linear_wgrad, ops.linear_dgrad, w_in.data_ptr(), w_out.data_ptr()
+    else:
+        if w16 is None:
+            w16, _alive = weight_copies16(mod, params, st)   # _alive: until the launches below are queued
+        wgrad, dgrad, (p_in, _, p_out) = ops.bf16_linear_wgrad, ops.bf16_linear_dgrad, w16
 
     def empty(*shape, dtype=F32):
         return torch.empty(shape, dtype=dtype, device=dev)
@@ -149,78 +175,34 @@ def _layer_backward16(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out, gds
     shapes = ((2 * D, dm), (D, 1, 4), (D,), (r + 32, D), (D, r), (D,), (D, 16), (D,), (dm, D))
     (s_in, s_cw, s_cb, s_x, s_dtw, s_dtb, s_A, s_D, s_out), grads = grad_slots(shapes, dev, gdst)
 
-    ops.bf16_linear_wgrad(y, dout2, s_out[0], ws, accumulate=bool(s_out[1]))
-    dy = ops.bf16_linear_dgrad(dout2, p_out, D)
-    dxz, dxdbl, dxc, ddraw = empty(M, 2 * D, dtype=h16), empty(M, r + 32), empty(M, D), empty(M, D)
-    Bm, Cm = x_dbl[:, r:r + 16], x_dbl[:, r + 16:r + 32]
+    wgrad(y, dout2, s_out[0], ws, accumulate=bool(s_out[1]))
+    dy = dgrad(dout2, p_out, D)
+    dxz, dxdbl, dxc, ddraw = empty(M, 2 * D, dtype=st), empty(M, r + 32), empty(M, D), empty(M, D)
 
     def scan(pa, pd, _acc):
-        ops.h16_selective_scan_bwd(xc, draw, b_dt, A_log, Bm, Cm, Dp, xz[:, D:], dy, saved, dxc, ddraw, dxdbl[:, r:r + 16],
-                                   dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse, out=(pa, pd))
+        ops.selective_scan_bwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:r + 32], Dp, xz[:, D:], dy, saved,
+                               dxc, ddraw, dxdbl[:, r:r + 16], dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse,
+                               out=(pa, pd))
     deliver_pair(scan, s_A, s_D, shapes[6], shapes[7], dev, has_flag=False)
     deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(dt, ddraw, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_dtw, s_dtb,
                  shapes[4], shapes[5], dev)
     ops.copy_cols(ops.linear_dgrad(ddraw, w_dt.data_ptr(), r), dxdbl[:, :r])
-    # x_proj's r + 32 rows fit neither the 16-bit wgrad (rows % 8) nor its dgrad (contraction % 64): both stay fp32 GEMMs, the
-    # weight gradient on an fp32 widening of xc, the data gradient added to the scan's fp32 du
-    ops.linear_wgrad(ops.cast_f32(xc), dxdbl, s_x[0], ws, accumulate=bool(s_x[1]))
+    # x_proj's r + 32 rows fit neither the 16-bit wgrad (rows % 8) nor its dgrad (contraction % 64): on every storage both
+    # are fp32 GEMMs, the weight gradient on xc (16-bit: an fp32 widening of it), the data gradient added to the scan's fp32
+    # du; the conv backward reads that sum in the storage type (16-bit: ONE rounding)
+    ops.linear_wgrad(ops.cast_f32(xc) if h16 else xc, dxdbl, s_x[0], ws, accumulate=bool(s_x[1]))
     ops.linear_dgrad(dxdbl, w_x.data_ptr(), D, out=dxc, accumulate=True)
-    dxc16 = ops.cast_bf16(dxc, dtype=h16)
+    dxc_st = ops.cast_bf16(dxc, dtype=st) if h16 else dxc
 
     def conv(pw, pb, _acc):
-        ops.h16_causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc16, dxz[:, :D], Bsz, L, ws, reverse, out=(pw, pb))
+        ops.causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc_st, dxz[:, :D], Bsz, L, ws, reverse, out=(pw, pb))
     deliver_pair(conv, s_cw, s_cb, shapes[1], shapes[2], dev, has_flag=False)
-    ops.bf16_linear_wgrad(u2, dxz, s_in[0], ws, accumulate=bool(s_in[1]))
+    wgrad(u2, dxz, s_in[0], ws, accumulate=bool(s_in[1]))
     if du_out is None:
-        du = ops.bf16_linear_dgrad(dxz, p_in, dm)
+        du = dgrad(dxz, p_in, dm)
     else:
-        du = ops.bf16_linear_dgrad(dxz, p_in, dm, out16=du_out.dtype != F32, out=du_out, accumulate=True)
-    return du, grads
-
-
-def layer_backward(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out=None, gdst=None, w16=None):
-    """-> (du [B*L, d_model], the nine parameter gradients in Mamba._params() order).  du_out: an existing gradient of the
-    layer's input that du is ADDED to (the in_proj data-gradient GEMM accumulates into it).  gdst: nine (device pointer,
-    accumulate flag) pairs in the same order - the gradients are written there in place (added where the flag is set) and
-    None is returned in their stead; the conv and scan kernels have no accumulate flag, so a set flag takes those four
-    through a temporary and an add, a fresh gradient (the training case) does not.
-    A bf16 / f16 dout2 (with the tape of a 16-bit forward) runs the 16-bit-storage path: du has dout2's dtype, du_out may be
-    of that dtype (added to with one rounding) or fp32, the parameter gradients and gdst stay fp32; w16 as in layer_forward."""
-    if dout2.dtype != F32:
-        return _layer_backward16(mod, ws, reverse, Bsz, L, tape, params, dout2, du_out, gdst, w16)
-    u2, xz, xc, x_dbl, dt, draw, y, saved = tape
-    w_in, conv_w, conv_b, w_x, w_dt, b_dt, A_log, Dp, w_out = params
-    M, D, r, dm = Bsz * L, mod.d_inner, mod.dt_rank, mod.d_model
-    dev = dout2.device
-
-    def empty(*shape):
-        return torch.empty(shape, dtype=F32, device=dev)
-
-    shapes = ((2 * D, dm), (D, 1, 4), (D,), (r + 32, D), (D, r), (D,), (D, 16), (D,), (dm, D))
-    (s_in, s_cw, s_cb, s_x, s_dtw, s_dtb, s_A, s_D, s_out), grads = grad_slots(shapes, dev, gdst)
-
-    ops.linear_wgrad(y, dout2, s_out[0], ws, accumulate=bool(s_out[1]))
-    dy = ops.linear_dgrad(dout2, w_out.data_ptr(), D)
-    dxz, dxdbl, dxc, ddraw = empty(M, 2 * D), empty(M, r + 32), empty(M, D), empty(M, D)
-
-    def scan(pa, pd, _acc):
-        ops.selective_scan_bwd(xc, draw, b_dt, A_log, x_dbl[:, r:r + 16], x_dbl[:, r + 16:], Dp, xz[:, D:], dy, saved, dxc,
-                               ddraw, dxdbl[:, r:r + 16], dxdbl[:, r + 16:], dxz[:, D:], Bsz, L, ws, reverse, out=(pa, pd))
-    deliver_pair(scan, s_A, s_D, shapes[6], shapes[7], dev, has_flag=False)
-    deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(dt, ddraw, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_dtw, s_dtb,
-                 shapes[4], shapes[5], dev)
-    ops.copy_cols(ops.linear_dgrad(ddraw, w_dt.data_ptr(), r), dxdbl[:, :r])
-    ops.linear_wgrad(xc, dxdbl, s_x[0], ws, accumulate=bool(s_x[1]))
-    ops.linear_dgrad(dxdbl, w_x.data_ptr(), D, out=dxc, accumulate=True)
-
-    def conv(pw, pb, _acc):
-        ops.causal_conv1d_silu_bwd(xz[:, :D], conv_w, conv_b, dxc, dxz[:, :D], Bsz, L, ws, reverse, out=(pw, pb))
-    deliver_pair(conv, s_cw, s_cb, shapes[1], shapes[2], dev, has_flag=False)
-    ops.linear_wgrad(u2, dxz, s_in[0], ws, accumulate=bool(s_in[1]))
-    if du_out is None:
-        du = ops.linear_dgrad(dxz, w_in.data_ptr(), dm)
-    else:
-        du = ops.linear_dgrad(dxz, w_in.data_ptr(), dm, out=du_out, accumulate=True)
+        du_kw = dict(out16=du_out.dtype != F32) if h16 else {}
+        du = dgrad(dxz, p_in, dm, out=du_out, accumulate=True, **du_kw)
     return du, grads
 
 
@@ -299,7 +281,7 @@ class Mamba(nn.Module):
         self.D = nn.Parameter(torch.ones(d_inner, **kw))
         self.D._no_weight_decay = True
         self.out_proj = nn.Linear(d_inner, d_model, bias=False, **kw)
-        self._ws = {}   # raw stream handle -> ops.Workspace (per instance; stream order makes the reuse safe)
+        self._ws = {}   # stream_workspace's per-instance cache
 
     def workspace_bytes(self, B, L):
         from ._lib import lib
@@ -308,12 +290,7 @@ class Mamba(nn.Module):
                    _MIN_WS)
 
     def _workspace(self, device, B, L):
-        need = self.workspace_bytes(B, L)
-        key = (device.index, ops._stream())
-        ws = self._ws.get(key)
-        if ws is None or ws.nbytes < need:
-            self._ws[key] = ws = ops.Workspace(device, need)
-        return ws
+        return stream_workspace(self._ws, device, self.workspace_bytes(B, L))
 
     def _params(self):
         return (self.in_proj.weight, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
@@ -330,11 +307,7 @@ class Mamba(nn.Module):
             raise ValueError(f"Mamba: expected a (B, L, {self.d_model}) fp32, bf16 or f16 tensor, got {tuple(u.shape)} "
                              f"{u.dtype}")
         params = self._params()
-        for p in params:
-            if p.device != u.device:
-                raise RuntimeError("Mamba: parameters and input must be on the same HIP device")
-            if p.dtype != F32 or not p.is_contiguous():
-                raise ValueError("Mamba: parameters must be contiguous fp32 tensors")
+        _check_params("Mamba", params, u.device)
         save = torch.is_grad_enabled() and self.training and (u.requires_grad or any(p.requires_grad for p in params))
         with torch.cuda.device(u.device):
             if save:

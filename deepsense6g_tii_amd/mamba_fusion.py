@@ -42,17 +42,9 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .mamba import Mamba, deliver_pair, grad_slots, layer_forward, layer_backward
+from .mamba import Mamba, _check_params, deliver_pair, grad_slots, layer_forward, layer_backward, stream_workspace
 
 F32 = torch.float32
-
-
-def _check_params(name, params, device):
-    for p in params:
-        if p.device != device:
-            raise RuntimeError(f"{name}: parameters and input must be on the same HIP device")
-        if p.dtype != F32 or not p.is_contiguous():
-            raise ValueError(f"{name}: parameters must be contiguous fp32 tensors")
 
 
 def _empty(dev, *shape):
@@ -153,12 +145,7 @@ class MambaBlock(nn.Module):
         return max(self.forward_mamba.workspace_bytes(B, T), ops.sample_layernorm_workspace_bytes(B, T * self.n_embd))
 
     def _workspace(self, device, B, T):
-        need = self.workspace_bytes(B, T)
-        key = (device.index, ops._stream())
-        ws = self._ws.get(key)
-        if ws is None or ws.nbytes < need:
-            self._ws[key] = ws = ops.Workspace(device, need)
-        return ws
+        return stream_workspace(self._ws, device, self.workspace_bytes(B, T))
 
     def _params(self):
         return (self.ln1.weight, self.ln1.bias, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,

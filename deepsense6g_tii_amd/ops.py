@@ -936,11 +936,23 @@ def head_bwd(dfused, dfeat, frames_per_sample):
 
 
 # ------------------------------------------------------------------------------------------------
-# Mamba layer (csrc/mamba.hip): token-major [B*L, D] operands that may be column blocks of a wider matrix
-def _rows_al(t, M, C):
-    ld = _rows(t, M, C)
-    assert t.data_ptr() % 16 == 0 and (M == 1 or ld >= C), (t.data_ptr(), ld, C)
-    return max(ld, C)   # a one-row view reports an arbitrary stride
+# Mamba layer (csrc/mamba.hip): token-major [B*L, D] operands that may be column blocks of a wider matrix.  The conv and the
+# scan run on fp32, bf16 or f16 storage, named by the dtype of their first wide operand (x / u): the operands that follow it
+# (conv: x, y, dy, dx; scan: u, z, y, dy, dz) all have that dtype, every other operand, the parameters and their gradients
+# are fp32 (the storage map of include/ds6g.h).  Each operand is checked against the dtype that map gives it, so no 16-bit
+# buffer is read as fp32 or the other way round.
+def _rows_al(t, M, C, dtype=F32):
+    """[M, C] operand of `dtype` (fp32, bf16 or f16) whose rows may be a column block of a wider matrix -> its row stride in
+    elements of that type: whole 16-byte pieces (4 fp32, 8 16-bit elements) from a 16-byte aligned base"""
+    assert dtype == F32 or dtype in _ST16, dtype
+    assert t.dtype == dtype and t.is_cuda and tuple(t.shape) == (M, C) and t.stride(1) == 1, \
+        (t.dtype, dtype, tuple(t.shape), (M, C), t.stride())
+    s0 = t.stride(0)
+    if dtype == F32:   # fp32 rows also have to be whole pieces apart, and more than one row may not overlap
+        assert s0 % 4 == 0 and (M == 1 or s0 >= C), (s0, C)
+    ld = max(s0, C)   # a one-row view reports an arbitrary stride
+    assert t.data_ptr() % 16 == 0 and ld % (16 // t.element_size()) == 0, (t.data_ptr(), ld)
+    return ld
 
 
 def _vec(t, *shape):
@@ -978,49 +990,55 @@ def copy_cols(src, dst):
 
 
 def causal_conv1d_silu_fwd(x, w, bias, B, L, reverse=False):
-    """silu(causal depthwise conv1d(x) + bias): x [B*L, D] (a column block allowed), w conv1d.weight (D, 1, 4) -> [B*L, D]"""
+    """silu(causal depthwise conv1d(x) + bias): x [B*L, D] (a column block allowed), w conv1d.weight (D, 1, 4) -> [B*L, D] of
+    x's dtype"""
     M, D = x.shape
     assert M == B * L and D % 128 == 0
-    y = torch.empty((M, D), dtype=F32, device=x.device)
-    lib().causal_conv1d_silu_fwd(_p(x), _rows_al(x, M, D), _vec(w, D, 1, 4), _vec(bias, D), _p(y), D, B, L, D, int(reverse),
-                                 _stream())
+    st = x.dtype
+    y = torch.empty((M, D), dtype=st, device=x.device)
+    _launch(lib().causal_conv1d_silu_fwd, lib().h16_causal_conv1d_silu_fwd, st, _p(x), _rows_al(x, M, D, st),
+            _vec(w, D, 1, 4), _vec(bias, D), _p(y), D, B, L, D, int(reverse))
     return y
 
 
 def causal_conv1d_silu_bwd(x, w, bias, dy, dx, B, L, ws: Workspace, reverse=False, out=None):
-    """-> (dw (D, 1, 4), dbias (D,)); dx [B*L, D] is written in place (a column block allowed).  out: the caller's (dw, dbias)
-    tensors or device pointers, written (not added to) instead of two fresh tensors"""
+    """-> (dw (D, 1, 4), dbias (D,)), fp32; dx [B*L, D] is written in place (a column block allowed); dy and dx have x's dtype.
+    out: the caller's (dw, dbias) tensors or device pointers, written (not added to) instead of two fresh tensors"""
     M, D = x.shape
     assert M == B * L and D % 128 == 0
     assert ws.nbytes >= int(lib().causal_conv1d_workspace_bytes(B, L, D)), "workspace too small for causal_conv1d_silu_bwd"
     if out is None:
         out = (torch.empty((D, 1, 4), dtype=F32, device=x.device), torch.empty((D,), dtype=F32, device=x.device))
     dw, db = out
-    lib().causal_conv1d_silu_bwd(_p(x), _rows_al(x, M, D), _vec(w, D, 1, 4), _vec(bias, D), _p(dy), _rows_al(dy, M, D),
-                                 _p(dx), _rows_al(dx, M, D), _dst(dw, D, 1, 4), _dst(db, D), B, L, D, int(reverse), ws.ptr,
-                                 ws.nbytes, _stream())
+    st = x.dtype
+    _launch(lib().causal_conv1d_silu_bwd, lib().h16_causal_conv1d_silu_bwd, st, _p(x), _rows_al(x, M, D, st),
+            _vec(w, D, 1, 4), _vec(bias, D), _p(dy), _rows_al(dy, M, D, st), _p(dx), _rows_al(dx, M, D, st), _dst(dw, D, 1, 4),
+            _dst(db, D), B, L, D, int(reverse), ws.ptr, ws.nbytes)
     return dw, db
 
 
 def selective_scan_fwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, B, L, ws: Workspace, reverse=False, save=False):
-    """-> (y [B*L, D], saved or None).  u / delta_raw / z: [B*L, D], Bm / Cm: [B*L, 16] (column blocks allowed);
-    dt_bias, Dp: (D,), A_log: (D, 16).  save: also return the chunk-start states selective_scan_bwd needs."""
+    """-> (y [B*L, D] of u's dtype, saved or None).  u / z: [B*L, D] of one dtype, delta_raw: [B*L, D], Bm / Cm: [B*L, 16]
+    fp32 (column blocks allowed); dt_bias, Dp: (D,), A_log: (D, 16).  save: also return the fp32 chunk-start states
+    selective_scan_bwd needs."""
     M, D = u.shape
     assert M == B * L and D % 128 == 0
     assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_fwd"
-    y = torch.empty((M, D), dtype=F32, device=u.device)
+    st = u.dtype
+    y = torch.empty((M, D), dtype=st, device=u.device)
     saved = torch.empty(int(lib().selective_scan_saved_floats(B, L, D)), dtype=F32, device=u.device) if save else None
-    lib().selective_scan_fwd(_p(u), _rows_al(u, M, D), _p(delta_raw), _rows_al(delta_raw, M, D), _vec(dt_bias, D),
-                             _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16), _vec(Dp, D),
-                             _p(z), _rows_al(z, M, D), _p(y), D, _p(saved), B, L, D, int(reverse), ws.ptr, ws.nbytes,
-                             _stream())
+    _launch(lib().selective_scan_fwd, lib().h16_selective_scan_fwd, st, _p(u), _rows_al(u, M, D, st), _p(delta_raw),
+            _rows_al(delta_raw, M, D), _vec(dt_bias, D), _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm),
+            _rows_al(Cm, M, 16), _vec(Dp, D), _p(z), _rows_al(z, M, D, st), _p(y), D, _p(saved), B, L, D, int(reverse), ws.ptr,
+            ws.nbytes)
     return y, saved
 
 
 def selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, du, ddelta, dBm, dCm, dz, B, L,
                        ws: Workspace, reverse=False, out=None):
-    """writes du, ddelta (= d delta_raw), dz [B*L, D] and dBm, dCm [B*L, 16] in place (column blocks allowed)
-    -> (dA_log (D, 16), dD (D,)).  out: the caller's (dA_log, dD) tensors or device pointers, written (not added to)"""
+    """writes dz [B*L, D] of u's dtype (as are z and dy), fp32 du, ddelta (= d delta_raw) [B*L, D] and dBm, dCm [B*L, 16] in
+    place (column blocks allowed) -> fp32 (dA_log (D, 16), dD (D,)).  out: the caller's (dA_log, dD) tensors or device
+    pointers, written (not added to)"""
     M, D = u.shape
     assert M == B * L and D % 128 == 0
     assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_bwd"
@@ -1029,23 +1047,14 @@ def selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, d
     if out is None:
         out = (torch.empty((D, 16), dtype=F32, device=u.device), torch.empty((D,), dtype=F32, device=u.device))
     dA, dD = out
-    lib().selective_scan_bwd(_p(u), _rows_al(u, M, D), _p(delta_raw), _rows_al(delta_raw, M, D), _vec(dt_bias, D),
-                             _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16), _vec(Dp, D),
-                             _p(z), _rows_al(z, M, D), _p(dy), _rows_al(dy, M, D), _p(saved), _p(du), _rows_al(du, M, D),
-                             _p(ddelta), _rows_al(ddelta, M, D), _p(dBm), _rows_al(dBm, M, 16), _p(dCm),
-                             _rows_al(dCm, M, 16), _p(dz), _rows_al(dz, M, D), _dst(dA, D, 16), _dst(dD, D), B, L, D,
-                             int(reverse), ws.ptr, ws.nbytes, _stream())
+    st = u.dtype
+    _launch(lib().selective_scan_bwd, lib().h16_selective_scan_bwd, st, _p(u), _rows_al(u, M, D, st), _p(delta_raw),
+            _rows_al(delta_raw, M, D), _vec(dt_bias, D), _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm),
+            _rows_al(Cm, M, 16), _vec(Dp, D), _p(z), _rows_al(z, M, D, st), _p(dy), _rows_al(dy, M, D, st), _p(saved), _p(du),
+            _rows_al(du, M, D), _p(ddelta), _rows_al(ddelta, M, D), _p(dBm), _rows_al(dBm, M, 16), _p(dCm),
+            _rows_al(dCm, M, 16), _p(dz), _rows_al(dz, M, D, st), _dst(dA, D, 16), _dst(dD, D), B, L, D, int(reverse), ws.ptr,
+            ws.nbytes)
     return dA, dD
-
-
-# The same four operators on 16-bit storage (ds6g_h16_causal_conv1d_* / ds6g_h16_selective_scan_*): the wide activations are
-# bf16 / f16, every operand of one call shares that dtype; the narrow operands, the parameters and their gradients stay fp32.
-def _rows_al16(t, M, C, dtype):
-    assert t.dtype == dtype and dtype in _ST16, (t.dtype, dtype)
-    assert t.is_cuda and t.dim() == 2 and tuple(t.shape) == (M, C) and t.stride(1) == 1, (tuple(t.shape), t.stride())
-    ld = max(t.stride(0), C)   # a one-row view reports an arbitrary stride
-    assert t.data_ptr() % 16 == 0 and ld % 8 == 0, (t.data_ptr(), ld)
-    return ld
 
 
 def cast_f32(src, out=None):
@@ -1056,69 +1065,6 @@ def cast_f32(src, out=None):
     assert dst.numel() == src.numel()
     lib().cast_h16_f32(_ST16[src.dtype], _p(src), _p(dst), src.numel(), _stream())
     return dst
-
-
-def h16_causal_conv1d_silu_fwd(x, w, bias, B, L, reverse=False):
-    """causal_conv1d_silu_fwd on a 16-bit x [B*L, D] (a column block allowed) -> y [B*L, D] of x's dtype; w, bias fp32"""
-    M, D = x.shape
-    assert M == B * L and D % 128 == 0
-    y = torch.empty((M, D), dtype=x.dtype, device=x.device)
-    lib().h16_causal_conv1d_silu_fwd(_ST16[x.dtype], _p(x), _rows_al16(x, M, D, x.dtype), _vec(w, D, 1, 4), _vec(bias, D), _p(y),
-                                     D, B, L, D, int(reverse), _stream())
-    return y
-
-
-def h16_causal_conv1d_silu_bwd(x, w, bias, dy, dx, B, L, ws: Workspace, reverse=False, out=None):
-    """causal_conv1d_silu_bwd on 16-bit x, dy, dx (column blocks allowed) -> fp32 (dw, dbias), as the fp32 wrapper"""
-    M, D = x.shape
-    assert M == B * L and D % 128 == 0
-    assert ws.nbytes >= int(lib().causal_conv1d_workspace_bytes(B, L, D)), "workspace too small for causal_conv1d_silu_bwd"
-    if out is None:
-        out = (torch.empty((D, 1, 4), dtype=F32, device=x.device), torch.empty((D,), dtype=F32, device=x.device))
-    dw, db = out
-    dt = x.dtype
-    lib().h16_causal_conv1d_silu_bwd(_ST16[dt], _p(x), _rows_al16(x, M, D, dt), _vec(w, D, 1, 4), _vec(bias, D), _p(dy),
-                                     _rows_al16(dy, M, D, dt), _p(dx), _rows_al16(dx, M, D, dt), _dst(dw, D, 1, 4), _dst(db, D),
-                                     B, L, D, int(reverse), ws.ptr, ws.nbytes, _stream())
-    return dw, db
-
-
-def h16_selective_scan_fwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, B, L, ws: Workspace, reverse=False, save=False):
-    """selective_scan_fwd with 16-bit u, z (column blocks allowed) -> (y of their dtype, saved fp32 or None); delta_raw, Bm,
-    Cm and the parameters are fp32"""
-    M, D = u.shape
-    assert M == B * L and D % 128 == 0
-    assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_fwd"
-    dt = u.dtype
-    y = torch.empty((M, D), dtype=dt, device=u.device)
-    saved = torch.empty(int(lib().selective_scan_saved_floats(B, L, D)), dtype=F32, device=u.device) if save else None
-    lib().h16_selective_scan_fwd(_ST16[dt], _p(u), _rows_al16(u, M, D, dt), _p(delta_raw), _rows_al(delta_raw, M, D),
-                                 _vec(dt_bias, D), _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16),
-                                 _vec(Dp, D), _p(z), _rows_al16(z, M, D, dt), _p(y), D, _p(saved), B, L, D, int(reverse),
-                                 ws.ptr, ws.nbytes, _stream())
-    return y, saved
-
-
-def h16_selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, du, ddelta, dBm, dCm, dz, B, L,
-                           ws: Workspace, reverse=False, out=None):
-    """selective_scan_bwd with 16-bit u, z, dy and a 16-bit dz; du, ddelta [B*L, D] and dBm, dCm [B*L, 16] are written as fp32
-    -> fp32 (dA_log, dD), as the fp32 wrapper"""
-    M, D = u.shape
-    assert M == B * L and D % 128 == 0
-    assert ws.nbytes >= int(lib().selective_scan_workspace_bytes(B, L, D)), "workspace too small for selective_scan_bwd"
-    assert saved.dtype == F32 and saved.is_cuda and saved.is_contiguous() and \
-        saved.numel() == int(lib().selective_scan_saved_floats(B, L, D)), tuple(saved.shape)
-    if out is None:
-        out = (torch.empty((D, 16), dtype=F32, device=u.device), torch.empty((D,), dtype=F32, device=u.device))
-    dA, dD = out
-    dt = u.dtype
-    lib().h16_selective_scan_bwd(_ST16[dt], _p(u), _rows_al16(u, M, D, dt), _p(delta_raw), _rows_al(delta_raw, M, D),
-                                 _vec(dt_bias, D), _vec(A_log, D, 16), _p(Bm), _rows_al(Bm, M, 16), _p(Cm), _rows_al(Cm, M, 16),
-                                 _vec(Dp, D), _p(z), _rows_al16(z, M, D, dt), _p(dy), _rows_al16(dy, M, D, dt), _p(saved),
-                                 _p(du), _rows_al(du, M, D), _p(ddelta), _rows_al(ddelta, M, D), _p(dBm), _rows_al(dBm, M, 16),
-                                 _p(dCm), _rows_al(dCm, M, 16), _p(dz), _rows_al16(dz, M, D, dt), _dst(dA, D, 16), _dst(dD, D),
-                                 B, L, D, int(reverse), ws.ptr, ws.nbytes, _stream())
-    return dA, dD
 
 
 # ------------------------------------------------------------------------------------------------

@@ -29,8 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .mamba import Mamba, layer_forward, layer_backward
-from .mamba_fusion import _check_params
+from .mamba import Mamba, _check_params, layer_forward, layer_backward
 
 F32 = torch.float32
 D_MODEL = 512

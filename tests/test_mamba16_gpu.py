@@ -372,3 +372,95 @@ def test_module_runs_bf16_and_keeps_its_fp32_bits():
         assert m(u.half()).dtype == torch.float16
         after = m(u)
     assert torch.equal(moat.bits(after), moat.bits(before))   # workspace and weight copies do not leak between the paths
+
+
+# ---- 7. the wrappers pick the entry point and type every operand ------------------------------------------------------
+_ENTRIES = ("causal_conv1d_silu_fwd", "causal_conv1d_silu_bwd", "selective_scan_fwd", "selective_scan_bwd")
+
+
+def test_wrappers_pick_entry_by_storage_and_refuse_mixed_operands(monkeypatch):
+    """ops.causal_conv1d_silu_* / ops.selective_scan_* on fp32, bf16 and f16: which of the eight entry points is called, with
+    which storage code and row strides, and that an operand of the wrong dtype is refused before anything is called.  The
+    entry points are replaced by recording stubs for the test: no kernel runs, so none reads mistyped memory."""
+    ops, lib = _ops(), _lib()
+    calls = []
+    for e in _ENTRIES:
+        for name in (e, "h16_" + e):
+            monkeypatch.setattr(lib, name, lambda *a, _n=name: calls.append((_n, a)))
+    Bq, L, M, X = 1, 4, 4, R + 32
+    ws = ops.Workspace(torch.device(DEV), max(int(lib.selective_scan_workspace_bytes(Bq, L, D)),
+                                              int(lib.causal_conv1d_workspace_bytes(Bq, L, D))))
+    z = lambda *s, dt=F32: torch.zeros(s, dtype=dt, device=DEV)
+    w, bias, dtb, A_log, Dp = z(D, 1, 4), z(D), z(D), z(D, 16), z(D)
+    draw, du, dd, x_dbl, dxdbl = z(M, D), z(M, D), z(M, D), z(M, X), z(M, X)
+    saved = z(int(lib.selective_scan_saved_floats(Bq, L, D)))
+    Bm, Cm, dBm, dCm = x_dbl[:, R:R + 16], x_dbl[:, R + 16:], dxdbl[:, R:R + 16], dxdbl[:, R + 16:]
+    wide = {dt: (z(M, 2 * D, dt=dt), z(M, 2 * D, dt=dt), z(M, D, dt=dt)) for dt in (F32, *DTYPES)}   # xz, dxz, dy
+
+    def one(fn, *a, **k):
+        """-> (entry name, its arguments without the stream, what the wrapper returned) of the ONE call fn makes"""
+        del calls[:]
+        ret = fn(*a, **k)
+        assert len(calls) == 1, calls
+        return calls[0][0], calls[0][1][:-1], ret
+
+    for dt in (F32, *DTYPES):
+        xz, dxz, dy = wide[dt]
+        x, zz, dx, dz = xz[:, :D], xz[:, D:], dxz[:, :D], dxz[:, D:]
+
+        def entry(name, args):
+            """the entry point of this storage was called; -> its arguments after the storage code"""
+            if dt == F32:
+                assert name == entry.want, (name, dt)
+                return args
+            assert name == "h16_" + entry.want and args[0] == ST[dt], (name, args[0], dt)
+            return args[1:]
+
+        entry.want = "causal_conv1d_silu_fwd"
+        name, args, y = one(ops.causal_conv1d_silu_fwd, x, w, bias, Bq, L)
+        a = entry(name, args)
+        assert y.dtype == dt and tuple(y.shape) == (M, D)
+        assert a == (x.data_ptr(), 2 * D, w.data_ptr(), bias.data_ptr(), y.data_ptr(), D, Bq, L, D, 0)
+
+        entry.want = "causal_conv1d_silu_bwd"
+        dwb = (z(D, 1, 4), z(D))
+        name, args, _ = one(ops.causal_conv1d_silu_bwd, x, w, bias, dy, dx, Bq, L, ws, out=dwb)
+        a = entry(name, args)
+        assert a == (x.data_ptr(), 2 * D, w.data_ptr(), bias.data_ptr(), dy.data_ptr(), D, dx.data_ptr(), 2 * D,
+                     dwb[0].data_ptr(), dwb[1].data_ptr(), Bq, L, D, 0, ws.ptr, ws.nbytes)
+
+        entry.want = "selective_scan_fwd"
+        name, args, (y, sv) = one(ops.selective_scan_fwd, x, draw, dtb, A_log, Bm, Cm, Dp, zz, Bq, L, ws, save=True)
+        a = entry(name, args)
+        assert y.dtype == dt and tuple(y.shape) == (M, D) and sv.dtype == F32
+        assert a == (x.data_ptr(), 2 * D, draw.data_ptr(), D, dtb.data_ptr(), A_log.data_ptr(), Bm.data_ptr(), X, Cm.data_ptr(),
+                     X, Dp.data_ptr(), zz.data_ptr(), 2 * D, y.data_ptr(), D, sv.data_ptr(), Bq, L, D, 0, ws.ptr, ws.nbytes)
+
+        entry.want = "selective_scan_bwd"
+        dAD = (z(D, 16), z(D))
+        name, args, _ = one(ops.selective_scan_bwd, x, draw, dtb, A_log, Bm, Cm, Dp, zz, dy, saved, du, dd, dBm, dCm, dz, Bq, L,
+                            ws, out=dAD)
+        a = entry(name, args)
+        assert a == (x.data_ptr(), 2 * D, draw.data_ptr(), D, dtb.data_ptr(), A_log.data_ptr(), Bm.data_ptr(), X, Cm.data_ptr(),
+                     X, Dp.data_ptr(), zz.data_ptr(), 2 * D, dy.data_ptr(), D, saved.data_ptr(), du.data_ptr(), D,
+                     dd.data_ptr(), D, dBm.data_ptr(), X, dCm.data_ptr(), X, dz.data_ptr(), 2 * D, dAD[0].data_ptr(),
+                     dAD[1].data_ptr(), Bq, L, D, 0, ws.ptr, ws.nbytes)
+
+    bf, hf = torch.bfloat16, torch.float16
+    (xz32, dxz32, dy32), (xzb, dxzb, dyb), (xzh, dxzh, dyh) = wide[F32], wide[bf], wide[hf]
+    scan_f = lambda u, raw, zz: ops.selective_scan_fwd(u, raw, dtb, A_log, Bm, Cm, Dp, zz, Bq, L, ws)
+    scan_b = lambda u, zz, dy, du_, dz: ops.selective_scan_bwd(u, draw, dtb, A_log, Bm, Cm, Dp, zz, dy, saved, du_, dd, dBm,
+                                                              dCm, dz, Bq, L, ws)
+    mixed = {
+        "conv bwd: fp32 x, bf16 dy": lambda: ops.causal_conv1d_silu_bwd(xz32[:, :D], w, bias, dyb, dxz32[:, :D], Bq, L, ws),
+        "conv bwd: bf16 x, f16 dx": lambda: ops.causal_conv1d_silu_bwd(xzb[:, :D], w, bias, dyb, dxzh[:, :D], Bq, L, ws),
+        "scan fwd: bf16 u, f16 z": lambda: scan_f(xzb[:, :D], draw, xzh[:, D:]),
+        "scan fwd: bf16 u, bf16 delta_raw": lambda: scan_f(xzb[:, :D], z(M, D, dt=bf), xzb[:, D:]),
+        "scan bwd: f16 u, fp32 dz": lambda: scan_b(xzh[:, :D], xzh[:, D:], dyh, du, dxz32[:, D:]),
+        "scan bwd: fp32 u, bf16 du": lambda: scan_b(xz32[:, :D], xz32[:, D:], dy32, z(M, D, dt=bf), dxz32[:, D:]),
+    }
+    for what, call in mixed.items():
+        del calls[:]
+        with pytest.raises(AssertionError):
+            call()
+        assert not calls, (what, calls)

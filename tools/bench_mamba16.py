@@ -48,15 +48,13 @@ def _figures(torch, ops, m, dt, d_model):
     u2, y, dout2 = f(M, d_model, t=dt), f(M, D, t=dt), f(M, d_model, t=dt)
     w_in, w_out = m.in_proj.weight.data, m.out_proj.weight.data
     g_in, g_out = torch.empty_like(w_in), torch.empty_like(w_out)
+    conv_f, conv_b, scan_f, scan_b = (ops.causal_conv1d_silu_fwd, ops.causal_conv1d_silu_bwd, ops.selective_scan_fwd,
+                                      ops.selective_scan_bwd)   # they pick the entry point by operand dtype
     if dt == F32:
-        conv_f, conv_b, scan_f, scan_b = (ops.causal_conv1d_silu_fwd, ops.causal_conv1d_silu_bwd, ops.selective_scan_fwd,
-                                          ops.selective_scan_bwd)
         p_in, p_out = w_in.data_ptr(), w_out.data_ptr()
         lin_f, lin_d, lin_w = ops.linear_fwd, ops.linear_dgrad, ops.linear_wgrad
         w16 = alive = None
     else:
-        conv_f, conv_b, scan_f, scan_b = (ops.h16_causal_conv1d_silu_fwd, ops.h16_causal_conv1d_silu_bwd,
-                                          ops.h16_selective_scan_fwd, ops.h16_selective_scan_bwd)
         w16, alive = weight_copies16(m, m._params(), dt)
         p_in, _, p_out = w16
         lin_f, lin_d, lin_w = ops.bf16_linear_fwd, ops.bf16_linear_dgrad, ops.bf16_linear_wgrad
