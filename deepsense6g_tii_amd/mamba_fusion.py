@@ -1,5 +1,5 @@
 """The bi-branch Mamba fusion stage of the reference (mambafuser_seq.py:74-231) on the gfx950 kernels: MambaBlock and
-MambaFusion, drop-in fp32 nn.Modules whose state dicts are interchangeable with the reference's.
+MambaFusion, drop-in nn.Modules (fp32 parameters) whose state dicts are interchangeable with the reference's.
 
     MambaBlock      x1  = fc1(ln1(x))                    ln1 = LayerNorm((T, C)): one mean / variance per SAMPLE
                     fm  = forward_mamba(x1)
@@ -31,10 +31,36 @@ dt_rank**-0.5 scale - LayerNorm is (1, 0) and pos_emb zeros; A_log, D and conv1d
 That is not what mamba_ssm intends for dt_proj (its _no_reinit mark is not honoured by the reference's hook), and it is what
 the reference trains.
 
-Supported: fp32, HIP device only, n_embd in {64, 128, 256, 512}, d_state 16, d_conv 4, 8 x 8 anchors, config.n_views == 1 (the
-reference's cat of the three modalities only lines up then), ln_size == (T, n_embd).  Train and eval; dropout is off in eval;
-no tape is kept when no gradient is needed.  Not covered: 16-bit storage, the frozen inference engine,
-missing-modality options (TimeMamba is time_mamba.py, the model mamba_fuser.py).
+Storage: the dtype of a block's input (fp32, bf16 or f16), or of the stage's maps, is the type the wide activations are stored
+in.  block_forward / block_backward and stage_forward / stage_backward state the launch sequence once; the
+sample LayerNorm, gate and pool-swap wrappers pick their entry point by operand dtype, and the storage decides only which
+linear triple runs (ops.linear_* / ops.bf16_linear_*), where the fc1 / fc2 weights come from (the masters / 16-bit copies:
+block_weight_copies16, or the caller's w16=), the dtype of dx1 and one extra cast (block: dx1 to 16-bit; stage: the ln_f input
+to fp32).  On 16-bit storage:
+
+    tensor                                                        storage
+    block input x, xl = ln1 output, x1, fm, bm, f2, block output  16-bit
+    dout, dfm, dbm, df2, dxl, block dx                            16-bit
+    dx1 (fc2's data gradient + the two layers' input gradients)   fp32 while it accumulates (bf16_linear_dgrad(out16=False),
+                                                                  then du_out=), then ONE 16-bit copy (ops.cast_bf16) that
+                                                                  fc1's weight and data gradients read
+    ln1 mean / rstd, its double partials, every parameter and     fp32 / double as on fp32 storage
+    parameter gradient, gdst= destinations
+    fc1 / fc2 weights                                             16-bit copies, forward and data gradient; biases fp32
+    stage: the three NHWC maps in and out, their gradients        the walk's storage (16-bit)
+    stage: tokens out of the pack, the gradient into its backward 16-bit
+    stage: gemb, dgemb, pos_emb, dpos_emb                         fp32
+    stage: ln_f input (widened once: ops.cast_f32), xo (the       fp32; ln_f's backward is ops.layernorm_bwd_bf16, whose second
+    returned tokens), dxo                                         output is the 16-bit dx the last block reads
+The two Mamba layers inside a block follow mamba.py's map.  Without a caller's w16= the stage casts every block's weights once
+in the forward and carries the copies on its tape; a MambaBlock module casts on every call, as Mamba does.
+
+Supported: fp32 / bf16 / f16 activations for MambaBlock and the walk-form stage, fp32 only for the MambaFusion module (its NCHW
+pack / unpack kernels are fp32); HIP device only, n_embd in {64, 128, 256, 512}, d_state 16, d_conv 4, 8 x 8 anchors,
+config.n_views == 1 (the reference's cat of the three modalities only lines up then), ln_size == (T, n_embd).  Train and eval;
+dropout is off in eval; no tape is kept when no gradient is needed.  Not covered: 16-bit storage of the MambaFusion module
+form, of the head (TimeMamba, time_mamba.py) and of the model (MambaFuser, mamba_fuser.py, which refuses compute modes other
+than "f32"), the frozen inference engine, missing-modality options.
 """
 from __future__ import annotations
 
@@ -42,7 +68,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .mamba import Mamba, _check_params, deliver_pair, grad_slots, layer_forward, layer_backward, stream_workspace
+from .mamba import (Mamba, _check_params, deliver_pair, grad_slots, layer_forward, layer_backward, stream_workspace,
+                    weight_copies16)
 
 F32 = torch.float32
 
@@ -51,46 +78,78 @@ def _empty(dev, *shape):
     return torch.empty(shape, dtype=F32, device=dev)
 
 
-def block_forward(blk, ws, save, x2, B, T, params):
+def block_weight_copies16(blk, params, dtype):
+    """-> the `w16` of block_forward / block_backward: (device pointer of the 16-bit fc1.weight copy, of the fc2.weight copy,
+    the forward Mamba's weight_copies16 pointers, the reverse Mamba's), cast from the fp32 masters now; the tensors ride along
+    so the pointers stay valid"""
+    c1, c2 = ops.cast_bf16(params[2], dtype=dtype), ops.cast_bf16(params[4], dtype=dtype)
+    pf, tf = weight_copies16(blk.forward_mamba, params[6:15], dtype)
+    pb, tb = weight_copies16(blk.backward_mamba, params[15:24], dtype)
+    return (c1.data_ptr(), c2.data_ptr(), pf, pb), (c1, c2, *tf, *tb)
+
+
+def block_forward(blk, ws, save, x2, B, T, params, w16=None):
     """one MambaBlock on x2 [B, T * C] (contiguous) -> (out [B * T, C], tape or None).  `params`: the 24 parameters in
     MambaBlock._params() order; `ws`: a Workspace of at least blk.workspace_bytes(B, T).  The body of _BlockFn, and what a
-    model walk calls without autograd."""
+    model walk calls without autograd.
+    x2's dtype is the storage type (the map of the module docstring), and `out`'s.  w16 (16-bit storage only): the pointers
+    block_weight_copies16 returns, for a caller that keeps 16-bit weight copies of its own; None casts the weights here, on
+    every call."""
     ln_w, ln_b, w1, b1, w2, b2 = params[:6]
     mp = params[6:]
     C = blk.n_embd
     M = B * T
+    if x2.dtype == F32:
+        linear, (p1, p2, w16_f, w16_b) = ops.linear_fwd, (w1.data_ptr(), w2.data_ptr(), None, None)
+    else:
+        if w16 is None:
+            w16, _alive = block_weight_copies16(blk, params, x2.dtype)   # _alive: until the launches below are queued
+        linear, (p1, p2, w16_f, w16_b) = ops.bf16_linear_fwd, w16
     xl, mean, rstd = ops.sample_layernorm_fwd(x2, ln_w, ln_b, ws)
-    x1 = ops.linear_fwd(xl.view(M, C), w1.data_ptr(), b1.data_ptr(), C)
-    fm, tape_f = layer_forward(blk.forward_mamba, ws, False, save, x1, B, T, mp[:9])
-    bm, tape_b = layer_forward(blk.backward_mamba, ws, True, save, x1, B, T, mp[9:])
-    f2 = ops.linear_fwd(x1, w2.data_ptr(), b2.data_ptr(), C)
+    x1 = linear(xl.view(M, C), p1, b1.data_ptr(), C)
+    fm, tape_f = layer_forward(blk.forward_mamba, ws, False, save, x1, B, T, mp[:9], w16=w16_f)
+    bm, tape_b = layer_forward(blk.backward_mamba, ws, True, save, x1, B, T, mp[9:], w16=w16_b)
+    f2 = linear(x1, p2, b2.data_ptr(), C)
     out = ops.bimamba_gate_fwd(fm, bm, f2, B, T)
     return out, ((x2, mean, rstd, xl, fm, bm, f2, *tape_f, *tape_b) if save else None)
 
 
-def block_backward(blk, ws, tape, dout2, B, T, params, gdst=None):
+def block_backward(blk, ws, tape, dout2, B, T, params, gdst=None, w16=None):
     """dout2 [B * T, C] (contiguous) -> (dx [B, T * C], the 24 parameter gradients in MambaBlock._params() order).  gdst: 24
     (device pointer, accumulate flag) pairs in that order - the gradients are written there in place and None is returned in
-    their stead (mamba.layer_backward's convention)."""
+    their stead (mamba.layer_backward's convention).
+    dout2's dtype is the storage type, the one of the forward that made the tape, and dx's; the parameter gradients and gdst
+    are fp32; w16 as in block_forward."""
     x2, mean, rstd, xl, fm, bm, f2 = tape[:7]
     tape_f, tape_b = tape[7:15], tape[15:23]
     ln_w, w1, w2, mp = params[0], params[2], params[4], params[6:]
     C = blk.n_embd
-    M, dev = B * T, dout2.device
+    M, dev, st = B * T, dout2.device, dout2.dtype
+    h16 = st != F32
+    if not h16:
+        wgrad, dgrad, dx1_kw = ops.linear_wgrad, ops.linear_dgrad, {}
+        p1, p2, w16_f, w16_b = w1.data_ptr(), w2.data_ptr(), None, None
+    else:
+        if w16 is None:
+            w16, _alive = block_weight_copies16(blk, params, st)   # _alive: until the launches below are queued
+        wgrad, dgrad, dx1_kw = ops.bf16_linear_wgrad, ops.bf16_linear_dgrad, dict(out16=False)
+        p1, p2, w16_f, w16_b = w16
     shapes = ((T, C), (T, C), (C, C), (C,), (C, C), (C,))
     (s_lw, s_lb, s_w1, s_b1, s_w2, s_b2), own = grad_slots(shapes, dev, None if gdst is None else gdst[:6])
     x1 = tape_f[0]
     dfm, dbm, df2 = ops.bimamba_gate_bwd(dout2, fm, bm, f2, B, T)
-    deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(x1, df2, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_w2, s_b2,
+    deliver_pair(lambda pw, pb, acc: wgrad(x1, df2, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_w2, s_b2,
                  shapes[4], shapes[5], dev)
-    dx1 = ops.linear_dgrad(df2, w2.data_ptr(), C)               # the two Mamba layers add their input gradients to it
+    # dx1 is fp32 on every storage while fc2's data gradient and the two Mamba layers' input gradients are summed into it
+    dx1 = dgrad(df2, p2, C, **dx1_kw)
     _, g_f = layer_backward(blk.forward_mamba, ws, False, B, T, tape_f, mp[:9], dfm, du_out=dx1,
-                            gdst=None if gdst is None else gdst[6:15])
+                            gdst=None if gdst is None else gdst[6:15], w16=w16_f)
     _, g_b = layer_backward(blk.backward_mamba, ws, True, B, T, tape_b, mp[9:], dbm, du_out=dx1,
-                            gdst=None if gdst is None else gdst[15:24])
-    deliver_pair(lambda pw, pb, acc: ops.linear_wgrad(xl.view(M, C), dx1, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_w1,
+                            gdst=None if gdst is None else gdst[15:24], w16=w16_b)
+    dx1_st = ops.cast_bf16(dx1, dtype=st) if h16 else dx1       # 16-bit: ONE rounding of the sum, read by fc1's two GEMMs
+    deliver_pair(lambda pw, pb, acc: wgrad(xl.view(M, C), dx1_st, pw, ws, accumulate=bool(acc), dbias_ptr=pb), s_w1,
                  s_b1, shapes[2], shapes[3], dev)
-    dxl = ops.linear_dgrad(dx1, w1.data_ptr(), C)
+    dxl = dgrad(dx1_st, p1, C)
     dx = None
 
     def ln1_bwd(pw, pb, acc):
@@ -154,15 +213,17 @@ class MambaBlock(nn.Module):
     def _check(self, x):
         if not x.is_cuda:
             raise RuntimeError("deepsense6g_tii_amd.MambaBlock runs on MI355X HIP kernels only (no CPU path)")
-        if x.dim() != 3 or tuple(x.shape[1:]) != self.ln_size or x.dtype != F32 or x.shape[0] < 1:
-            raise ValueError(f"MambaBlock: expected a (B, {self.ln_size[0]}, {self.ln_size[1]}) fp32 tensor, got "
+        if x.dim() != 3 or tuple(x.shape[1:]) != self.ln_size or x.dtype not in (F32, ops.BF16, ops.F16) or x.shape[0] < 1:
+            raise ValueError(f"MambaBlock: expected a (B, {self.ln_size[0]}, {self.ln_size[1]}) fp32, bf16 or f16 tensor, got "
                              f"{tuple(x.shape)} {x.dtype}")
         params = self._params()
         _check_params("MambaBlock", params, x.device)
         return params
 
     def forward(self, x):
-        """x: (B, T, n_embd) fp32 on the HIP device, (T, n_embd) == ln_size -> (B, T, n_embd)"""
+        """x: (B, T, n_embd) fp32, bf16 or f16 on the HIP device, (T, n_embd) == ln_size -> (B, T, n_embd) of the same dtype.
+        A 16-bit input runs the 16-bit-storage path (module docstring): its gradient is 16-bit, the parameters and their
+        gradients fp32, the weight copies are cast on every call"""
         params = self._check(x)
         save = torch.is_grad_enabled() and self.training and (x.requires_grad or any(p.requires_grad for p in params))
         with torch.cuda.device(x.device):
@@ -321,35 +382,50 @@ def _stage_ws(fus, ws, B):
         raise ValueError(f"Mamba stage: the workspace has {ws.nbytes} bytes, B = {B} needs {need}")
 
 
-def stage_forward(fus, ws, save, feats, gemb, outs, B, drop=(0.0, 0, 0), w=None):
+def stage_forward(fus, ws, save, feats, gemb, outs, B, drop=(0.0, 0, 0), w=None, w16=None):
     """feats: the three NHWC maps [B * S, H, H, C]; gemb [B, 2, C]: the embedded gps rows; outs: three maps like feats that
     receive feats[m] + the bilinear upsampling of modality m's output tokens; drop = (p, seed, seed_off) of the embedding
     dropout; w(p): device pointer of parameter p (default: where p.data lives).  -> (tokens after ln_f [B * T, C], tape or
-    None)"""
+    None).
+    feats[0].dtype is the storage type (fp32, bf16 or f16) of the maps, the tokens and the blocks; gemb, the pos_emb add and
+    the returned tokens are fp32 on every storage.  w16 (16-bit storage): one block_weight_copies16 pointer tuple per block,
+    for a caller that keeps the copies; None casts every block's weights once here and carries the copies on the tape, so the
+    backward does not cast again."""
     _stage_ws(fus, ws, B)
     w = w or (lambda p: p.data_ptr())
     S, C, T = fus.seq_len, fus.n_embd, fus.n_tokens
-    x = torch.empty((B, T, C), dtype=F32, device=gemb.device)
+    st = feats[0].dtype
+    h16 = st != F32
+    x = torch.empty((B, T, C), dtype=st, device=gemb.device)
     ops.pool_swap_tokens_fwd(feats, gemb, w(fus.pos_emb), x, S, *drop)
     x = x.view(B, T * C)
+    alive = None
+    if h16 and w16 is None:
+        made = [block_weight_copies16(blk, blk._params(), st) for blk in fus.mambablocks]
+        w16, alive = [m[0] for m in made], [m[1] for m in made]
     tapes = []
-    for blk in fus.mambablocks:
-        x, tp = block_forward(blk, ws, save, x.view(B, T * C), B, T, blk._params())
+    for i, blk in enumerate(fus.mambablocks):
+        x, tp = block_forward(blk, ws, save, x.view(B, T * C), B, T, blk._params(), w16=w16[i] if h16 else None)
         tapes.append(tp)
     x = x.view(B * T, C)
+    if h16:
+        x = ops.cast_f32(x)                                        # ln_f reads the last block's output widened once
     xo, mf, rf = ops.layernorm_fwd(x, w(fus.ln_f.weight), w(fus.ln_f.bias), fus.ln_f.eps)
     ops.upsample_add_fwd3(feats, xo, outs, (S, S, S), (0, S * 64, 2 * S * 64), T)
-    return xo, ((tapes, x, mf, rf, drop) if save else None)
+    return xo, ((tapes, x, mf, rf, drop, (st, w16, alive)) if save else None)
 
 
 def stage_backward(fus, ws, tape, dfeats_out, dgps_tok, dfeats, dgemb, B, g, w=None):
     """dfeats_out: gradients of the three output maps; dgps_tok = (tensor, bcast): gradient of the two gps rows of the
     stage's output tokens, [B, 2, C] or (bcast) one [B, C] row for both; g(p) -> (device pointer, accumulate flag) of
     parameter p's gradient.  Writes dfeats (three maps: dfeats_out[m] + the pooled-token gradient; may be dfeats_out
-    themselves) and dgemb [B, 2, C]; every parameter gradient of the stage goes to its g(p)."""
+    themselves) and dgemb [B, 2, C]; every parameter gradient of the stage goes to its g(p).
+    The storage type is the forward's (dfeats_out and dfeats have it; dgps_tok, dgemb and every parameter gradient are fp32);
+    the 16-bit weight copies are the ones the forward used."""
     _stage_ws(fus, ws, B)
     w = w or (lambda p: p.data_ptr())
-    tapes, x_last, mf, rf, drop = tape
+    tapes, x_last, mf, rf, drop, (st, w16, _alive) = tape
+    h16 = st != F32
     S, C, T = fus.seq_len, fus.n_embd, fus.n_tokens
     dxo = torch.empty((B * T, C), dtype=F32, device=dgemb.device)
     ops.upsample_add_bwd3(dfeats_out, dxo, (S, S, S), (0, S * 64, 2 * S * 64), T)
@@ -357,8 +433,14 @@ def stage_backward(fus, ws, tape, dfeats_out, dgps_tok, dfeats, dgemb, B, g, w=N
     ops.lib().gps_rows(gsrc.data_ptr(), dxo.data_ptr(), B, C, T, 1, 0, int(bcast), ops._stream())
     (gfw, af), (gfb, ab) = g(fus.ln_f.weight), g(fus.ln_f.bias)
     assert af == ab, "ln_f.weight and ln_f.bias gradients must share one accumulate flag"
-    dx = ops.layernorm_bwd(dxo, x_last, mf, rf, w(fus.ln_f.weight), gfw, gfb, ws, accumulate=bool(af))
-    for blk, tp in zip(reversed(list(fus.mambablocks)), reversed(tapes)):
-        dx, _ = block_backward(blk, ws, tp, dx.view(B * T, C), B, T, blk._params(), gdst=[g(p) for p in blk._params()])
+    if h16:     # the row kernel's second output is the 16-bit copy of dx the last block reads
+        _, dx = ops.layernorm_bwd_bf16(dxo, x_last, mf, rf, w(fus.ln_f.weight), gfw, gfb, ws, accumulate=bool(af), dtype=st)
+    else:
+        dx = ops.layernorm_bwd(dxo, x_last, mf, rf, w(fus.ln_f.weight), gfw, gfb, ws, accumulate=bool(af))
+    blocks = list(fus.mambablocks)
+    for i in reversed(range(len(blocks))):
+        blk = blocks[i]
+        dx, _ = block_backward(blk, ws, tapes[i], dx.view(B * T, C), B, T, blk._params(), gdst=[g(p) for p in blk._params()],
+                               w16=w16[i] if h16 else None)
     gpos, apos = g(fus.pos_emb)
     ops.pool_swap_tokens_bwd(dx.view(B, T, C), dfeats_out, dfeats, dgemb, gpos, apos, S, *drop)

@@ -1073,54 +1073,72 @@ def sample_layernorm_workspace_bytes(B, n):
     return int(lib().sample_layernorm_workspace_bytes(B, n))
 
 
+def _chk_st(t, st, *shape):
+    """a contiguous device tensor of the storage dtype `st` (fp32, bf16 or f16), of `shape` when given"""
+    assert st == F32 or st in _ST16, st
+    assert t.dtype == st and t.is_cuda and t.is_contiguous(), (t.dtype, st, t.device, t.stride())
+    if shape:
+        assert tuple(t.shape) == tuple(shape), (tuple(t.shape), shape)
+
+
+# The sample LayerNorm, the gate and the pool-swap pack run on fp32, bf16 or f16 storage, named by the dtype of their first wide
+# operand; every other operand is checked against the stage's storage map (mamba_fusion.py): the wide operands share that
+# dtype, parameters, statistics and parameter gradients are fp32.  A 16-bit piece is 8 elements: n % 8, C % 8.
 def sample_layernorm_fwd(x, gamma, beta, ws: Workspace, eps=1e-5):
-    """LayerNorm over ALL n values of each sample: x [B, n], gamma / beta n elements -> (y, mean [B], rstd [B])"""
+    """LayerNorm over ALL n values of each sample: x [B, n] (fp32 / bf16 / f16), gamma / beta n fp32 elements -> (y of x's
+    dtype, fp32 mean [B], rstd [B])"""
     B, n = x.shape
-    _chk(x)
-    assert n % 4 == 0 and ws.nbytes >= sample_layernorm_workspace_bytes(B, n), (B, n, ws.nbytes)
+    st = x.dtype
+    _chk_st(x, st)
+    assert n % (16 // x.element_size()) == 0 and ws.nbytes >= sample_layernorm_workspace_bytes(B, n), (B, n, ws.nbytes)
     y = torch.empty_like(x)
     mean = torch.empty(B, dtype=F32, device=x.device)
     rstd = torch.empty(B, dtype=F32, device=x.device)
-    lib().sample_layernorm_fwd(_p(x), _vec(gamma, n), _vec(beta, n), _p(y), _p(mean), _p(rstd), B, n, eps, ws.ptr, ws.nbytes,
-                               _stream())
+    _launch(lib().sample_layernorm_fwd, lib().h16_sample_layernorm_fwd, st, _p(x), _vec(gamma, n), _vec(beta, n), _p(y),
+            _p(mean), _p(rstd), B, n, eps, ws.ptr, ws.nbytes)
     return y, mean, rstd
 
 
 def sample_layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, ws: Workspace, accumulate=False):
-    """-> dx [B, n]; dgamma / dbeta (n elements each, the caller's tensors or device pointers) are written, or added to when
-    accumulate"""
+    """-> dx [B, n] of dy's dtype (x has it too); dgamma / dbeta (n fp32 elements each, the caller's tensors or device
+    pointers) are written, or added to when accumulate"""
     B, n = x.shape
-    _chk(x)
-    _chk(dy, B, n)
+    st = dy.dtype
+    _chk_st(dy, st, B, n)
+    _chk_st(x, st)
     _chk(mean, B)
     _chk(rstd, B)
-    assert n % 4 == 0 and ws.nbytes >= sample_layernorm_workspace_bytes(B, n), (B, n, ws.nbytes)
+    assert n % (16 // x.element_size()) == 0 and ws.nbytes >= sample_layernorm_workspace_bytes(B, n), (B, n, ws.nbytes)
     dx = torch.empty_like(x)
-    lib().sample_layernorm_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _vec(gamma, n), _p(dx), _dst(dgamma, n), _dst(dbeta, n), B, n,
-                               int(accumulate), ws.ptr, ws.nbytes, _stream())
+    _launch(lib().sample_layernorm_bwd, lib().h16_sample_layernorm_bwd, st, _p(dy), _p(x), _p(mean), _p(rstd), _vec(gamma, n),
+            _p(dx), _dst(dgamma, n), _dst(dbeta, n), B, n, int(accumulate), ws.ptr, ws.nbytes)
     return dx
 
 
 def bimamba_gate_fwd(fm, bm, f2, B, L, out=None):
-    """out[b, t] = bm[b, L-1-t] * (leaky_relu_0.2(f2[b, L-1-t]) + fm[b, t]); operands [B*L, C], column blocks allowed"""
+    """out[b, t] = bm[b, L-1-t] * (leaky_relu_0.2(f2[b, L-1-t]) + fm[b, t]); operands [B*L, C] of fm's dtype, column blocks
+    allowed"""
     M, C = fm.shape
+    st = fm.dtype
     assert M == B * L and C % 4 == 0
-    o = out if out is not None else torch.empty((M, C), dtype=F32, device=fm.device)
-    lib().bimamba_gate_fwd(_p(fm), _rows_al(fm, M, C), _p(bm), _rows_al(bm, M, C), _p(f2), _rows_al(f2, M, C), _p(o),
-                           _rows_al(o, M, C), B, L, C, _stream())
+    o = out if out is not None else torch.empty((M, C), dtype=st, device=fm.device)
+    _launch(lib().bimamba_gate_fwd, lib().h16_bimamba_gate_fwd, st, _p(fm), _rows_al(fm, M, C, st), _p(bm),
+            _rows_al(bm, M, C, st), _p(f2), _rows_al(f2, M, C, st), _p(o), _rows_al(o, M, C, st), B, L, C)
     return o
 
 
 def bimamba_gate_bwd(dout, fm, bm, f2, B, L, out=None):
-    """-> (dfm, dbm, df2), each in its producer's token order; `out`: three [B*L, C] destinations (column blocks allowed)"""
+    """-> (dfm, dbm, df2), each in its producer's token order and of dout's dtype (as are fm, bm, f2); `out`: three
+    [B*L, C] destinations (column blocks allowed)"""
     M, C = fm.shape
+    st = dout.dtype
     assert M == B * L and C % 4 == 0
     if out is None:
-        out = tuple(torch.empty((M, C), dtype=F32, device=fm.device) for _ in range(3))
+        out = tuple(torch.empty((M, C), dtype=st, device=fm.device) for _ in range(3))
     dfm, dbm, df2 = out
-    lib().bimamba_gate_bwd(_p(dout), _rows_al(dout, M, C), _p(fm), _rows_al(fm, M, C), _p(bm), _rows_al(bm, M, C), _p(f2),
-                           _rows_al(f2, M, C), _p(dfm), _rows_al(dfm, M, C), _p(dbm), _rows_al(dbm, M, C), _p(df2),
-                           _rows_al(df2, M, C), B, L, C, _stream())
+    _launch(lib().bimamba_gate_bwd, lib().h16_bimamba_gate_bwd, st, _p(dout), _rows_al(dout, M, C, st), _p(fm),
+            _rows_al(fm, M, C, st), _p(bm), _rows_al(bm, M, C, st), _p(f2), _rows_al(f2, M, C, st), _p(dfm),
+            _rows_al(dfm, M, C, st), _p(dbm), _rows_al(dbm, M, C, st), _p(df2), _rows_al(df2, M, C, st), B, L, C)
     return dfm, dbm, df2
 
 
@@ -1157,17 +1175,19 @@ def swap_pack_bwd(dtokens, B, S, drop_p=0.0, seed=0, seed_off=0):
     return (*dmaps, dgps, dpos)
 
 
-def _pool_swap_descs(ins, outs, S, C):
-    """descriptor array of the pool-swap pack: three fp32 NHWC maps [B * S, H, H, C] (ins[m] may be None) -> (descs, B, H)"""
+def _pool_swap_descs(ins, outs, S, C, st=F32):
+    """descriptor array of the pool-swap pack: three NHWC maps [B * S, H, H, C] of the storage dtype `st` (ins[m] may be
+    None) -> (descs, B, H)"""
     ref = outs[0] if outs is not None else ins[0]
     N, H, _, _ = ref.shape
     assert len(ins) == 3 and (outs is None or len(outs) == 3) and S >= 1 and N % S == 0, (len(ins), N, S)
-    assert H % 8 == 0 and 8 <= H <= 64 and C % 4 == 0 and 4 <= C <= 512, (H, C)
+    piece = 4 if st == F32 else 8
+    assert H % 8 == 0 and 8 <= H <= 64 and C % piece == 0 and piece <= C <= 512, (H, C)
     descs = (_MapDesc * 3)()
     for m in range(3):
         for t in (ins[m], outs[m] if outs is not None else None):
             if t is not None:
-                _chk(t, N, H, H, C)
+                _chk_st(t, st, N, H, H, C)
                 assert t.data_ptr() % 16 == 0
         descs[m].inp, descs[m].out = _p(ins[m]), _p(outs[m]) if outs is not None else 0
         descs[m].frames_per_sample, descs[m].mod_off = S, m * S * 64
@@ -1177,25 +1197,28 @@ def _pool_swap_descs(ins, outs, S, C):
 def pool_swap_tokens_fwd(feats, gemb, pos_emb_ptr, tokens, S, drop_p=0.0, seed=0, seed_off=0):
     """the Mamba stage's token pack on the walk's layout: tokens [B, T, C] (T = 192 S + 2) = embd_drop(pos_emb + the 8 x 8
     average pool of the three NHWC maps feats[m] [B * S, H, H, C] with swap_pack_fwd's channel swap; the two gps rows from
-    gemb [B, 2, C]), one launch"""
+    gemb [B, 2, C]), one launch.  The maps' dtype (fp32 / bf16 / f16) is the tokens'; gemb and pos_emb are fp32"""
     C = feats[0].shape[3]
-    descs, B, H = _pool_swap_descs(feats, None, S, C)
+    st = feats[0].dtype
+    descs, B, H = _pool_swap_descs(feats, None, S, C, st)
     _chk(gemb, B, 2, C)
-    _chk(tokens, B, 192 * S + 2, C)
-    lib().pool_swap_tokens_fwd(ctypes.addressof(descs), _p(gemb), pos_emb_ptr, _p(tokens), B, S, H, C, float(drop_p), seed,
-                               seed_off, _stream())
+    _chk_st(tokens, st, B, 192 * S + 2, C)
+    _launch(lib().pool_swap_tokens_fwd, lib().h16_pool_swap_tokens_fwd, st, ctypes.addressof(descs), _p(gemb), pos_emb_ptr,
+            _p(tokens), B, S, H, C, float(drop_p), seed, seed_off)
 
 
 def pool_swap_tokens_bwd(dtokens, dfeats_in, dfeats, dgemb, dpos_ptr, accumulate, S, drop_p=0.0, seed=0, seed_off=0):
     """backward of pool_swap_tokens_fwd from dtokens [B, T, C], the mask regenerated: dfeats[q] = dfeats_in[q] (None: zero;
     may be dfeats[q] itself) + the token gradient spread back over its windows through the inverse swap; dgemb [B, 2, C]
-    written; the (T, C) gradient of pos_emb at dpos_ptr written, or added to when `accumulate`"""
+    written; the (T, C) gradient of pos_emb at dpos_ptr written, or added to when `accumulate`.  dtokens' dtype is the maps';
+    dgemb and the pos_emb gradient are fp32"""
     C = dfeats[0].shape[3]
-    descs, B, H = _pool_swap_descs(dfeats_in if dfeats_in is not None else (None,) * 3, dfeats, S, C)
-    _chk(dtokens, B, 192 * S + 2, C)
+    st = dtokens.dtype
+    descs, B, H = _pool_swap_descs(dfeats_in if dfeats_in is not None else (None,) * 3, dfeats, S, C, st)
+    _chk_st(dtokens, st, B, 192 * S + 2, C)
     _chk(dgemb, B, 2, C)
-    lib().pool_swap_tokens_bwd(ctypes.addressof(descs), _p(dtokens), _p(dgemb), dpos_ptr, int(bool(accumulate)), B, S, H, C,
-                               float(drop_p), seed, seed_off, _stream())
+    _launch(lib().pool_swap_tokens_bwd, lib().h16_pool_swap_tokens_bwd, st, ctypes.addressof(descs), _p(dtokens), _p(dgemb),
+            dpos_ptr, int(bool(accumulate)), B, S, H, C, float(drop_p), seed, seed_off)
 
 
 def token_unpack_fwd(tokens, B, S):

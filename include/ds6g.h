@@ -514,6 +514,32 @@ int ds6g_pool_swap_tokens_fwd(const ds6g_map_desc* maps, const float* gemb, cons
 int ds6g_pool_swap_tokens_bwd(const ds6g_map_desc* maps, const float* dtokens, float* dgemb, float* dpos_emb,
                               int accumulate_dpos, int B, int S, int H, int C, float drop_p, uint64_t seed,
                               uint64_t seed_off, void* stream);
+/* The sample LayerNorm, the gate and the pool-swap pack on 16-bit storage (st16: DS6G_ST_BF16 / DS6G_ST_F16) - the same
+ * kernels instantiated on the storage type, the same chunking, fixed-order partials and workspace query, fp32 arithmetic with
+ * ONE rounding per stored element, no atomics.  What is 16-bit follows the stage's storage map
+ * (deepsense6g_tii_amd/mamba_fusion.py):
+ *   sample_layernorm   16-bit: x, y, dy, dx                 fp32: gamma, beta, dgamma, dbeta, mean, rstd (statistics of the
+ *                      widened values), the double partials of the workspace
+ *   bimamba_gate       16-bit: all seven streams (fm, bm, f2, out; dout, dfm, dbm, df2); the LeakyReLU slope from the stored f2
+ *   pool_swap_tokens   16-bit: the maps (in and out), tokens, dtokens       fp32: gemb, pos_emb, dgemb, dpos_emb
+ * A thread moves 16 bytes = 8 elements of a 16-bit operand: n % 8 == 0, C % 8 == 0, row strides (in ELEMENTS of the operand's
+ * own type) % 8 for a 16-bit operand; every pointer 16-byte aligned.  Refusals (DS6G_ERR_ARG / DS6G_ERR_WORKSPACE) come before
+ * any launch. */
+int ds6g_h16_sample_layernorm_fwd(int st16, const void* x, const float* gamma, const float* beta, void* y, float* mean,
+                                  float* rstd, int B, long n, float eps, void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_sample_layernorm_bwd(int st16, const void* dy, const void* x, const float* mean, const float* rstd,
+                                  const float* gamma, void* dx, float* dgamma, float* dbeta, int B, long n,
+                                  int accumulate_param_grads, void* ws, size_t ws_bytes, void* stream);
+int ds6g_h16_bimamba_gate_fwd(int st16, const void* fm, int ld_fm, const void* bm, int ld_bm, const void* f2, int ld_f2,
+                              void* out, int ld_out, int B, int L, int C, void* stream);
+int ds6g_h16_bimamba_gate_bwd(int st16, const void* dout, int ld_dout, const void* fm, int ld_fm, const void* bm, int ld_bm,
+                              const void* f2, int ld_f2, void* dfm, int ld_dfm, void* dbm, int ld_dbm, void* df2, int ld_df2,
+                              int B, int L, int C, void* stream);
+int ds6g_h16_pool_swap_tokens_fwd(int st16, const ds6g_map_desc* maps, const float* gemb, const float* pos_emb, void* tokens,
+                                  int B, int S, int H, int C, float drop_p, uint64_t seed, uint64_t seed_off, void* stream);
+int ds6g_h16_pool_swap_tokens_bwd(int st16, const ds6g_map_desc* maps, const void* dtokens, float* dgemb, float* dpos_emb,
+                                  int accumulate_dpos, int B, int S, int H, int C, float drop_p, uint64_t seed,
+                                  uint64_t seed_off, void* stream);
 
 /* ---- time_mamba.hip : the temporal Mamba fusion head behind its shared Mamba layer, fp32 (mambafuser_seq.py:233-284) --
  * A sample has 17 rows of C = 512 floats: 3 modalities x S = 5 frames of the layer's output y, then its 2 gps rows.  y is
