@@ -10,7 +10,8 @@
 // linears and softmaxes are done by 4 lanes (one per softmax group) out of LDS.  No float atomics: every sum has a fixed
 // order, two runs are bit-identical.  The backward leaves the 36 parameter-gradient values of a sample in a [B][36] slab
 // (W5 25, b5 5, W2 4, b2 2) for ds6g_batch_sum, or for ds6g_temporal_param_grads, which delivers the sums to the four
-// parameters' own gradients.  Below them: the grouped head pool that feeds the head from a model walk (ds6g_pool_rows3_*).
+// parameters' own gradients.  Below them: the grouped head pool that feeds the head from a model walk (ds6g_pool_rows3_*), a
+// template on the storage type of the walk's maps (ds6g_h16_pool_rows3_* for bf16 / f16 maps); the head itself stays fp32.
 #include "common.h"
 
 namespace {
@@ -230,41 +231,89 @@ __global__ __launch_bounds__(64) void time_param_grads_kernel(const float* __res
 // ---- the grouped head pool: the frames of the three 8 x 8 modality maps <-> the head's modality-major rows --------------------
 // rows[m * N + n][c] = mean over the 64 positions of map m's frame n.  One launch for the three maps (blockIdx.z = m), a
 // thread per (frame, 4 channels): 64 coalesced 16-byte loads summed in position order - ds6g_global_pool's arithmetic.
+// Both kernels are templates on the storage type T of the MAPS (feat_m; dfeat_in_m and dfeat_m): float behind
+// ds6g_pool_rows3_*, __bf16 / _Float16 behind ds6g_h16_pool_rows3_* (the maps of a model walk on 16-bit storage).  rows and
+// drows - the temporal head's input and its gradient - and all arithmetic are fp32 for every T.  A thread moves one 16-byte
+// piece of a map: 4 floats, or 8 elements of a 16-bit type as two f32x4 halves.
+template <typename T>
 struct PoolRows3 {
-    const float* in[3];
-    float* out[3];
+    const T* in[3];
+    T* out[3];
 };
 
-__global__ __launch_bounds__(256) void pool_rows3_fwd_kernel(PoolRows3 g, float* __restrict__ rows, int N, int C) {
-    const int cg = C >> 2;
+template <typename T> struct PoolPiece {
+    static constexpr int SH = sizeof(T) == 4 ? 2 : 3;   // log2 of the elements per piece
+    static constexpr int N = 1 << SH, NV = N / 4;
+};
+__device__ __forceinline__ void ld_piece(const float* p, f32x4 (&v)[1]) { v[0] = ld4(p); }
+__device__ __forceinline__ void st_piece(float* p, const f32x4 (&v)[1]) { st4(p, v[0]); }
+template <typename H>
+__device__ __forceinline__ void ld_piece(const H* p, f32x4 (&v)[2]) {     // widening is exact
+    const typename H16<H>::x8 t = *reinterpret_cast<const typename H16<H>::x8*>(p);
+    v[0] = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+    v[1] = f32x4{(float)t[4], (float)t[5], (float)t[6], (float)t[7]};
+}
+template <typename H>
+__device__ __forceinline__ void st_piece(H* p, const f32x4 (&v)[2]) {     // round to nearest even, ONE rounding per element
+    typename H16<H>::x8 t;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { t[e] = (H)v[0][e]; t[4 + e] = (H)v[1][e]; }
+    *reinterpret_cast<typename H16<H>::x8*>(p) = t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pool_rows3_fwd_kernel(PoolRows3<T> g, float* __restrict__ rows, int N, int C) {
+    constexpr int PN = PoolPiece<T>::N, NV = PoolPiece<T>::NV;
+    const int cg = C >> PoolPiece<T>::SH;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)N * cg) return;
     const int m = blockIdx.z;
-    const float* __restrict__ feat = g.in[m];
-    const int c4 = (int)(i % cg) * 4;
+    const T* __restrict__ feat = g.in[m];
+    const int c4 = (int)(i % cg) * PN;
     const long n = i / cg;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < 64; ++p) s += ld4(feat + (n * 64 + p) * C + c4);
-    st4(rows + ((long)m * N + n) * C + c4, s * (1.0f / 64.0f));
+    f32x4 s[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int p = 0; p < 64; ++p) {
+        f32x4 v[NV];
+        ld_piece(feat + (n * 64 + p) * C + c4, v);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) s[j] += v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) st4(rows + ((long)m * N + n) * C + c4 + 4 * j, s[j] * (1.0f / 64.0f));
 }
 
 // out_m[n][p][c] = (in_m or 0) + drows[m * N + n][c] / 64: a thread per 16 bytes of a map, every element written exactly once
 // (in_m may be out_m: the thread that writes an element is the one that read it, so neither pointer is __restrict__)
-__global__ __launch_bounds__(256) void pool_rows3_bwd_kernel(PoolRows3 g, const float* __restrict__ drows, int N, int C) {
-    const int cg = C >> 2;
+template <typename T>
+__global__ __launch_bounds__(256) void pool_rows3_bwd_kernel(PoolRows3<T> g, const float* __restrict__ drows, int N, int C) {
+    constexpr int PN = PoolPiece<T>::N, NV = PoolPiece<T>::NV;
+    const int cg = C >> PoolPiece<T>::SH;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)N * 64 * cg) return;
     const int m = blockIdx.z;
-    const int c4 = (int)(i % cg) * 4;
+    const int c4 = (int)(i % cg) * PN;
     const long n = i / ((long)64 * cg);
-    f32x4 v = ld4(drows + ((long)m * N + n) * C + c4) * (1.0f / 64.0f);
-    const float* in = g.in[m];
-    if (in) v += ld4(in + i * 4);
-    st4(g.out[m] + i * 4, v);
+    f32x4 v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = ld4(drows + ((long)m * N + n) * C + c4 + 4 * j) * (1.0f / 64.0f);
+    const T* in = g.in[m];
+    if (in) {
+        f32x4 a[NV];
+        ld_piece(in + i * PN, a);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[j] += a[j];
+    }
+    st_piece(g.out[m] + i * PN, v);
 }
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool pool_rows3_dims_ok(int N, int C) { return N >= 1 && C >= 4 && C % 4 == 0 && (long)N * 64 * C <= (1L << 31); }
+template <typename T>
+inline bool pool_rows3_dims_ok(int N, int C) {
+    constexpr int PN = PoolPiece<T>::N;
+    return N >= 1 && C >= PN && C % PN == 0 && (long)N * 64 * C <= (1L << 31);
+}
 inline bool tm_dims_ok(int B, int S, int C) { return B >= 1 && B <= (1 << 20) && S == TM_S && C == TM_C; }
 inline bool tm_ld_ok(long ld) { return ld >= 2 * TM_C && ld % 4 == 0; }
 
@@ -312,28 +361,48 @@ int ds6g_temporal_param_grads(const float* dparam_part, int B, float* dw5, int a
     return DS6G_OK;
 }
 
-int ds6g_pool_rows3_fwd(const float* feat0, const float* feat1, const float* feat2, float* rows, int N, int C, void* stream) {
+// The head pool over the storage type T of the maps: float behind the fp32 entry points, __bf16 / _Float16 behind the
+// ds6g_h16_* ones.  Same checks and the same one launch for every T; a thread per 16-byte piece (C % 4, or C % 8 on 16-bit).
+extern "C++" template <typename T>
+static int pool_rows3_fwd(const void* feat0, const void* feat1, const void* feat2, float* rows, int N, int C, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(feat0 && feat1 && feat2 && rows && pool_rows3_dims_ok(N, C));
+    DS6G_CHECK_ARG(feat0 && feat1 && feat2 && rows && pool_rows3_dims_ok<T>(N, C));
     DS6G_CHECK_ARG(al16(feat0) && al16(feat1) && al16(feat2) && al16(rows));
-    const PoolRows3 g = {{feat0, feat1, feat2}, {nullptr, nullptr, nullptr}};
-    hipLaunchKernelGGL(pool_rows3_fwd_kernel, dim3(cdiv((long)N * (C / 4), 256), 1, 3), dim3(256), 0, (hipStream_t)stream, g,
-                       rows, N, C);
+    const PoolRows3<T> g = {{(const T*)feat0, (const T*)feat1, (const T*)feat2}, {nullptr, nullptr, nullptr}};
+    hipLaunchKernelGGL(pool_rows3_fwd_kernel<T>, dim3(cdiv((long)N * (C / PoolPiece<T>::N), 256), 1, 3), dim3(256), 0,
+                       (hipStream_t)stream, g, rows, N, C);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
 }
+int ds6g_pool_rows3_fwd(const float* feat0, const float* feat1, const float* feat2, float* rows, int N, int C, void* stream) {
+    return pool_rows3_fwd<float>(feat0, feat1, feat2, rows, N, C, stream);
+}
+int ds6g_h16_pool_rows3_fwd(int st16, const void* feat0, const void* feat1, const void* feat2, float* rows, int N, int C,
+                            void* stream) {
+    DS6G_RETURN_H16(st16, pool_rows3_fwd, feat0, feat1, feat2, rows, N, C, stream);
+}
 
-int ds6g_pool_rows3_bwd(const float* drows, const float* dfeat_in0, const float* dfeat_in1, const float* dfeat_in2,
-                        float* dfeat0, float* dfeat1, float* dfeat2, int N, int C, void* stream) {
+extern "C++" template <typename T>
+static int pool_rows3_bwd(const float* drows, const void* dfeat_in0, const void* dfeat_in1, const void* dfeat_in2,
+                          void* dfeat0, void* dfeat1, void* dfeat2, int N, int C, void* stream) {
     DS6G_ENTER();
-    DS6G_CHECK_ARG(drows && dfeat0 && dfeat1 && dfeat2 && pool_rows3_dims_ok(N, C));
+    DS6G_CHECK_ARG(drows && dfeat0 && dfeat1 && dfeat2 && pool_rows3_dims_ok<T>(N, C));
     DS6G_CHECK_ARG(al16(drows) && al16(dfeat_in0) && al16(dfeat_in1) && al16(dfeat_in2) && al16(dfeat0) && al16(dfeat1) &&
                    al16(dfeat2));
-    const PoolRows3 g = {{dfeat_in0, dfeat_in1, dfeat_in2}, {dfeat0, dfeat1, dfeat2}};
-    hipLaunchKernelGGL(pool_rows3_bwd_kernel, dim3(cdiv((long)N * 64 * (C / 4), 256), 1, 3), dim3(256), 0,
+    const PoolRows3<T> g = {{(const T*)dfeat_in0, (const T*)dfeat_in1, (const T*)dfeat_in2},
+                            {(T*)dfeat0, (T*)dfeat1, (T*)dfeat2}};
+    hipLaunchKernelGGL(pool_rows3_bwd_kernel<T>, dim3(cdiv((long)N * 64 * (C / PoolPiece<T>::N), 256), 1, 3), dim3(256), 0,
                        (hipStream_t)stream, g, drows, N, C);
     DS6G_LAUNCH_CHECK();
     return DS6G_OK;
+}
+int ds6g_pool_rows3_bwd(const float* drows, const float* dfeat_in0, const float* dfeat_in1, const float* dfeat_in2,
+                        float* dfeat0, float* dfeat1, float* dfeat2, int N, int C, void* stream) {
+    return pool_rows3_bwd<float>(drows, dfeat_in0, dfeat_in1, dfeat_in2, dfeat0, dfeat1, dfeat2, N, C, stream);
+}
+int ds6g_h16_pool_rows3_bwd(int st16, const float* drows, const void* dfeat_in0, const void* dfeat_in1, const void* dfeat_in2,
+                            void* dfeat0, void* dfeat1, void* dfeat2, int N, int C, void* stream) {
+    DS6G_RETURN_H16(st16, pool_rows3_bwd, drows, dfeat_in0, dfeat_in1, dfeat_in2, dfeat0, dfeat1, dfeat2, N, C, stream);
 }
 
 }  // extern "C"

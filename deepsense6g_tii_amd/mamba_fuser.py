@@ -11,11 +11,32 @@ gradient written straight into the gradient arena.  The head: with config.TFM th
 csrc/time_mamba.hip) and time_mamba_forward / time_mamba_backward(gdst=), the gps rows read from the last stage's tokens by sample
 stride; without it the parent's 17-token sum.  Parameter names and shapes equal the reference's state dict.
 
-Supported: fp32 with compute mode "f32", config.n_views == 1, 8 x 8 anchors, no missing-modality options, any seq_len >= 1
-without TFM, seq_len == 5 with it (the head hard-wires Linear(5, 5)).  Anything else raises at construction, or at the first
-forward for the compute mode.  Not covered: 16-bit storage, the frozen inference engine and hipGraph capture
-(freeze_inference, capture_inference and train.CapturedTrainStep raise NotImplementedError), missing-modality input replacement
-and feature injection, n_views > 1.
+Storage: the compute modes "f32", "bf16" and "f16", as for TransFuser - the parent's _refresh_shadow16 decides the walk's
+storage once per forward ("f16": train it under train.DynamicLossScaler).  On a 16-bit walk:
+
+    tensor                                                          storage
+    the trunks' maps, the stage's maps in and out, their gradients  16-bit (the parent's walk; mamba_fusion.py's stage map)
+    gemb, dgemb, xo (a stage's output tokens, cap["mamba{s}"]),     fp32
+    dgps_tok, vel_emb{s} and its gradients
+    the stage's fc1 / fc2 / in_proj / x_proj / out_proj weights     read in place in the walk's 16-bit shadow of the arena
+                                                                    (stage_forward(w16=)) where weight_route allows it; a copy
+                                                                    cast once per forward, kept on the stage record, for the rest
+                                                                    (stage 1's x_proj: 36 rows padded with zero rows to 40)
+    head with TFM: rows, drows, the whole temporal head              fp32: ops.pool_rows3_fwd reads the 16-bit maps into fp32
+                                                                    rows, time_mamba_forward / _backward are untouched,
+                                                                    ops.pool_rows3_bwd writes 16-bit map gradients (one rounding)
+    head without TFM, join, logits, loss, every parameter gradient  the parent's (fp32)
+The walk falls back to fp32 storage where the parent's does: eval() with folded BatchNorm, parameters re-pointed away from the
+arena (an applied EMA shadow); the stages then take fp32 maps and run as in mode "f32".  In mode "f32" the model makes the
+launches it made before 16-bit storage existed, bit for bit.
+
+Supported: compute modes "f32", "bf16", "f16"; config.n_views == 1, 8 x 8 anchors, no missing-modality options, any
+seq_len >= 1 without TFM, seq_len == 5 with it (the head hard-wires Linear(5, 5)).  Anything else raises at construction, or at
+the first forward for the compute mode ("f32x3" / "f32x6": the Mamba kernels have no split-bf16 form).  Not covered: TimeMamba
+on 16-bit storage (its tensors are [3 B 5, 512] fp32 rows, 0.3 ms of a 115 ms step, and the last arithmetic before the logits),
+the MambaFusion module form on 16-bit storage, the frozen inference engine and hipGraph capture (freeze_inference,
+capture_inference and train.CapturedTrainStep raise NotImplementedError in every mode), missing-modality input replacement and
+feature injection, n_views > 1.
 """
 from __future__ import annotations
 
@@ -24,13 +45,40 @@ from torch import nn
 
 from . import mamba_fusion, ops
 from ._lib import lib
+from .mamba import x_proj_rows16
 from .mamba_fusion import MambaFusion
 from .model import F32, STAGE_WIDTH, ImageCNN, LidarEncoder, TransFuser, _record
 from .time_mamba import FRAMES, TimeMamba, time_mamba_backward, time_mamba_forward
 
 # a Mamba fusion stage: C, T as the walk reads them; gps_src addresses the (B, 2, K) input of vel_emb{s}; tape = what
-# mamba_fusion.stage_backward takes; fshapes = the shapes of the three maps
-_MambaStageRec = _record("_MambaStageRec", "s C T gps_src tape fshapes")
+# mamba_fusion.stage_backward takes; fshapes = the shapes of the three maps; copies = the 16-bit weight copies the tape's
+# pointers address (None on fp32 storage), alive until the backward has run
+_MambaStageRec = _record("_MambaStageRec", "s C T gps_src tape fshapes copies")
+
+# ---- where a stage's 16-bit GEMM weights come from ---------------------------------------------------------------------------
+# The 16-bit GEMMs (csrc/bgemm.hip) read a weight [rows, cols] through a buffer descriptor in 16-byte pieces of one row: cols a
+# multiple of 64 where the weight is the K-contiguous operand, rows a multiple of 8, and a base address that only has to be
+# dword-aligned - the GPT stages and the trunk convolutions have always handed them shadow pointers that are 8-byte aligned
+# and no better (arena segments are padded to 4 elements, so a shadow offset is a multiple of 8 bytes).
+SHADOW_ALIGN = 8
+
+
+def block_weights16(blk):
+    """the eight weights of a MambaBlock that its 16-bit GEMMs read, in mamba_fusion.block_weight_copies16's order (fc1, fc2;
+    in_proj, x_proj, out_proj of the forward Mamba, then of the reverse one), each with the rows its 16-bit operand must
+    have: the weight's own, but mamba.x_proj_rows16 for x_proj (the added rows zero)"""
+    out = [(blk.fc1.weight, blk.fc1.weight.shape[0]), (blk.fc2.weight, blk.fc2.weight.shape[0])]
+    for mod in (blk.forward_mamba, blk.backward_mamba):
+        out += [(mod.in_proj.weight, mod.in_proj.weight.shape[0]), (mod.x_proj.weight, x_proj_rows16(mod.dt_rank)),
+                (mod.out_proj.weight, mod.out_proj.weight.shape[0])]
+    return out
+
+
+def weight_route(shadow_ptr, rows, rows16):
+    """Pure host rule: "shadow" - the 16-bit GEMMs read the weight in place in the walk's 16-bit shadow of the arena - where the
+    shadow holds exactly the operand they need (rows == rows16: nothing to pad) at an address they accept (SHADOW_ALIGN);
+    "copy" otherwise: a separate buffer of rows16 rows, cast once per forward"""
+    return "shadow" if rows == rows16 and int(shadow_ptr) % SHADOW_ALIGN == 0 else "copy"
 
 
 class EncoderWithMamba(nn.Module):  # mambafuser_seq.py:286-359
@@ -72,6 +120,8 @@ class MambaFuser(TransFuser):
             raise ValueError(f"MambaFuser: config.TFM needs seq_len == {FRAMES} (the temporal head hard-wires "
                              f"Linear({FRAMES}, {FRAMES})), got {config.seq_len}")
         super().__init__(config, device, pretrain_weight)
+        # stage -> (weights read from the 16-bit shadow, weights copied) of the last forward on 16-bit storage (weight_route)
+        self.w16_routes = {}
 
     def _make_encoder(self, config):
         return EncoderWithMamba(config)
@@ -108,8 +158,12 @@ class MambaFuser(TransFuser):
         return out
 
     def _new_walk(self, record):
-        if lib().get_compute_mode() != 0:
-            raise RuntimeError(f'MambaFuser runs in compute mode "f32" only, the library is in "{ops.get_compute_mode()}"')
+        """the parent's walk: in compute modes "bf16" / "f16" the parent's _refresh_shadow16 decides the storage (16-bit from
+        the arena's shadow; fp32 in eval() with folded BatchNorm or with re-pointed parameters, as for TransFuser).  The split
+        modes have no Mamba kernels"""
+        if lib().get_compute_mode() not in (0, 1, 5):
+            raise RuntimeError(f'MambaFuser runs in compute modes "f32", "bf16" and "f16" only, the library is in '
+                               f'"{ops.get_compute_mode()}"')
         return super()._new_walk(record)
 
     # ---------------------------------------------------------------- the stages ----------------
@@ -122,14 +176,39 @@ class MambaFuser(TransFuser):
             self._ws_main = ws = ops.Workspace(self.device, need)
         return ws
 
+    def _stage_w16(self, wk, fus, st):
+        """the `w16` of mamba_fusion.stage_forward on 16-bit storage `st`, without the stage's own casts: a pointer into the
+        walk's 16-bit shadow (refreshed once per forward) for every weight weight_route sends there, a copy cast now from the
+        fp32 master for the rest.  -> (one block_weight_copies16 pointer tuple per block, the copies - they have to outlive
+        the backward -, (weights read from the shadow, weights copied))"""
+        ptrs, copies, n_shadow = [], [], 0
+        for blk in fus.mambablocks:
+            p = []
+            for prm, rows16 in block_weights16(blk):
+                rows, cols = prm.shape
+                if weight_route(wk.w16(prm), rows, rows16) == "shadow":
+                    p.append(wk.w16(prm))
+                    n_shadow += 1
+                    continue
+                # the added rows must be zero (mamba.weight_copies16's layout, so also its bits)
+                c = (torch.zeros if rows16 != rows else torch.empty)((rows16, cols), dtype=st, device=self.device)
+                ops.cast_bf16(prm.detach(), out=c[:rows])
+                copies.append(c)
+                p.append(c.data_ptr())
+            ptrs.append((p[0], p[1], tuple(p[2:5]), tuple(p[5:8])))
+        return ptrs, copies, (n_shadow, len(copies))
+
     def _stage_fwd(self, wk, s, feats, gps_src, B):
-        """Mamba fusion at scale s (1-based): vel_emb{s}, then the stage on the walk's conventions"""
+        """Mamba fusion at scale s (1-based): vel_emb{s}, then the stage on the walk's conventions.  feats[0].dtype is the
+        stage's storage (the walk's: fp32, bf16 or f16): the maps in and out have it; gemb, the returned tokens xo and
+        vel_emb{s} are fp32 on every storage"""
         C = STAGE_WIDTH[s - 1]
         fus = getattr(self.encoder, f"mambafusion{s}")
         vel = getattr(self.encoder, f"vel_emb{s}")
         T = fus.n_tokens
+        st = feats[0].dtype
         for m in range(3):
-            assert feats[m].shape[0] == B * fus.seq_len and feats[m].shape[3] == C and feats[m].dtype == F32
+            assert feats[m].shape[0] == B * fus.seq_len and feats[m].shape[3] == C and feats[m].dtype == st
         pe = fus.embd_pdrop if wk.train else 0.0
         off_e = self._next_drop(B * T * C) if pe > 0 else 0
         _, gptr, rpg, gstride, K = gps_src
@@ -138,19 +217,24 @@ class MambaFuser(TransFuser):
                                ops._stream())
         ws = self._mamba_ws(mamba_fusion.stage_workspace_bytes(fus, B))
         outs = [torch.empty_like(f) for f in feats]
-        xo, tape = mamba_fusion.stage_forward(fus, ws, wk.record, feats, gemb, outs, B, drop=(pe, self._seed, off_e))
+        w16 = copies = None
+        if st != F32:
+            assert st == wk.dtype and wk.w16 is not None, (st, wk.dtype)
+            w16, copies, self.w16_routes[s] = self._stage_w16(wk, fus, st)
+        xo, tape = mamba_fusion.stage_forward(fus, ws, wk.record, feats, gemb, outs, B, drop=(pe, self._seed, off_e), w16=w16)
         cap = getattr(self, "_capture", None)
         if cap is not None:
             cap[f"mamba{s}"] = xo.clone()
-        return outs, xo, _MambaStageRec(s, C, T, gps_src, tape, [f.shape for f in feats])
+        return outs, xo, _MambaStageRec(s, C, T, gps_src, tape, [f.shape for f in feats], copies)
 
     def _stage_bwd(self, wk, rec, dfeats_out, dgps_tok, B):
         s, C, fshapes = rec.s, rec.C, rec.fshapes
         fus = getattr(self.encoder, f"mambafusion{s}")
         vel = getattr(self.encoder, f"vel_emb{s}")
+        st = dfeats_out[0].dtype     # the forward's storage: stage_backward holds the tape to it
         for m in range(3):
-            assert dfeats_out[m].shape == tuple(fshapes[m])
-        dfeats = [torch.empty(tuple(fshapes[m]), dtype=F32, device=self.device) for m in range(3)]
+            assert dfeats_out[m].shape == tuple(fshapes[m]) and dfeats_out[m].dtype == st
+        dfeats = [torch.empty(tuple(fshapes[m]), dtype=st, device=self.device) for m in range(3)]
         dgemb = torch.empty((B, 2, C), dtype=F32, device=self.device)
         ws = self._mamba_ws(mamba_fusion.stage_workspace_bytes(fus, B))
         mamba_fusion.stage_backward(fus, ws, rec.tape, dfeats_out, dgps_tok, dfeats, dgemb, B, wk.g)
@@ -172,7 +256,8 @@ class MambaFuser(TransFuser):
             return super()._head_fwd(wk, feats, xo, B, T)
         tm = self.encoder.time_mamba
         for f in feats:
-            assert tuple(f.shape) == (B * FRAMES, 8, 8, 512) and f.dtype == F32, (tuple(f.shape), f.dtype)
+            assert tuple(f.shape) == (B * FRAMES, 8, 8, 512) and f.dtype == feats[0].dtype, (tuple(f.shape), f.dtype)
+        # the maps have the walk's storage; from the pooled rows on, the temporal head is fp32 on every storage
         rows = torch.empty((3 * B * FRAMES, 512), dtype=F32, device=self.device)
         ops.pool_rows3_fwd(feats, rows)
         gps = xo.view(-1)[(T - 2) * 512:]   # sample b's two gps rows start b * T * 512 floats further: no copy
@@ -194,6 +279,6 @@ class MambaFuser(TransFuser):
         tape, gps, T = head.hook
         ws = self._mamba_ws(tm.mamba.workspace_bytes(3 * B, FRAMES))
         drows, dgps, _ = time_mamba_backward(tm, ws, tape, dfused, gps, T * 512, B, gdst=[wk.g(p) for p in params])
-        dfeats = [torch.empty(tuple(head.fshapes[m]), dtype=F32, device=self.device) for m in range(3)]
+        dfeats = [torch.empty(tuple(head.fshapes[m]), dtype=head.fdtype, device=self.device) for m in range(3)]
         ops.pool_rows3_bwd(drows, None, dfeats)
         return dfeats, (dgps, False)

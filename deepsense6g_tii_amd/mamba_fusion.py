@@ -59,8 +59,8 @@ Supported: fp32 / bf16 / f16 activations for MambaBlock and the walk-form stage,
 pack / unpack kernels are fp32); HIP device only, n_embd in {64, 128, 256, 512}, d_state 16, d_conv 4, 8 x 8 anchors,
 config.n_views == 1 (the reference's cat of the three modalities only lines up then), ln_size == (T, n_embd).  Train and eval;
 dropout is off in eval; no tape is kept when no gradient is needed.  Not covered: 16-bit storage of the MambaFusion module
-form, of the head (TimeMamba, time_mamba.py) and of the model (MambaFuser, mamba_fuser.py, which refuses compute modes other
-than "f32"), the frozen inference engine, missing-modality options.
+form and of the head (TimeMamba, time_mamba.py; the model, MambaFuser of mamba_fuser.py, runs the walk-form stage on 16-bit
+storage and keeps the head fp32), the frozen inference engine, missing-modality options.
 """
 from __future__ import annotations
 

@@ -1301,30 +1301,44 @@ def time_attn_bwd(dout, y, gps, attn, score, argmax, w5, w2, B, dparams=None, ac
     return dy, dgps, dparams
 
 
+def _pool_rows3_dtype(name, maps):
+    """the one storage dtype (fp32, bf16 or f16) of the maps of a head-pool call; a mixed set is refused here, on the host"""
+    dts = {t.dtype for t in maps if t is not None}
+    if len(dts) != 1 or not (dts <= {F32, BF16, F16}):
+        raise ValueError(f"{name}: the maps must share one dtype out of fp32, bf16 and f16, got "
+                         f"{[None if t is None else t.dtype for t in maps]}")
+    return dts.pop()
+
+
 def pool_rows3_fwd(feats, rows):
-    """rows [3 * N, C] (modality-major: map m's frame n is row m * N + n) = the mean over the 64 positions of the three fp32
-    NHWC maps feats[m] [N, 8, 8, C], one launch"""
+    """rows [3 * N, C] fp32 (modality-major: map m's frame n is row m * N + n) = the mean over the 64 positions of the three
+    NHWC maps feats[m] [N, 8, 8, C], one launch.  The maps' dtype (fp32, bf16 or f16, one for the three) picks the kernel; a
+    16-bit map needs C % 8 == 0"""
     assert len(feats) == 3
+    dt = _pool_rows3_dtype("pool_rows3_fwd", feats)
     N, _, _, C = feats[0].shape
     for f in feats:
-        _chk(f, N, 8, 8, C)
+        _chkmap(f, N, 8, 8, C, dtype=dt)
     _chk(rows, 3 * N, C)
-    assert C % 4 == 0 and N >= 1, (N, C)
-    lib().pool_rows3_fwd(_p(feats[0]), _p(feats[1]), _p(feats[2]), _p(rows), N, C, _stream())
+    assert C % (4 if dt == F32 else 8) == 0 and N >= 1, (N, C, dt)
+    _launch(lib().pool_rows3_fwd, lib().h16_pool_rows3_fwd, dt, _p(feats[0]), _p(feats[1]), _p(feats[2]), _p(rows), N, C)
     return rows
 
 
 def pool_rows3_bwd(drows, dfeats_in, dfeats):
     """backward of pool_rows3_fwd: dfeats[m] [N, 8, 8, C] = (dfeats_in[m] or 0) + drows[m * N + n] / 64 at every position, one
-    launch; dfeats_in: None, or three maps each of which may be None or dfeats[m] itself"""
+    launch; dfeats_in: None, or three maps each of which may be None or dfeats[m] itself.  drows is fp32; dfeats and dfeats_in
+    share one dtype (fp32, bf16 or f16), which picks the kernel: on 16-bit maps the sum is formed in fp32 and rounded once"""
     assert len(dfeats) == 3
     dfeats_in = (None,) * 3 if dfeats_in is None else dfeats_in
     assert len(dfeats_in) == 3
+    dt = _pool_rows3_dtype("pool_rows3_bwd", (*dfeats, *dfeats_in))
     N, _, _, C = dfeats[0].shape
     for t in (*dfeats, *dfeats_in):
         if t is not None:
-            _chk(t, N, 8, 8, C)
+            _chkmap(t, N, 8, 8, C, dtype=dt)
     _chk(drows, 3 * N, C)
-    assert C % 4 == 0 and N >= 1, (N, C)
-    lib().pool_rows3_bwd(_p(drows), *(_p(t) for t in dfeats_in), *(_p(t) for t in dfeats), N, C, _stream())
+    assert C % (4 if dt == F32 else 8) == 0 and N >= 1, (N, C, dt)
+    _launch(lib().pool_rows3_bwd, lib().h16_pool_rows3_bwd, dt, _p(drows), *(_p(t) for t in dfeats_in),
+            *(_p(t) for t in dfeats), N, C)
     return dfeats

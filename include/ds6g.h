@@ -581,6 +581,19 @@ int ds6g_temporal_param_grads(const float* dparam_part, int B, float* dw5, int a
 int ds6g_pool_rows3_fwd(const float* feat0, const float* feat1, const float* feat2, float* rows, int N, int C, void* stream);
 int ds6g_pool_rows3_bwd(const float* drows, const float* dfeat_in0, const float* dfeat_in1, const float* dfeat_in2,
                         float* dfeat0, float* dfeat1, float* dfeat2, int N, int C, void* stream);
+/* The head pool on 16-bit storage (st16: DS6G_ST_BF16 / DS6G_ST_F16): the same two kernels instantiated on the storage type of
+ * the MAPS of a model walk, the same single launch each way.  Storage map:
+ *   16-bit: feat_m; dfeat_in_m and dfeat_m          fp32: rows, drows (the temporal head's input and its gradient, which stay
+ *                                                   fp32 whatever the walk's storage), every sum and product
+ * A thread moves 16 bytes = 8 map elements: C % 8 == 0, C >= 8; N >= 1, N * 64 * C <= 2^31, all pointers 16-byte aligned;
+ * anything else (st16 == 0 included) is DS6G_ERR_ARG before anything is launched.
+ *   fwd  the 64 positions are widened and summed in fp32 in position order, as on fp32 storage; rows is not rounded.
+ *   bwd  float(dfeat_in_m or 0) + drows / 64 in fp32, rounded ONCE (to nearest even) at the store; dfeat_in_m may be null or
+ *        dfeat_m itself.  No atomics, fixed order: two runs are bit-identical. */
+int ds6g_h16_pool_rows3_fwd(int st16, const void* feat0, const void* feat1, const void* feat2, float* rows, int N, int C,
+                            void* stream);
+int ds6g_h16_pool_rows3_bwd(int st16, const float* drows, const void* dfeat_in0, const void* dfeat_in1, const void* dfeat_in2,
+                            void* dfeat0, void* dfeat1, void* dfeat2, int N, int C, void* stream);
 
 /* ---- spatial.hip-------------------------------------------------------------------------------*/
 /* normalize_imagenet + stack + NCHW->NHWC: model2_seq.py:36-45,481-482,491-493 */

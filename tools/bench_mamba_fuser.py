@@ -1,16 +1,18 @@
 """The MambaFuser training step (deepsense6g_tii_amd/mamba_fuser.py) at the reference's shapes - B = 12, seq_len 5, n_layer 8,
-dropout 0.1, fp32 - with config.TFM on and off, beside TransFuser (the GPT variant) in the same process: ms / step and
-samples/s of train_step_loss (forward + focal loss + backward), the four fusion stages alone (each model's own _stage_fwd +
-_stage_bwd on random maps of the walk's shapes, one after the other on one stream), torch.cuda.max_memory_allocated of one
-step, and kernel launches per step from rocprofv3 --kernel-trace --stats child runs (--no-count skips them).
+dropout 0.1 - with config.TFM on and off, beside TransFuser (the GPT variant), each in the compute modes "f32", "bf16" and "f16"
+(f16 under train.DynamicLossScaler) in the same process: ms / step and samples/s of train_step_loss (forward + focal loss +
+backward), the four fusion stages alone (each model's own _stage_fwd + _stage_bwd on random maps of the walk's shapes and
+storage, one after the other on one stream), torch.cuda.max_memory_allocated of one step, and kernel launches per step from
+rocprofv3 --kernel-trace --stats child runs (--no-count skips them).
 
 "rest" = step - stages alone: stems, BasicBlocks, head, join, loss.  The three models run the same trunks, so their rests
 should agree; where the Mamba models' rest is larger, the stages cost more inside the step than alone (or the reverse).
 
-The three models alternate inside every repeat.  Device-synchronised HIP-event timing, 3 warm-up and `--steps` timed steps
-per figure, median of 3 repeats; `--runs` child processes (the spread column is the noise between them).
+The models and their three storages alternate inside every repeat.  Device-synchronised HIP-event timing, 3 warm-up and
+`--steps` timed steps per figure, median of 3 repeats; `--runs` child processes (the spread column is the noise between them).
 
-usage: python tools/bench_mamba_fuser.py [--runs 2] [--steps 10] [--no-count] [--out profiles/mamba_fuser.txt]"""
+usage: python tools/bench_mamba_fuser.py [--runs 2] [--steps 10] [--variants ...] [--modes f32 bf16 f16] [--no-count]
+                                         [--count-variants ...] [--out profiles/mamba_fuser16.txt]"""
 import argparse
 import csv
 import json
@@ -26,6 +28,7 @@ sys.path.insert(0, ROOT)
 
 B, S, N_LAYER, PDROP = 12, 5, 8, 0.1
 VARIANTS = ("transfuser", "mamba_tfm1", "mamba_tfm0")
+MODES = ("f32", "bf16", "f16")
 COUNT_LO, COUNT_HI = 2, 4
 
 
@@ -49,23 +52,38 @@ def inputs():
     return fr.make_inputs(fr.RefConfig(seq_len=S), B, seed=100)[:5]
 
 
-def stages_alone(model):
-    """-> a callable running the four fusion stages forward + backward on random maps, as the walk calls them"""
+def stepper(model, mode, batch):
+    """-> a callable: one train_step_loss of `model` in compute mode `mode` ("f16": under a dynamic loss scaler)"""
+    from deepsense6g_tii_amd import ops
+    from deepsense6g_tii_amd.train import DynamicLossScaler
+    scaler = DynamicLossScaler().bind(model.device, model.flat_parameters()[0].numel()) if mode == "f16" else None
+
+    def step():
+        ops.set_compute_mode(mode)
+        return model.train_step_loss(*batch, loss_scaler=scaler)
+    return step
+
+
+def stages_alone(model, mode):
+    """-> a callable running the four fusion stages forward + backward on random maps of the mode's storage, as the walk
+    calls them"""
     import torch
     from deepsense6g_tii_amd import ops
     from deepsense6g_tii_amd._lib import lib
     from deepsense6g_tii_amd.model import STAGE_WIDTH
     dev = model.device
-    feats = [[torch.randn(B * S, 64 >> (s - 1), 64 >> (s - 1), C, device=dev) for _ in range(3)]
+    ops.set_compute_mode(mode)
+    wk = model._new_walk(True)      # refreshes the 16-bit weight shadow the stages read
+    feats = [[torch.randn(B * S, 64 >> (s - 1), 64 >> (s - 1), C, device=dev).to(wk.dtype) for _ in range(3)]
              for s, C in enumerate(STAGE_WIDTH, start=1)]
     gps = torch.randn(B, 2, 2, device=dev)
     dgps4 = torch.randn(B, 2, 512, device=dev)
-    wk = model._new_walk(True)
     for p in model.parameters():
         p.grad = None
     model._begin_backward(wk)
 
     def run():
+        ops.set_compute_mode(mode)
         model._advance_salt()
         lib().set_dropout_salt(model._salt_cur.data_ptr())
         recs, src = [], (gps, gps.data_ptr(), 2 * B, 0, 2)
@@ -97,13 +115,15 @@ def timed(fn, n):
     return reps
 
 
-def time_child(steps):
+def time_child(steps, variants, modes):
     import torch
     batch = inputs()
-    models = {v: build(v) for v in VARIANTS}
+    built = {v: build(v) for v in variants}
+    models = {f"{v}|{mode}": built[v] for v in variants for mode in modes}     # a model's three storages share its weights
+    steppers = {k: stepper(m, k.split("|")[1], batch) for k, m in models.items()}
     res = {}
     for v, m in models.items():
-        step = lambda m=m: m.train_step_loss(*batch)   # noqa: E731
+        step = steppers[v]
         for _ in range(3):
             step()
         torch.cuda.synchronize()
@@ -114,31 +134,31 @@ def time_child(steps):
         res[f"{v}_peak_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
         res[f"{v}_resident_gib"] = base / 2 ** 30
         res[f"{v}_finite"] = int(bool(torch.isfinite(loss).all()) and bool(torch.isfinite(logits).all()))
-    reps = {v: [] for v in VARIANTS}
-    for _ in range(3):                                  # the three models alternate inside every repeat
-        for v, m in models.items():
-            reps[v].append(timed(lambda m=m: m.train_step_loss(*batch), steps)[0])
-    for v in VARIANTS:
+    reps = {v: [] for v in models}
+    for _ in range(3):                                  # the models and their storages alternate inside every repeat
+        for v in models:
+            reps[v].append(timed(steppers[v], steps)[0])
+    for v in models:
         res[f"{v}_step_ms"] = statistics.median(reps[v])
     for v, m in models.items():
-        run = stages_alone(m)
+        run = stages_alone(m, v.split("|")[1])
         for _ in range(2):
             run()
         res[f"{v}_stages_ms"] = statistics.median(timed(run, steps))
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def count_child(variant, n):
+def count_child(key, n):
     import torch
-    batch = inputs()
-    model = build(variant)
+    variant, mode = key.split("|")
+    step = stepper(build(variant), mode, inputs())
     for _ in range(n):
-        model.train_step_loss(*batch)
+        step()
     torch.cuda.synchronize()
 
 
 def kernels_of(variant, n, tmp):
-    d = os.path.join(tmp, f"{variant}_{n}")
+    d = os.path.join(tmp, f"{variant.replace('|', '_')}_{n}")
     cmd = ["timeout", "-k", "10", "280", "rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "c", "--output-format", "csv",
            "--", sys.executable, os.path.abspath(__file__), "--count-child", variant, str(n)]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -155,20 +175,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=VARIANTS)
+    ap.add_argument("--modes", nargs="+", default=list(MODES), choices=MODES)
     ap.add_argument("--no-count", action="store_true")
+    ap.add_argument("--count-variants", nargs="*", default=None, choices=VARIANTS, help="default: --variants")
     ap.add_argument("--out")
     ap.add_argument("--time-child", action="store_true")
     ap.add_argument("--count-child", nargs=2, metavar=("VARIANT", "N"))
     args = ap.parse_args()
     if args.time_child:
-        time_child(args.steps)
+        time_child(args.steps, args.variants, args.modes)
         return 0
     if args.count_child:
         count_child(args.count_child[0], int(args.count_child[1]))
         return 0
     runs = []
     for run in range(args.runs):
-        cmd = ["timeout", "-k", "10", "400", sys.executable, os.path.abspath(__file__), "--time-child", "--steps", str(args.steps)]
+        cmd = ["timeout", "-k", "10", "500", sys.executable, os.path.abspath(__file__), "--time-child", "--steps", str(args.steps),
+               "--variants", *args.variants, "--modes", *args.modes]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         line = [s for s in p.stdout.splitlines() if s.startswith("RESULT ")]
         if p.returncode != 0 or not line:
@@ -180,7 +204,8 @@ def main():
     if not args.no_count:
         tmp = tempfile.mkdtemp(prefix="bench_mamba_fuser_")
         try:
-            for v in VARIANTS:
+            for v in [f"{a}|{m}" for a in (args.variants if args.count_variants is None else args.count_variants)
+                      for m in args.modes]:
                 counts[v] = (kernels_of(v, COUNT_HI, tmp) - kernels_of(v, COUNT_LO, tmp)) / (COUNT_HI - COUNT_LO)
                 print(f"{v}: launches counted", file=sys.stderr, flush=True)
         except RuntimeError as e:
@@ -189,21 +214,30 @@ def main():
         finally:
             shutil.rmtree(tmp, ignore_errors=True)
     lines = [f"training step (train_step_loss: forward + focal loss + backward), B = {B}, seq_len {S}, n_layer {N_LAYER}, dropout "
-             f"{PDROP}, fp32, one MI355X; {args.runs} runs, each the median of 3 x {args.steps} steps, the three models alternating "
-             "in one process",
-             f"{'model':11s} {'figure':22s} " + " ".join(f"{'run ' + str(i):>9s}" for i in range(args.runs)) + f" {'spread':>8s}"]
-    for v in VARIANTS:
+             f"{PDROP}, one MI355X; {args.runs} runs, each the median of 3 x {args.steps} steps, the models and their storages "
+             "(compute modes; f16 under the dynamic loss scaler) alternating in one process",
+             f"{'model|mode':16s} {'figure':22s} " + " ".join(f"{'run ' + str(i):>9s}" for i in range(args.runs)) + f" {'spread':>8s}"]
+    for v in [f"{a}|{m}" for a in args.variants for m in args.modes]:
         for fig, key, fmt in (("ms / step", "step_ms", "9.2f"), ("stages alone, ms", "stages_ms", "9.2f"),
                               ("peak GiB in a step", "peak_gib", "9.2f"), ("resident GiB", "resident_gib", "9.2f")):
             ts = [r[f"{v}_{key}"] for r in runs]
-            lines.append(f"{v:11s} {fig:22s} " + " ".join(format(t, fmt) for t in ts) +
+            lines.append(f"{v:16s} {fig:22s} " + " ".join(format(t, fmt) for t in ts) +
                          f" {(max(ts) - min(ts)) / min(ts) * 100:7.1f}%")
         step = statistics.median(r[f"{v}_step_ms"] for r in runs)
         stages = statistics.median(r[f"{v}_stages_ms"] for r in runs)
-        lines.append(f"{v:11s} samples/s {B / step * 1e3:.1f}; rest = step - stages alone = {step - stages:.2f} ms; launches / step "
-                     f"{counts[v]:.0f}" if counts else
-                     f"{v:11s} samples/s {B / step * 1e3:.1f}; rest = step - stages alone = {step - stages:.2f} ms")
-        lines.append(f"{v:11s} loss and logits finite: {'yes' if all(r[f'{v}_finite'] for r in runs) else 'NO'}")
+        lines.append(f"{v:16s} samples/s {B / step * 1e3:.1f}; rest = step - stages alone = {step - stages:.2f} ms; launches / step "
+                     f"{counts[v]:.0f}" if v in counts else
+                     f"{v:16s} samples/s {B / step * 1e3:.1f}; rest = step - stages alone = {step - stages:.2f} ms")
+        lines.append(f"{v:16s} loss and logits finite: {'yes' if all(r[f'{v}_finite'] for r in runs) else 'NO'}")
+    # the same figures as one table (medians over the runs); working set = peak in a step - resident before it
+    med = lambda v, key: statistics.median(r[f"{v}_{key}"] for r in runs)   # noqa: E731
+    lines += ["", f"{'model|mode':16s} {'ms / step':>10s} {'samples/s':>10s} {'stages, ms':>11s} {'rest, ms':>9s} "
+                  f"{'launches':>9s} {'working set, GiB':>17s}"]
+    for v in [f"{a}|{m}" for a in args.variants for m in args.modes]:
+        step, stages = med(v, "step_ms"), med(v, "stages_ms")
+        launches = f"{counts[v]:.0f}" if v in counts else "-"
+        lines.append(f"{v:16s} {step:10.2f} {B / step * 1e3:10.1f} {stages:11.2f} {step - stages:9.2f} {launches:>9s} "
+                     f"{med(v, 'peak_gib') - med(v, 'resident_gib'):17.2f}")
     text = "\n".join(lines)
     print(text)
     if args.out:
