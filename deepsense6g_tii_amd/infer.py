@@ -57,10 +57,23 @@ class InferenceEngine:
     # ---------------------------------------------------------------- snapshot ------------------
     def _allocate(self):
         """device buffers of the snapshot (allocated once: refresh() writes into them) and the walk that reads them"""
+        self._allocate_params()
+        self._allocate_folds()
+        self._walk = self._make_walk()
+
+    def _placement(self, name):
+        """where the snapshot keeps the non-trunk parameter `name`: True - the 16-bit flat buffer (a GEMM operand on 16-bit
+        storage), False - the fp32 one, None - the engine snapshots it in a buffer of its own layout (a subclass does)"""
+        return self.dtype != F32 and _GEMM_WEIGHT.search(name) is not None
+
+    def _allocate_params(self):
         m, dev, h16 = self.model, self.model.device, self.dtype != F32
         named = [(n, p) for n, p in m.arena_layout()[0] if not n.startswith(_TRUNKS)]   # arena order: k|q|v stay adjacent
+        place = {n: self._placement(n) for n, _ in named}
+        self._own_ids = {id(p) for n, p in named if place[n] is None}
+        named = [(n, p) for n, p in named if place[n] is not None]
         pad4 = lambda n: (n + 3) // 4 * 4  # noqa: E731
-        in16 = lambda n: h16 and _GEMM_WEIGHT.search(n) is not None  # noqa: E731
+        in16 = lambda n: place[n]  # noqa: E731
         self._flat32 = torch.zeros(sum(pad4(p.numel()) for n, p in named if not in16(n)), dtype=F32, device=dev)
         self._flat16 = torch.zeros(sum(pad4(p.numel()) for n, p in named if in16(n)), dtype=self.dtype if h16 else F32,
                                    device=dev)
@@ -74,8 +87,11 @@ class InferenceEngine:
             off[k] += pad4(p.numel())
             (self.wtable16 if k else self.wtable)[id(p)] = seg.data_ptr()
             self._copies.append((p, seg))
+
+    def _allocate_folds(self):
         # every BatchNorm-followed conv: (conv, bn, K, taps, cin, cpad) -> folded filter w, bias b, Winograd filter u (fp32
         # storage, 3x3 / stride 1), packed stem filter wp (16-bit storage)
+        m = self.model
         self.folded, self._folds = {}, []
         for trunk, _, cin, _ in m._trunks():
             self._add_fold(trunk.conv1, trunk.bn1, 64, 49, cin, 4, stem=True)
@@ -86,8 +102,10 @@ class InferenceEngine:
                     self._add_fold(blk.conv2, blk.bn2, K, 9, K, K, wino=True)
                     if blk.downsample is not None:
                         self._add_fold(blk.downsample[0], blk.downsample[1], K, 1, C, C)
-        self._walk = _Walk(_table(self.wtable), _table(self.wtable16) if h16 else None,
-                           lambda conv, *_: self.folded[id(conv.weight)], self.dtype)
+
+    def _make_walk(self):
+        return _Walk(_table(self.wtable), _table(self.wtable16) if self.dtype != F32 else None,
+                     lambda conv, *_: self.folded[id(conv.weight)], self.dtype)
 
     def _add_fold(self, conv, bn, K, taps, cin, cpad, wino=False, stem=False):
         dev, h16 = self.model.device, self.dtype != F32
@@ -116,8 +134,8 @@ class InferenceEngine:
         shadow is honoured) and the BatchNorm running statistics - into the SAME device buffers (a graph captured by
         capture() sees the new weights).  Asynchronous on the current stream."""
         m = self.model
-        if any(id(p) not in self.wtable and id(p) not in self.wtable16 and id(p) not in self._trunk_ids
-               for p in m.parameters()):
+        if any(id(p) not in self.wtable and id(p) not in self.wtable16 and id(p) not in self._trunk_ids and
+               id(p) not in self._own_ids for p in m.parameters()):
             raise RuntimeError("the model's Parameter objects were replaced after freeze_inference(); freeze it again")
         for p, seg in self._copies:
             if seg.dtype == F32:

@@ -43,7 +43,9 @@ The tape of one layer is u, xz, xc, y (16-bit) and x_dbl, dt, delta_raw, the chu
 Supported: d_state 16, d_conv 4, d_model % 64 == 0 (expand * d_model % 128 == 0, dt_rank % 4 == 0), bias=False,
 conv_bias=True, fp32 parameters, fp32 / bf16 / f16 activations, any B, L >= 1.  Anything else raises ValueError at
 construction.  Not covered: 16-bit storage of the head (TimeMamba) and the model (MambaFuser) above this layer (the block and
-the walk-form stage run it: mamba_fusion.py), the frozen inference engine, the single-step inference_params path.
+the walk-form stage run it: mamba_fusion.py), the single-step inference_params path.  A frozen model runs this layer's conv
+and scan through the grouped forward-only kernels of csrc/mamba_infer.hip (mamba_fusion.block_forward_frozen), not through
+layer_forward.
 """
 from __future__ import annotations
 

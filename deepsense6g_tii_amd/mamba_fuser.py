@@ -34,9 +34,13 @@ Supported: compute modes "f32", "bf16", "f16"; config.n_views == 1, 8 x 8 anchor
 seq_len >= 1 without TFM, seq_len == 5 with it (the head hard-wires Linear(5, 5)).  Anything else raises at construction, or at
 the first forward for the compute mode ("f32x3" / "f32x6": the Mamba kernels have no split-bf16 form).  Not covered: TimeMamba
 on 16-bit storage (its tensors are [3 B 5, 512] fp32 rows, 0.3 ms of a 115 ms step, and the last arithmetic before the logits),
-the MambaFusion module form on 16-bit storage, the frozen inference engine and hipGraph capture (freeze_inference,
-capture_inference and train.CapturedTrainStep raise NotImplementedError in every mode), missing-modality input replacement and
-feature injection, n_views > 1.
+the MambaFusion module form on 16-bit storage, hipGraph capture (capture_inference and train.CapturedTrainStep raise
+NotImplementedError in every mode), missing-modality input replacement and feature injection, n_views > 1.
+
+Serving: mamba_infer.freeze(model, storage) -> MambaFuserEngine, the frozen inference engine on f32 / bf16 / f16 storage (a
+snapshot with BN-folded trunks and the stages' stacked GEMM weights; this model's walk under _Walk.frozen, where _stage_fwd
+runs mamba_fusion.stage_forward_frozen).  MambaFuser.freeze_inference itself still raises NotImplementedError and names that
+entry point.
 """
 from __future__ import annotations
 
@@ -141,7 +145,8 @@ class MambaFuser(TransFuser):
 
     # ---------------------------------------------------------------- what is not built ---------
     def freeze_inference(self, storage="f32"):
-        raise NotImplementedError("MambaFuser.freeze_inference: the frozen inference engine does not cover the Mamba stages")
+        raise NotImplementedError("MambaFuser.freeze_inference is not routed to the frozen engine of the Mamba walk yet: "
+                                  "use deepsense6g_tii_amd.mamba_infer.freeze(model, storage)")
 
     def capture_inference(self, image_list, lidar_list, radar_list, gps):
         raise NotImplementedError("MambaFuser.capture_inference: graph replay of the Mamba walk is not supported")
@@ -217,6 +222,12 @@ class MambaFuser(TransFuser):
                                ops._stream())
         ws = self._mamba_ws(mamba_fusion.stage_workspace_bytes(fus, B))
         outs = [torch.empty_like(f) for f in feats]
+        if wk.frozen is not None:     # a frozen engine's walk (mamba_infer.py): its own operands, no tape, no weight cast
+            xo = mamba_fusion.stage_forward_frozen(fus, ws, feats, gemb, outs, B, wk.frozen.stages[s - 1])
+            cap = getattr(self, "_capture", None)
+            if cap is not None:
+                cap[f"mamba{s}"] = xo.clone()
+            return outs, xo, _MambaStageRec(s, C, T, gps_src, None, [f.shape for f in feats], None)
         w16 = copies = None
         if st != F32:
             assert st == wk.dtype and wk.w16 is not None, (st, wk.dtype)
@@ -262,7 +273,9 @@ class MambaFuser(TransFuser):
         ops.pool_rows3_fwd(feats, rows)
         gps = xo.view(-1)[(T - 2) * 512:]   # sample b's two gps rows start b * T * 512 floats further: no copy
         ws = self._mamba_ws(tm.mamba.workspace_bytes(3 * B, FRAMES))
-        fused, tape = time_mamba_forward(tm, ws, wk.record, rows, gps, T * 512, B)
+        # a frozen engine's walk reads the head's parameters from its snapshot, every other walk where they live
+        fused, tape = time_mamba_forward(tm, ws, wk.record, rows, gps, T * 512, B,
+                                         params=None if wk.frozen is None else wk.frozen.time_params)
         return fused, (tape, gps, T)
 
     def _head_bwd(self, wk, head, dfused, B):

@@ -60,16 +60,23 @@ pack / unpack kernels are fp32); HIP device only, n_embd in {64, 128, 256, 512},
 config.n_views == 1 (the reference's cat of the three modalities only lines up then), ln_size == (T, n_embd).  Train and eval;
 dropout is off in eval; no tape is kept when no gradient is needed.  Not covered: 16-bit storage of the MambaFusion module
 form and of the head (TimeMamba, time_mamba.py; the model, MambaFuser of mamba_fuser.py, runs the walk-form stage on 16-bit
-storage and keeps the head fp32), the frozen inference engine, missing-modality options.
+storage and keeps the head fp32), missing-modality options.
+
+Frozen form (block_forward_frozen / stage_forward_frozen, end of the file): the stage of a frozen model
+(mamba_infer.MambaFuserEngine), forward only and without a tape, on operands the engine prepared once - the three GEMMs that
+read x1 as ONE GEMM on a [9C, C] weight (cat9_layout), the two directions' convs and scans as one grouped launch each
+(csrc/mamba_infer.hip) with dt_proj inside the scan.  The activations follow the storage map above.
 """
 from __future__ import annotations
+
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
 from . import ops
 from .mamba import (Mamba, _check_params, deliver_pair, grad_slots, layer_forward, layer_backward, stream_workspace,
-                    weight_copies16)
+                    weight_copies16, x_proj_rows16)
 
 F32 = torch.float32
 
@@ -444,3 +451,132 @@ def stage_backward(fus, ws, tape, dfeats_out, dgps_tok, dfeats, dgemb, B, g, w=N
                                w16=w16[i] if h16 else None)
     gpos, apos = g(fus.pos_emb)
     ops.pool_swap_tokens_bwd(dx.view(B, T, C), dfeats_out, dfeats, dgemb, gpos, apos, S, *drop)
+
+
+# ---- the stage of a frozen model ----------------------------------------------------------------------------------------
+# A frozen model's weights do not change between calls and an inference forward keeps no tape, so the block can take a shape
+# the training walk cannot: in_proj of both directions and fc2 all read x1 - ONE GEMM on their weights stacked at freeze time;
+# its output `cat` [M, 9C] holds x | z of the forward layer, x | z of the reverse layer and f2 as column blocks that the
+# grouped conv, the grouped scan and the gate read in place.
+def cat9_layout(C):
+    """Pure host function: where the stacked [9C, C] weight (and its [9C] bias, zero but for fc2's) keeps what.  rows: name ->
+    (first row, end row) of in_proj.weight of the forward Mamba, of the reverse Mamba, and of fc2.weight / fc2.bias; cols: the
+    column blocks of the GEMM's output - a row block of the weight IS a column block of the output: x / z = the halves of each
+    in_proj, f2 = fc2's"""
+    D = 2 * C
+    return SimpleNamespace(n=9 * C, D=D,
+                           rows=dict(in_proj_fwd=(0, 2 * D), in_proj_bwd=(2 * D, 4 * D), fc2=(4 * D, 4 * D + C)),
+                           cols=dict(x_fwd=(0, D), z_fwd=(D, 2 * D), x_bwd=(2 * D, 3 * D), z_bwd=(3 * D, 4 * D),
+                                     f2=(4 * D, 4 * D + C)))
+
+
+def frozen_plan(C, dtype):
+    """Pure host rule: which form each step of a frozen block takes at width C on storage `dtype`, from the measured table
+    (profiles/mamba_infer.txt, B = 12, T = 962, new form against what it replaces, both storages):
+        grouped conv   wins at every width (1.04x .. 1.27x)                              -> always
+        grouped scan   1.40x / 1.18x at C = 64 / 128, level at 256, LOSES at 512 (0.88x:  -> C <= 256; at 512 the layer's own
+                       r = 32 there, and the dt_proj prologue costs more than the           sequence per direction (copy_cols,
+                       delta_raw round trip it saves)                                        dt_proj GEMM, selective_scan_fwd)
+        stacked GEMM   wins at every width on fp32 (1.04x .. 1.44x) and up to C = 256    -> everywhere but 16-bit C = 512: there
+                       on 16-bit (1.09x .. 2.5x), LOSES at 16-bit C = 512 (0.94x)           three GEMMs on the row blocks of the
+                                                                                             same stacked weight
+    -> SimpleNamespace(grouped_scan, stacked_gemm)"""
+    return SimpleNamespace(grouped_scan=C <= 256, stacked_gemm=not (C >= 512 and dtype != F32))
+
+
+def block_forward_frozen(blk, ws, x2, B, T, fz):
+    """one MambaBlock of a frozen model on x2 [B, T * C] (contiguous, the storage dtype) -> out [B * T, C] of that dtype.  fz:
+    the block's frozen operands, tensors the caller owns: ln_w, ln_b [T, C], fc1_b [C], cat_b [9C] fp32; fc1_w [C, C] and
+    cat_w [9C, C] (cat9_layout) in the storage dtype; dirs = (forward, reverse), each with conv_w, conv_b, dt_w, dt_b, A_log, D
+    fp32 and x_w [n_x, 2C] (16-bit storage: zero-padded to mamba.x_proj_rows16 rows), out_w [C, 2C] in the storage dtype.
+    Six GEMMs, one grouped conv, one grouped scan (three launches), the sample LayerNorm and the gate; no tape, no cast, no
+    copy - except where frozen_plan(C, dtype) picks the older form of a step at C = 512, on the measured table."""
+    C, M = blk.n_embd, B * T
+    D, r = 2 * C, blk.forward_mamba.dt_rank
+    if x2.dtype == F32:
+        linear, xkw = ops.linear_fwd, {}
+    else:
+        linear, xkw = ops.bf16_linear_fwd, dict(out16=False)     # fp32 x_dbl from the zero-padded weight
+    plan, lay = frozen_plan(C, x2.dtype), cat9_layout(C)
+    xl, _, _ = ops.sample_layernorm_fwd(x2, fz.ln_w, fz.ln_b, ws)
+    x1 = linear(xl.view(M, C), fz.fc1_w.data_ptr(), fz.fc1_b.data_ptr(), C)
+    if plan.stacked_gemm:
+        cat = linear(x1, fz.cat_w.data_ptr(), fz.cat_b.data_ptr(), lay.n)
+        col = lambda name: cat[:, lay.cols[name][0]:lay.cols[name][1]]  # noqa: E731
+    else:                                  # the same weight, one GEMM per row block (frozen_plan has the reason)
+        part = {}
+        for name, (lo, hi) in lay.rows.items():
+            part[name] = linear(x1, fz.cat_w[lo:].data_ptr(), fz.cat_b[lo:].data_ptr() if name == "fc2" else 0, hi - lo)
+        src = dict(x_fwd=("in_proj_fwd", 0), z_fwd=("in_proj_fwd", D), x_bwd=("in_proj_bwd", 0), z_bwd=("in_proj_bwd", D),
+                   f2=("fc2", 0))
+        col = lambda name: part[src[name][0]][:, src[name][1]:src[name][1] + (C if name == "f2" else D)]  # noqa: E731
+    df, db = fz.dirs
+    xc = ops.mamba_conv_fwd_grouped([(col("x_fwd"), df.conv_w, df.conv_b, False), (col("x_bwd"), db.conv_w, db.conv_b, True)],
+                                    B, T)
+    x_dbl = [linear(xc[k], d.x_w.data_ptr(), 0, d.x_w.shape[0], **xkw) for k, d in enumerate(fz.dirs)]
+    zs = (col("z_fwd"), col("z_bwd"))
+    if plan.grouped_scan:
+        y = ops.mamba_scan_fwd_grouped([(xc[k], zs[k], x_dbl[k], d.dt_w, d.dt_b, d.A_log, d.D, bool(k))
+                                        for k, d in enumerate(fz.dirs)], B, T, r, ws)
+    else:                                  # the layer's own sequence per direction (frozen_plan has the reason)
+        y = []
+        for k, d in enumerate(fz.dirs):
+            dt = ops.copy_cols(x_dbl[k][:, :r], torch.empty((M, r), dtype=F32, device=x2.device))
+            raw = ops.linear_fwd(dt, d.dt_w.data_ptr(), 0, D)
+            y.append(ops.selective_scan_fwd(xc[k], raw, d.dt_b, d.A_log, x_dbl[k][:, r:r + 16], x_dbl[k][:, r + 16:r + 32], d.D,
+                                            zs[k], B, T, ws, bool(k), False)[0])
+    fm = linear(y[0], df.out_w.data_ptr(), 0, C)
+    bm = linear(y[1], db.out_w.data_ptr(), 0, C)
+    return ops.bimamba_gate_fwd(fm, bm, col("f2"), B, T)
+
+
+def stage_forward_frozen(fus, ws, feats, gemb, outs, B, fz):
+    """stage_forward for a frozen model: the pool-swap pack without dropout, the frozen blocks, ln_f and the grouped
+    upsample-add, as stage_forward runs them.  fz: pos_emb [1, T, C], ln_f_w, ln_f_b [C] fp32 tensors and blocks = one
+    block_forward_frozen operand set per block.  -> xo, the tokens after ln_f [B * T, C] fp32"""
+    _stage_ws(fus, ws, B)
+    S, C, T = fus.seq_len, fus.n_embd, fus.n_tokens
+    st = feats[0].dtype
+    assert len(fz.blocks) == len(fus.mambablocks)
+    assert ws.nbytes >= ops.mamba_scan_fwd_grouped_workspace_bytes(B, T, 2 * C, 2)
+    x = torch.empty((B, T, C), dtype=st, device=gemb.device)
+    ops.pool_swap_tokens_fwd(feats, gemb, fz.pos_emb.data_ptr(), x, S)
+    for blk, bz in zip(fus.mambablocks, fz.blocks):
+        x = block_forward_frozen(blk, ws, x.view(B, T * C), B, T, bz)
+    x = x.view(B * T, C)
+    if st != F32:
+        x = ops.cast_f32(x)                                        # ln_f reads the last block's output widened once
+    xo, _, _ = ops.layernorm_fwd(x, fz.ln_f_w.data_ptr(), fz.ln_f_b.data_ptr(), fus.ln_f.eps)
+    ops.upsample_add_fwd3(feats, xo, outs, (S, S, S), (0, S * 64, 2 * S * 64), T)
+    return xo
+
+
+def freeze_block(blk, dtype=F32):
+    """-> the `fz` of block_forward_frozen from the block's parameters as they are now, in fresh tensors: the GEMM weights in
+    `dtype` (the storage), everything else fp32.  For a block on its own (tests, tools); the engine of a whole model
+    (mamba_infer.MambaFuserEngine) lays the same operands out in the snapshot it owns."""
+    C = blk.n_embd
+    lay = cat9_layout(C)
+    dev = blk.fc1.weight.device
+
+    def gemm(ws, rows=None):     # the rows of `ws` stacked, zero rows added up to `rows`
+        src = torch.cat([w.detach() for w in ws], 0).contiguous()
+        out = torch.zeros((rows or src.shape[0], src.shape[1]), dtype=dtype, device=dev)
+        if dtype == F32:
+            out[:src.shape[0]].copy_(src)
+        else:
+            ops.cast_bf16(src, out=out[:src.shape[0]])
+        return out
+
+    f32 = lambda p: p.detach().clone().contiguous()  # noqa: E731
+    cat_b = torch.zeros(lay.n, dtype=F32, device=dev)
+    cat_b[lay.rows["fc2"][0]:lay.rows["fc2"][1]].copy_(blk.fc2.bias.detach())
+    dirs = []
+    for mod in (blk.forward_mamba, blk.backward_mamba):
+        n_x = mod.dt_rank + 32 if dtype == F32 else x_proj_rows16(mod.dt_rank)
+        dirs.append(SimpleNamespace(conv_w=f32(mod.conv1d.weight), conv_b=f32(mod.conv1d.bias), x_w=gemm([mod.x_proj.weight], n_x),
+                                    dt_w=f32(mod.dt_proj.weight), dt_b=f32(mod.dt_proj.bias), A_log=f32(mod.A_log),
+                                    D=f32(mod.D), out_w=gemm([mod.out_proj.weight])))
+    return SimpleNamespace(ln_w=f32(blk.ln1.weight), ln_b=f32(blk.ln1.bias), fc1_w=gemm([blk.fc1.weight]), fc1_b=f32(blk.fc1.bias),
+                           cat_w=gemm([blk.forward_mamba.in_proj.weight, blk.backward_mamba.in_proj.weight, blk.fc2.weight]),
+                           cat_b=cat_b, dirs=tuple(dirs))

@@ -237,13 +237,14 @@ class _Walk:
     w(p) / w16(p): fp32 / 16-bit device pointer of parameter p (w16 None on fp32 storage); folded(conv, bn, K, taps, cin,
     cpad, wino) -> _Folded of a BN-folded inference conv, None when BatchNorm is not folded; dtype: the storage of feature
     maps and GEMM operands (F32, BF16 or F16); train: train-mode BatchNorm and dropout; record: a tape is kept; g(p): (grad
-    pointer, accumulate flag) of p, set by _begin_backward."""
-    __slots__ = ("w", "w16", "folded", "dtype", "train", "record", "fold", "g")
+    pointer, accumulate flag) of p, set by _begin_backward; frozen: a frozen engine's operands beyond the pointer tables (the
+    per-stage operands of mamba_infer.MambaFuserEngine), None for every other walk."""
+    __slots__ = ("w", "w16", "folded", "dtype", "train", "record", "fold", "g", "frozen")
 
     def __init__(self, w, w16=None, folded=None, dtype=F32, train=False, record=False):
         assert not (folded is not None and (train or record)), "the backward needs the BatchNorm tape"
         self.w, self.w16, self.folded, self.dtype, self.train, self.record = w, w16, folded, dtype, train, record
-        self.fold, self.g = folded is not None, None
+        self.fold, self.g, self.frozen = folded is not None, None, None
 
 
 # ------------------------------------------------------------------------------------------------

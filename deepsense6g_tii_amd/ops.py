@@ -1057,6 +1057,69 @@ def selective_scan_bwd(u, delta_raw, dt_bias, A_log, Bm, Cm, Dp, z, dy, saved, d
     return dA, dD
 
 
+# The layer's conv and scan for a frozen model (csrc/mamba_infer.hip): forward only, no tape, one launch for ndir = 1 or 2
+# directions.  The operand rules are the ones above; x_dbl and every parameter are fp32 on every storage.
+class _MambaConvDir(ctypes.Structure):     # ds6g_mamba_conv_dir
+    _fields_ = [("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("ld_x", ctypes.c_int), ("reverse", ctypes.c_int)]
+
+
+class _MambaScanDir(ctypes.Structure):     # ds6g_mamba_scan_dir
+    _fields_ = [("u", ctypes.c_void_p), ("z", ctypes.c_void_p), ("x_dbl", ctypes.c_void_p), ("dt_w", ctypes.c_void_p),
+                ("dt_b", ctypes.c_void_p), ("A_log", ctypes.c_void_p), ("D", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("ld_u", ctypes.c_int), ("ld_z", ctypes.c_int), ("ld_x", ctypes.c_int), ("reverse", ctypes.c_int)]
+
+
+def mamba_scan_fwd_grouped_workspace_bytes(B, L, D, ndir):
+    return int(lib().mamba_scan_fwd_grouped_workspace_size(B, L, D, ndir))
+
+
+def mamba_conv_fwd_grouped(dirs, B, L):
+    """dirs: one or two (x, w, bias, reverse) - x [B*L, D] (a column block allowed), conv1d.weight (D, 1, 4), conv1d.bias (D,) -
+    of one D and one dtype -> the list of silu(causal depthwise conv1d(x) + bias) [B*L, D], one per direction, from ONE launch;
+    each equals causal_conv1d_silu_fwd on the same operands bit for bit"""
+    n = len(dirs)
+    assert n in (1, 2), n
+    M, D = dirs[0][0].shape
+    st = dirs[0][0].dtype
+    assert M == B * L and D % 128 == 0
+    descs = (_MambaConvDir * n)()
+    ys = []
+    for d, (x, w, bias, reverse) in zip(descs, dirs):
+        y = torch.empty((M, D), dtype=st, device=x.device)
+        d.x, d.ld_x, d.w, d.bias, d.y, d.reverse = _p(x), _rows_al(x, M, D, st), _vec(w, D, 1, 4), _vec(bias, D), _p(y), \
+            int(bool(reverse))
+        ys.append(y)
+    _launch(lib().mamba_conv_fwd_grouped, lib().h16_mamba_conv_fwd_grouped, st, descs, n, B, L, D)
+    return ys
+
+
+def mamba_scan_fwd_grouped(dirs, B, L, r, ws: Workspace):
+    """dirs: one or two (u, z, x_dbl, dt_w, dt_b, A_log, Dp, reverse): u / z [B*L, D] of one dtype (column blocks allowed);
+    x_dbl [B*L, >= r + 32] fp32, read in place as dt | Bm | Cm; dt_proj.weight (D, r), dt_proj.bias (D,), A_log (D, 16),
+    D (D,) fp32 -> the list of y [B*L, D] of u's dtype.  The selective scan with dt_proj evaluated in its staging prologue, no
+    tape; three launches for all directions, one when L fits a chunk"""
+    n = len(dirs)
+    assert n in (1, 2), n
+    M, D = dirs[0][0].shape
+    st = dirs[0][0].dtype
+    assert M == B * L and D % 128 == 0 and r % 4 == 0 and 4 <= r <= 32, (M, B, L, D, r)
+    assert ws.nbytes >= mamba_scan_fwd_grouped_workspace_bytes(B, L, D, n), "workspace too small for mamba_scan_fwd_grouped"
+    descs = (_MambaScanDir * n)()
+    ys = []
+    for d, (u, z, x_dbl, dt_w, dt_b, A_log, Dp, reverse) in zip(descs, dirs):
+        y = torch.empty((M, D), dtype=st, device=u.device)
+        n_x = x_dbl.shape[1]
+        assert n_x >= r + 32, (n_x, r)
+        d.u, d.ld_u, d.z, d.ld_z = _p(u), _rows_al(u, M, D, st), _p(z), _rows_al(z, M, D, st)
+        d.x_dbl, d.ld_x = _p(x_dbl), _rows_al(x_dbl, M, n_x)
+        d.dt_w, d.dt_b, d.A_log, d.D = _vec(dt_w, D, r), _vec(dt_b, D), _vec(A_log, D, 16), _vec(Dp, D)
+        d.y, d.reverse = _p(y), int(bool(reverse))
+        ys.append(y)
+    _launch(lib().mamba_scan_fwd_grouped, lib().h16_mamba_scan_fwd_grouped, st, descs, n, B, L, D, r, ws.ptr, ws.nbytes)
+    return ys
+
+
 def cast_f32(src, out=None):
     """fp32 copy (exact) of a contiguous bf16 / f16 tensor whose numel is a multiple of 8"""
     _chk16(src)

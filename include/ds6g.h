@@ -450,6 +450,36 @@ int ds6g_h16_selective_scan_bwd(int st16, const void* u, int ld_u, const float* 
                                 size_t ws_bytes, void* stream);
 int ds6g_cast_h16_f32(int st16, const void* src, float* dst, long n, void* stream);
 
+/* ---- mamba_infer.hip : the layer's conv and scan for a frozen model - forward only, no tape, grouped ------------------
+ * One launch covers ndir = 1 or 2 directions; dirs: host array of ndir descriptors (ds6g_mamba_conv_dir / ds6g_mamba_scan_dir,
+ * ds6g_types.h), read during the call and handed to the kernel by value.  Every direction has operands, row strides (in
+ * elements of the operand's type, whole 16-byte pieces) and a `reverse` flag of its own; B, L, D (and r) are shared.  The
+ * fp32 entry points take fp32 x / y (conv) and u / z / y (scan), the ds6g_h16_ ones bf16 / f16 (st16); x_dbl, every parameter,
+ * the chunk states and all arithmetic are fp32 for every storage.
+ *   mamba_conv_fwd_grouped  y = silu(causal depthwise conv1d(x) + bias) per direction: per element the arithmetic of
+ *                           ds6g_(h16_)causal_conv1d_silu_fwd, so the result equals ndir such calls bit for bit.  One launch.
+ *   mamba_scan_fwd_grouped  the selective scan of ds6g_(h16_)selective_scan_fwd with dt_proj inside: from x_dbl (x_proj's
+ *                           fp32 output, row stride ld_x >= r + 32) the kernel reads dt = columns [0, r), Bm = [r, r + 16),
+ *                           Cm = [r + 16, r + 32) in place and evaluates
+ *                               delta[t][d] = softplus(dt_b[d] + sum_j dt[t][j] dt_w[d][j])
+ *                           as one fmaf chain over j = 0 .. r - 1 starting from 0, the bias added last, once per (token,
+ *                           channel) in the staging prologue of both passes: no delta_raw tensor, no column copy.  Same lane
+ *                           mapping, chunking (ds6g_selective_scan_chunk) and recurrences as the layer's scan.  Three launches
+ *                           for all directions (state pass, carry, emit pass), one when L fits a single chunk.  The
+ *                           chunk-start states and delta sums live in ws: ds6g_mamba_scan_fwd_grouped_workspace_size
+ *                           (bytes; host only, 0 for a non-positive argument; a call on exactly that size inside poisoned
+ *                           moats and the refusal of one byte less: tests/test_mamba_infer_gpu.py / _cpu.py).
+ * Supported: D % 128 == 0, r % 4 == 0, 4 <= r <= 32, B, L >= 1, ndir * B <= 65535, pointers 16-byte aligned.  Anything else,
+ * a null operand or a bad stride returns DS6G_ERR_ARG, an undersized workspace DS6G_ERR_WORKSPACE, before any HIP call.
+ * No float atomics: two runs are bit-identical, and an ndir = 2 launch equals the two ndir = 1 launches bit for bit. */
+size_t ds6g_mamba_scan_fwd_grouped_workspace_size(int B, int L, int D, int ndir);
+int ds6g_mamba_conv_fwd_grouped(const ds6g_mamba_conv_dir* dirs, int ndir, int B, int L, int D, void* stream);
+int ds6g_h16_mamba_conv_fwd_grouped(int st16, const ds6g_mamba_conv_dir* dirs, int ndir, int B, int L, int D, void* stream);
+int ds6g_mamba_scan_fwd_grouped(const ds6g_mamba_scan_dir* dirs, int ndir, int B, int L, int D, int r, void* ws,
+                                size_t ws_bytes, void* stream);
+int ds6g_h16_mamba_scan_fwd_grouped(int st16, const ds6g_mamba_scan_dir* dirs, int ndir, int B, int L, int D, int r, void* ws,
+                                    size_t ws_bytes, void* stream);
+
 /* ---- mamba_fusion.hip : the bi-branch Mamba fusion stage around the Mamba layer, fp32 (mambafuser_seq.py:74-231) -------
  * Pointers 16-byte aligned, row strides (ld_*) in floats and multiples of 4; bad arguments return DS6G_ERR_ARG before
  * anything is launched.  No float atomics: every sum has a fixed order, two runs are bit-identical.

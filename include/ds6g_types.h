@@ -20,6 +20,28 @@ typedef struct {
     int frames_per_sample, mod_off;
 } ds6g_map_desc;
 
+/* one direction of the grouped forward-only Mamba kernels (ds6g_mamba_conv_fwd_grouped / ds6g_mamba_scan_fwd_grouped and
+ * their ds6g_h16_ forms): a launch covers ndir = 1 or 2 of them, each with operands, row strides and walk direction of its own */
+#define DS6G_MAMBA_MAX_DIR 2
+typedef struct {
+    const void* x;     /* [B L][D] of the storage type, a column block of a wider buffer: row stride ld_x elements */
+    const float* w;    /* conv1d.weight [D][1][4] */
+    const float* bias; /* conv1d.bias [D] */
+    void* y;           /* [B L][D] of the storage type, contiguous */
+    int ld_x, reverse;
+} ds6g_mamba_conv_dir;
+typedef struct {
+    const void* u;      /* the conv's output xc, [B L][D] of the storage type, row stride ld_u elements */
+    const void* z;      /* the gate half of in_proj's output, same type, row stride ld_z */
+    const float* x_dbl; /* fp32 [B L][>= r + 32], row stride ld_x: dt = columns [0, r), Bm = [r, r + 16), Cm = [r + 16, r + 32) */
+    const float* dt_w;  /* dt_proj.weight [D][r] */
+    const float* dt_b;  /* dt_proj.bias [D] */
+    const float* A_log; /* [D][16] */
+    const float* D;     /* [D] */
+    void* y;            /* [B L][D] of the storage type, contiguous */
+    int ld_u, ld_z, ld_x, reverse;
+} ds6g_mamba_scan_dir;
+
 /* ---- the launch plan of one attention call (ds6g_attention_plan; csrc/attention.hip plans every call with it, then runs it) */
 #define DS6G_ATTN_MAX_STEPS 8
 /* operand storage of the three entry-point pairs */
