@@ -1405,3 +1405,63 @@ def pool_rows3_bwd(drows, dfeats_in, dfeats):
     _launch(lib().pool_rows3_bwd, lib().h16_pool_rows3_bwd, dt, _p(drows), *(_p(t) for t in dfeats_in),
             *(_p(t) for t in dfeats), N, C)
     return dfeats
+
+
+# ---- radar cube -> range-angle / range-velocity maps (csrc/radar.hip).  The caller owns every buffer; the C side gets each
+# one's length in floats and refuses a short one before any launch ----
+RADAR_SAMPLES, RADAR_CHIRPS, RADAR_BINS, RADAR_MAX_ANTENNAS = 256, 128, 256, 8
+
+
+def radar_scratch(N, A, device):
+    """-> (R, raw, part): the scratch of the three radar launches for N frames of A antennas"""
+    return (torch.empty((N, A, RADAR_SAMPLES, RADAR_CHIRPS, 2), dtype=F32, device=device),
+            torch.empty((N, 2, RADAR_BINS, RADAR_BINS), dtype=F32, device=device),
+            torch.empty((N, RADAR_BINS, 2, 2), dtype=F32, device=device))
+
+
+def _chk_cube(cube):
+    """cube: [N, A, 256, 128, 2] fp32 = torch.view_as_real of the complex64 cubes"""
+    _chk(cube)
+    N, A = cube.shape[:2]
+    assert tuple(cube.shape) == (N, A, RADAR_SAMPLES, RADAR_CHIRPS, 2) and N >= 1 and 1 <= A <= RADAR_MAX_ANTENNAS, tuple(cube.shape)
+    return N, A
+
+
+def radar_range_fft(cube, R):
+    """R[n, a, r, k] = FFT over the 256 samples of cube[n, a, :, k] (complex64 as interleaved floats, [N, A, 256, 128, 2])"""
+    N, A = _chk_cube(cube)
+    _chk(R, N, A, RADAR_SAMPLES, RADAR_CHIRPS, 2)
+    lib().radar_range_fft(_p(cube), cube.numel(), _p(R), R.numel(), N, A, RADAR_SAMPLES, RADAR_CHIRPS, _stream())
+    return R
+
+
+def radar_maps_raw(R, raw, part, add_velocity=True):
+    """raw[n, 0] = un-normalised range-angle map, raw[n, 1] = range-velocity map (only with add_velocity) of the range spectra
+    R [N, A, 256, 128, 2]; part [N, 256, 2, 2] = (min, max) of every map row"""
+    N, A = _chk_cube(R)
+    _chk(raw, N, 2, RADAR_BINS, RADAR_BINS)
+    _chk(part, N, RADAR_BINS, 2, 2)
+    lib().radar_maps_raw(_p(R), R.numel(), _p(raw), raw.numel(), _p(part), part.numel(), N, A, RADAR_SAMPLES, RADAR_CHIRPS,
+                         2 if add_velocity else 1, _stream())
+    return raw, part
+
+
+def radar_finish(raw, part, dst, t=0, add_velocity=True, flip=False):
+    """min-max normalise each map of each frame and write it out.  dst [N * S, 256, 256, Cd] (NHWC): frame n goes to row
+    n * S + t, channel 0 angle, 1 velocity, the other channels zero.  dst [N, 1 | 2, 256, 256] (NCHW, as many channels as maps):
+    the reference's own stacked map format"""
+    N = raw.shape[0]
+    nch = 2 if add_velocity else 1
+    _chk(raw, N, 2, RADAR_BINS, RADAR_BINS)
+    _chk(part, N, RADAR_BINS, 2, 2)
+    _chk(dst)
+    assert dst.dim() == 4, tuple(dst.shape)
+    if tuple(dst.shape[2:]) == (RADAR_BINS, RADAR_BINS):
+        assert tuple(dst.shape[:2]) == (N, nch) and t == 0, (tuple(dst.shape), N, nch, t)
+        Cd, S, planar = nch, 1, 1
+    else:
+        Cd, S, planar = dst.shape[3], dst.shape[0] // N, 0
+        assert tuple(dst.shape) == (N * S, RADAR_BINS, RADAR_BINS, Cd) and Cd >= nch and 0 <= t < S, (tuple(dst.shape), N, nch, t)
+    lib().radar_finish(_p(raw), raw.numel(), _p(part), part.numel(), _p(dst), dst.numel(), N, nch, Cd, S, t, int(bool(flip)),
+                       planar, _stream())
+    return dst

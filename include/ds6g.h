@@ -369,6 +369,26 @@ int ds6g_lidar_bev_finish(unsigned* counts, float* dst, int B, int nbins, int Cd
 int ds6g_soft_beam_target(const int* beamidx, float* target, int* beamidx_out, int B, int nbeams, int flip,
                           void* stream);
 
+/* ---- radar.hip : raw radar cube -> range-angle / range-velocity maps, the offline numpy step of the reference
+ * (Data_Preprocessing/Radar_data_preprocessing.py:7-23,41-42), for N frames per launch.  cube: [N][A][256][128] complex64
+ * as interleaved floats (antenna, sample, chirp); S must be 256, K 128, 1 <= A <= 8; cube, R and a dst with Cd == 4 must
+ * be 16-byte aligned.  Every buffer comes with its length in floats and a short one is refused before any launch; the
+ * caller owns the scratch: R N*A*256*128*2 floats, raw N*2*256*256, part N*256*4.
+ * radar_range_fft: R[n][a][r][k] = sum_s cube[n][a][s][k] e^(-2 pi i r s / 256).
+ * radar_maps_raw: raw[n][0][r][th] = sum_k |sum_a (R[n][a][r][k] - mean_k R[n][a][r][:]) e^(-2 pi i th a / 256)| and, when
+ *   nch == 2, raw[n][1][r][v] = sum_a |sum_k R[n][a][r][k] e^(-2 pi i v k / 256)| (th, v < 256); part[n][r][c][0 / 1] =
+ *   min / max of row r of map c.  nch == 1 leaves plane 1 and its partials untouched.
+ * radar_finish: (map - min) / (max - min) per map and frame (a constant map is NaN, as in numpy) into frame slot t of an
+ *   NHWC xCd tensor dst[(n*frames_per_sample + t)][r][w][Cd], channel 0 angle, 1 velocity, channels nch..Cd-1 zero; with
+ *   planar != 0 (Cd == nch, frames_per_sample == 1) dst is [N][nch][256][256] instead.  flip mirrors the w axis
+ *   (data2_seq.py:144-152).  No float atomics anywhere: results are bit-reproducible. */
+int ds6g_radar_range_fft(const float* cube, long cube_elems, float* R, long r_elems, int N, int A, int S, int K,
+                         void* stream);
+int ds6g_radar_maps_raw(const float* R, long r_elems, float* raw, long raw_elems, float* part, long part_elems, int N,
+                        int A, int S, int K, int nch, void* stream);
+int ds6g_radar_finish(const float* raw, long raw_elems, const float* part, long part_elems, float* dst, long dst_elems,
+                      int N, int nch, int Cd, int frames_per_sample, int t, int flip, int planar, void* stream);
+
 /* ---- gru.hip : autoregressive GRU beam-sequence head of the 30->5 variant, model2_seq_30to5.py:842-862:
  * x = 0, h = h0 (the join output); T times: h = GRUCell(x, h); x = x + Linear(h); pred[:, t] = x.  H must be 64.
  * w_ih / w_hh: [3H][H] (gate rows r, z, n as in nn.GRUCell), b_ih / b_hh: [3H], w_out: [H][H], b_out: [H].
