@@ -21,6 +21,7 @@
 // image: whole 256/512-B rows per wave-instruction and 8 conflict-free ds_read_b32 per fragment.
 #include "common.h"
 #include "gemm_plan.h"
+#include <type_traits>
 #include <vector>
 
 extern int g_ds6g_attn_fused128;  // attention.hip: hd = 128 backward with the fused dK + dV kernel (experiment)
@@ -44,6 +45,14 @@ GCLK_STORAGE(g_igemm_clk, g_igemm_wg, ds6g_igemm_clocks_read)
 namespace {
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
+
+// x, but a value the compiler knows nothing about: the epilogue's store offsets are derived from such a copy of the block
+// base, so they are recomputed next to each store (one add) instead of being shared with the load offsets and kept alive,
+// 16 registers per block, from the loads to the stores
+__device__ __forceinline__ unsigned opaque_u32(unsigned x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
 
 struct IgemmParams {
     const float* a_src;
@@ -617,6 +626,40 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams pin) {
             bias_pre[j] = (p.bias && col < p.Ng) ? p.bias[col] : 0.f;
         }
     }
+    // The epilogue's per-element operands (ReLU mask, residual, previous output) are uniform over the launch: which of them
+    // exist is decided ONCE here, never per element (a per-element "load or not" on a runtime flag makes hipcc branch around
+    // every load and wait vmcnt(0) behind each one: one memory round trip per element and operand, back to back).
+    // 64 x 64 tiles also fetch the FIRST operand that exists here, ahead of the k loop, like the bias: 16 registers that the
+    // LDS-bound occupancy leaves free.  The loads are branch-free - an absent operand (and the strided data gradient, whose
+    // rows are remapped) reads through an empty descriptor, which returns zeros without touching memory.  They sit AHEAD of
+    // the first DMA, so the k loop's counted waits (which only look at the youngest entries of the queue) are not disturbed.
+    // (the split-bf16 operand modes, the 32-column k-tiles and wgrad have no registers to spare in the loop: they load after
+    // the last k-step)
+    constexpr bool EPI_PRE = EPI && MODE != MODE_WGRAD && TM == 1 && TN == 1 && BF == 0 && BK == 16;
+    // registers per batch of epilogue loads (all operands together): what fits beside the accumulators without costing a
+    // resident wave (resource report of every instantiation: profiles/igemm_epilogue.txt)
+    constexpr int EPI_BATCH = MODE == MODE_WGRAD ? 4 : TM * TN == 2 ? 32 : 16;
+    const int epi_sel = (p.mask_src ? 1 : 0) | (p.residual ? 2 : 0) | (p.accumulate ? 4 : 0);
+    const bool epi_remap = MODE == MODE_DGRAD && p.hstep != 1;
+    // byte offset of register 0 of the (i, j) 32 x 32 block in an [Mg][Ng] tensor; columns >= Ng point past every descriptor
+    auto blk_base = [&](int i, int j) -> unsigned {
+        const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
+        const int row0 = m0 + wm * (BM / 2) + i * 32 + 4 * (lane >> 5);
+        return col < p.Ng ? ((unsigned)row0 * (unsigned)p.Ng + (unsigned)col) * 4u : OOB_OFF;
+    };
+    // accumulator registers in flat order f = (i * TN + j) * 16 + r; row of register r inside its block (without the lane part)
+    auto reg_row = [](int f) -> unsigned { return (unsigned)((f & 3) + 8 * ((f >> 2) & 3)); };
+    float* outp = p.out + ((MODE == MODE_WGRAD) ? (size_t)split * p.split_stride : (size_t)0);
+    [[maybe_unused]] float epi_pre[16];
+    if (EPI_PRE) {
+        const float* src = p.mask_src ? p.mask_src : p.residual ? p.residual : outp;
+        const unsigned bytes = (epi_sel && !epi_remap) ? (unsigned)p.Mg * (unsigned)p.Ng * 4u : 0u;
+        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), 0, bytes, 0x00020000);
+        const unsigned base = blk_base(0, 0), rowbytes = (unsigned)p.Ng * 4u;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            epi_pre[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, base + (unsigned)((r & 3) + 8 * (r >> 2)) * rowbytes, 0, 0));
+    }
     GCLK(g_igemm_clk, 0);           // set-up
 #pragma unroll
     for (int u = 0; u < NS - 1; ++u)
@@ -635,38 +678,48 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams pin) {
     }
 
     // ---- epilogue: D[row][col], col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) ---------
-    float* outp = p.out + ((MODE == MODE_WGRAD) ? (size_t)split * p.split_stride : (size_t)0);
     if (MODE == MODE_WGRAD && do_csum && m0 + tid < p.Mg) outp[(size_t)p.Mg * p.Ng + m0 + tid] = csum;
+    constexpr int NREG = TM * TN * 16;
     if (EPI == 0) {
         // rows >= Mg land beyond the descriptor (Mg*Ng*4 bytes) and are dropped by the hardware range check;
         // columns >= Ng are sent there explicitly.  No divergent control flow, one add per store.
         const auto o_rsrc = __builtin_amdgcn_make_buffer_rsrc(outp, 0, (unsigned)p.Mg * (unsigned)p.Ng * 4u, 0x00020000);
         const unsigned rowbytes = (unsigned)p.Ng * 4u;
+        unsigned base[TM * TN];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
+        for (int b = 0; b < TM * TN; ++b) base[b] = ((p.dbg & 8) && b) ? OOB_OFF : blk_base(b / TN, b % TN);
+        // ACC is a compile-time property of the body: a batch of loads of the previous output is in flight before its first add
+        auto store_tiles = [&](auto acc_c) {
+            constexpr bool ACC = decltype(acc_c)::value;
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
-                const int row0 = m0 + wm * (BM / 2) + i * 32 + 4 * khalf;
-                const unsigned base = (col < p.Ng && !((p.dbg & 8) && (i | j)))
-                                          ? (unsigned)row0 * rowbytes + (unsigned)col * 4u
-                                          : OOB_OFF;
+            for (int f0 = 0; f0 < NREG; f0 += EPI_BATCH) {
+                [[maybe_unused]] float ov[EPI_BATCH];
+                unsigned sbase = 0;
+                // the scheduler must not pull the next batch's accumulator reads and offsets up into this one: it would copy all
+                // TM x TN x 16 accumulators out of the AGPRs at once and cost a resident wave
+                __builtin_amdgcn_sched_barrier(0);
+                if (ACC) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const unsigned off = base + (unsigned)((r & 3) + 8 * (r >> 2)) * rowbytes;
-                    float v = acc[i][j][r];
-                    // the b32 builtins move raw bits (unsigned): bit-cast, do not convert
-                    if (MODE != MODE_WGRAD && p.accumulate)
-                        v += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(o_rsrc, off, 0, 0));
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), o_rsrc, off, 0, 0);
+                    for (int f = f0; f < f0 + EPI_BATCH; ++f)  // the b32 builtins move raw bits (unsigned): bit-cast, do not convert
+                        ov[f - f0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(o_rsrc, base[f >> 4] + reg_row(f) * rowbytes, 0, 0));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int f = f0; f < f0 + EPI_BATCH; ++f) {
+                    if (f == f0 || (f & 15) == 0) sbase = opaque_u32(base[f >> 4]);
+                    float v = acc[(f >> 4) / TN][(f >> 4) % TN][f & 15];
+                    if (ACC) v += ov[f - f0];
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), o_rsrc, sbase + reg_row(f) * rowbytes, 0, 0);
                 }
             }
-        }
+        };
+        if (MODE != MODE_WGRAD && p.accumulate) store_tiles(std::true_type{});
+        else store_tiles(std::false_type{});
         GCLK(g_igemm_clk, 6);   // epilogue (stores issued)
         GCLK_END(g_igemm_clk, g_igemm_wg);
         return;
     }
-    if (!(MODE == MODE_DGRAD && p.hstep != 1)) {
+    if (!epi_remap) {
         // full epilogue with the same branch-free addressing: mask, residual and output all have the output's
         // [Mg][Ng] shape, so ONE 32-bit byte offset serves every per-element tensor and out-of-tile rows / columns fall
         // off the buffer descriptors (loads return 0, stores are dropped)
@@ -675,57 +728,148 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams pin) {
         const auto m_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.mask_src ? p.mask_src : outp), 0, nbytes, 0x00020000);
         const auto r_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.residual ? p.residual : outp), 0, nbytes, 0x00020000);
         const unsigned rowbytes = (unsigned)p.Ng * 4u;
+        unsigned base[TM * TN], e0[TM * TN];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
+        for (int b = 0; b < TM * TN; ++b) {
+            base[b] = blk_base(b / TN, b % TN);
+            e0[b] = (unsigned)(m0 + wm * (BM / 2) + (b / TN) * 32 + 4 * khalf) * (unsigned)p.Ng +
+                    (unsigned)(n0 + wn * (BN / 2) + (b % TN) * 32 + (lane & 31));  // element index (dropout counter)
+        }
+        // One body per (has mask, has residual, has accumulate), chosen once from epi_sel: inside a body no load sits behind
+        // a branch.  A batch issues every load of every operand first (the 16 registers of a 32 x 32 block with one operand,
+        // two blocks on the 128 x 64 tile; fewer registers of each with more operands), then does the arithmetic - per element
+        // in the unfused order: + bias, ReLU 1, mask, dropout, + residual, + out, ReLU 2 - then the stores.  With EPI_PRE the
+        // first operand that exists is already in epi_pre.
+        auto epi_tiles = [&](auto hm_c, auto hr_c, auto ha_c) {
+            constexpr bool HM = decltype(hm_c)::value, HR = decltype(hr_c)::value, HA = decltype(ha_c)::value;
+            constexpr int PRE = !EPI_PRE ? 0 : HM ? 1 : HR ? 2 : HA ? 3 : 0;  // which operand epi_pre holds
+            constexpr int NLOAD = HM + HR + HA - (PRE ? 1 : 0);               // operands loaded here
+            constexpr int RB = NLOAD <= 1 ? EPI_BATCH : NLOAD == 2 ? EPI_BATCH / 2 : EPI_BATCH / 4;  // registers per batch
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
-                const int row0 = m0 + wm * (BM / 2) + i * 32 + 4 * khalf;
-                const bool cok = col < p.Ng;
-                const float bias = bias_pre[j];
-                const unsigned base = cok ? (unsigned)row0 * rowbytes + (unsigned)col * 4u : OOB_OFF;
-                const unsigned e0 = (unsigned)row0 * (unsigned)p.Ng + (unsigned)col;  // element index (dropout counter)
+            for (int f0 = 0; f0 < NREG; f0 += RB) {
+                [[maybe_unused]] float mv[RB], rv[RB], ov[RB];
+                unsigned sbase = 0;
+                __builtin_amdgcn_sched_barrier(0);  // one batch at a time (see store_tiles)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const unsigned dr = (unsigned)((r & 3) + 8 * (r >> 2));
-                    const unsigned off = base + dr * rowbytes;
-                    float v = acc[i][j][r] + bias;
+                for (int f = f0; f < f0 + RB; ++f) {
+                    const unsigned off = base[f >> 4] + reg_row(f) * rowbytes;
+                    if (HM) mv[f - f0] = PRE == 1 ? epi_pre[f & 15] : __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(m_rsrc, off, 0, 0));
+                    if (HR) rv[f - f0] = PRE == 2 ? epi_pre[f & 15] : __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, off, 0, 0));
+                    if (HA) ov[f - f0] = PRE == 3 ? epi_pre[f & 15] : __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(o_rsrc, off, 0, 0));
+                }
+                if (NLOAD) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int f = f0; f < f0 + RB; ++f) {
+#pragma clang fp contract(off)  // v * drop_scale + residual stays a multiply and an add, as in the unfused chain
+                    if (f == f0 || (f & 15) == 0) sbase = opaque_u32(base[f >> 4]);
+                    float v = acc[(f >> 4) / TN][(f >> 4) % TN][f & 15] + bias_pre[(f >> 4) % TN];
                     if (p.relu == 1) v = fmaxf(v, 0.f);
-                    if (p.mask_src) v = (__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(m_rsrc, off, 0, 0)) > 0.f) ? v : 0.f;
+                    if (HM) v = (mv[f - f0] > 0.f) ? v : 0.f;
                     if (p.drop_thr)
-                        v = ds6g_keep(p.seed, p.seed_off + (uint64_t)(e0 + dr * (unsigned)p.Ng), p.drop_thr) ? v * p.drop_scale : 0.f;
-                    if (p.residual) v += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, off, 0, 0));
-                    if (p.accumulate) v += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(o_rsrc, off, 0, 0));
+                        v = ds6g_keep(p.seed, p.seed_off + (uint64_t)(e0[f >> 4] + reg_row(f) * (unsigned)p.Ng), p.drop_thr) ? v * p.drop_scale : 0.f;
+                    if (HR) v += rv[f - f0];
+                    if (HA) v += ov[f - f0];
                     if (p.relu == 2) v = fmaxf(v, 0.f);  // activation after the residual add (BasicBlock tail)
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), o_rsrc, off, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), o_rsrc, sbase + reg_row(f) * rowbytes, 0, 0);
                 }
             }
+        };
+        const std::true_type T{};
+        const std::false_type F{};
+        switch (epi_sel) {
+            case 0: epi_tiles(F, F, F); break;
+            case 1: epi_tiles(T, F, F); break;
+            case 2: epi_tiles(F, T, F); break;
+            case 3: epi_tiles(T, T, F); break;
+            case 4: epi_tiles(F, F, T); break;
+            case 5: epi_tiles(T, F, T); break;
+            case 6: epi_tiles(F, T, T); break;
+            default: epi_tiles(T, T, T); break;
         }
         GCLK(g_igemm_clk, 6);   // epilogue (stores issued)
         GCLK_END(g_igemm_clk, g_igemm_wg);
         return;
     }
-    // strided dgrad: rows of the parity-class sub-grid scatter to full-resolution pixels
+    // strided dgrad: rows of the parity-class sub-grid scatter to full-resolution pixels.  The same scheme: one body per
+    // "accumulate or not", branch-free addressing through a descriptor over the whole [N][H][W][Ng] tensor (rows >= Mg and
+    // columns >= Ng are sent past it).  A register's row is 8 * (r >> 2) + (r & 3) + const: the divisions run once per group
+    // of four consecutive rows, the rows after the first step (ww, hh, image) with compare-and-wrap.  A batch is two such
+    // groups (one on the 128 x 128 tile) over all TN column blocks: its loads are all issued before its first add.
+    constexpr int SG = TM * TN >= 4 ? 1 : 2;
+    const auto s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        outp, 0, (unsigned)p.N * (unsigned)p.H * (unsigned)p.W * (unsigned)p.Ng * 4u, 0x00020000);
+    auto scatter_tiles = [&](auto acc_c) {
+        constexpr bool ACC = decltype(acc_c)::value;
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
+        for (int i = 0; i < TM; ++i) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
-            if (col >= p.Ng) continue;
+            for (int g0 = 0; g0 < 4; g0 += SG) {
+                unsigned off[TN][4 * SG];
+                [[maybe_unused]] float ov[TN][4 * SG];
+                __builtin_amdgcn_sched_barrier(0);  // one batch at a time (see store_tiles)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                if (row >= p.Mg) continue;
-                const int ww = row % p.Ws;
-                const int t = row / p.Ws;
-                const int hh = t % p.Hs;
-                const size_t orow = ((size_t)(t / p.Hs) * p.H + p.h0 + hh * p.hstep) * p.W + p.w0 + ww * p.wstep;
-                const size_t o = orow * p.Ng + col;
-                float v = acc[i][j][r];
-                if (p.accumulate) v += outp[o];
-                outp[o] = v;
+                for (int g = g0; g < g0 + SG; ++g) {
+                    const int rg = m0 + wm * (BM / 2) + i * 32 + 8 * g + 4 * khalf;
+                    int ww = rg % p.Ws;
+                    const int t = rg / p.Ws;
+                    int hh = t % p.Hs;
+                    int n = t / p.Hs;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const unsigned orow = (unsigned)((n * p.H + p.h0 + hh * p.hstep) * p.W + p.w0 + ww * p.wstep);
+#pragma unroll
+                        for (int j = 0; j < TN; ++j) {
+                            const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
+                            const int e = 4 * (g - g0) + q;
+                            off[j][e] = (rg + q < p.Mg && col < p.Ng) ? (orow * (unsigned)p.Ng + (unsigned)col) * 4u : OOB_OFF;
+                            if (ACC) ov[j][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(s_rsrc, off[j][e], 0, 0));
+                        }
+                        if (++ww == p.Ws) {
+                            ww = 0;
+                            if (++hh == p.Hs) { hh = 0; ++n; }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4 * SG; ++e) {
+                        float v = acc[i][j][4 * g0 + e];
+                        if (ACC) v += ov[j][e];
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), s_rsrc, off[j][e], 0, 0);
+                    }
             }
         }
+    };
+    const size_t s_bytes = (size_t)p.N * p.H * p.W * p.Ng * 4;
+    if (s_bytes > (size_t)OOB_OFF) {
+        // the four classes together may exceed what a 32-bit descriptor offset (and OOB_OFF) can address although one class
+        // does not: such a tensor takes the pointer form, one element after the other
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
+                if (col >= p.Ng) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+                    if (row >= p.Mg) continue;
+                    const int ww = row % p.Ws;
+                    const int t = row / p.Ws;
+                    const int hh = t % p.Hs;
+                    const size_t orow = ((size_t)(t / p.Hs) * p.H + p.h0 + hh * p.hstep) * p.W + p.w0 + ww * p.wstep;
+                    const size_t o = orow * p.Ng + col;
+                    float v = acc[i][j][r];
+                    if (p.accumulate) v += outp[o];
+                    outp[o] = v;
+                }
+            }
+        }
+    } else if (p.accumulate) {
+        scatter_tiles(std::true_type{});
+    } else {
+        scatter_tiles(std::false_type{});
     }
     GCLK(g_igemm_clk, 6);
     GCLK_END(g_igemm_clk, g_igemm_wg);
